@@ -8,21 +8,27 @@ app/renderer.cpp:131-158), synthetic seeded inputs.
 A STEP is one whole frame job of the config: the first frame after a camera move -- primary hits of the
 camera (k_primary), `spp` render passes with fresh glibc-rand() seeds in launches of 64 passes each
 (k_bounce + k_env_fixup + k_commit), resolve [N > 1: of the rank's own tiles, then ONE RCCL all-gather of RGBA8 tiles]
-to the RGBA8 frame.  `--steps K` times exactly K such jobs between barrier + synchronize brackets; because K
-jobs of the headline config take only K x 5.5 ms, the K-step region is repeated until at least
-MIN_TIMED_SECONDS have been measured and the MEDIAN region is reported (every region's time is the max over
-ranks), so the number does not depend on --steps and does not rest on a 2 ms measurement.  Inputs (volume,
-SDF, env map, step bytes and hit records) are resident in HBM before the clock starts; the frame stays in HBM.
+to the RGBA8 frame.  `--steps K` times exactly K such jobs in ONE region between barrier + synchronize brackets (the
+region's time is the max over ranks); `ms_per_step` is that time / K.  Inputs (volume, SDF, env map, step bytes and
+hit records) are resident in HBM before the clock starts; the frame stays in HBM.  `--dump-outputs DIR` writes the
+RGBA8 frame of the last timed job (what a caller of the path receives) as DIR/frame.npy in float32 after the timed
+region; the inputs and seeds depend on the arguments only, so two builds can be compared output for output.
 Consecutive frame jobs alternate between two HIP streams (--frames-in-flight, each stream with its own
 accumulation and frame buffers): every persistent launch ends with ~0.3 ms in which its last waves wait for
 their longest samples, and the next frame's primary hits and first waves fill the GPU meanwhile (+4 % on one
-GPU).  The per-kernel durations of the roofline are measured in a separate region with ONE frame at a time.
+GPU).
 
 `--gpus N` starts its own N ranks (torch.distributed.run as a child process, before this process touches a
 GPU) unless it already runs under a launcher; the ranks share ONE frame as interleaved 8x8 image tiles
 (strong scaling).  On a box with fewer than N GPUs the same code path is rehearsed on one GPU over gloo.
 
-The JSON line also carries
+A plain run sets up, warms up (including the untimed choice of frame lanes), times the K jobs and prints the line.
+With `--full` the JSON line also carries
+  repeated_regions
+                 the K-step region repeated until at least MIN_TIMED_SECONDS have been measured, median region
+                 (so that a figure does not rest on a 2 ms measurement);
+  one_frame_at_a_time (in config)
+                 the same jobs strictly serial on one stream; the per-kernel durations of the roofline come from it;
   roofline       the dominant kernel k_bounce against the 8 TB/s HBM peak, counted with the bytes k_bounce
                  itself performs (oracle counters of the bounce phase only); per-kernel figures and the
                  SURVEY 8d contract figure (whole path, whole job) beside it;
@@ -45,7 +51,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import math
 import os
 import socket
 import statistics
@@ -59,8 +64,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
-MIN_TIMED_SECONDS = 0.5    # the K-step region is repeated until this much has been timed
+MIN_TIMED_SECONDS = 0.5    # --full: the K-step region is repeated until this much has been timed
 MAX_REGIONS = 60
+CALIBRATION_STEPS = 40     # jobs per region of the untimed choice of frame lanes (independent of --steps)
+DUMP_LIMIT_BYTES = 64 << 20
 
 PRESETS = {
     # BASELINE.json configs[1..4]; the launch shape (64 passes per launch) is the same for every one
@@ -86,6 +93,26 @@ def host_threads():
     except (OSError, ValueError):
         pass
     return max(1, min(n, int(os.environ.get("BENCH_CPU_THREADS", "16"))))
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every array of `outputs` ({name: array [..., channels]}) as out_dir/<name>.npy in float32.  When they
+    would exceed DUMP_LIMIT_BYTES together, an array's share is a fixed, seeded sample of its pixels: <name>_sample.npy
+    [n, channels] and the flat pixel indices drawn, <name>_sample_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in outputs.values())
+    share = DUMP_LIMIT_BYTES // max(1, len(outputs))
+    for name, a in outputs.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total <= DUMP_LIMIT_BYTES:
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            continue
+        rows = a.reshape(-1, a.shape[-1])
+        keep = min(len(rows), share // (rows.shape[1] * 4 + 8))
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), size=keep, replace=False))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), rows[idx])
+        np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+    log("[bench] outputs of the last timed step written to %s" % out_dir)
 
 
 def free_port():
@@ -371,6 +398,8 @@ def run_voxel_multi(args, ctx, kernel, d_vol, d_sdf, d_env, d_frame, pos, cdir, 
     for j in range(WU):
         region(j, 1)
     elapsed = max_over_ranks([region(WU, K)])[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frame": d_frame.pull()})
     counts = (cache.view(-1, 2)[:, 1] >> 16) & 0xFFFF
     if rank == 0:
         print(json.dumps({
@@ -381,7 +410,7 @@ def run_voxel_multi(args, ctx, kernel, d_vol, d_sdf, d_env, d_frame, pos, cdir, 
                                    "the 256-token rule applied to the global count" % (args.config - 1, N, W, H, SPP),
                        "accumulation": "replicated world-space cache; per pass one all-gather of the hit pixels' contributions "
                                        "(12 B each) + deterministic capped scatter-add on every rank (tiles.VoxelExchange)",
-                       "sdf_build_s": round(sdf_build_s, 5), "sdf_layers": n_layers,
+                       "sdf_build_s": round(sdf_build_s, 5) if sdf_build_s is not None else None, "sdf_layers": n_layers,
                        "voxels_touched": int((counts > 0).sum().item()), "voxels_at_cap": int((counts >= 256).sum().item()),
                        "max_count": int(counts.max().item())},
         }), flush=True)
@@ -405,10 +434,15 @@ def main():
     ap.add_argument("--spp", type=int, default=None, help="render passes per frame job")
     ap.add_argument("--env", type=int, nargs=2, default=[4096, 2048])
     ap.add_argument("--tf", choices=["default", "gradient"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated regions, the serial region with per-kernel durations, the roofline, the "
+                         "CPU baseline, the SDF build time and the secondary measurements (off: only what the headline needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the RGBA8 frame of the last timed job as DIR/frame.npy (float32) after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
-    ap.add_argument("--no-secondary", action="store_true", help="skip end_to_end / drop_in_path / reference_exact_mode")
-    ap.add_argument("--single-region", action="store_true", help="time ONE K-step region (profiling runs)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without end_to_end / drop_in_path / reference_exact_mode")
+    ap.add_argument("--single-region", action="store_true", help="no frame-lane calibration, no repeated regions (profiling runs)")
     ap.add_argument("--accumulation", choices=["image", "voxel"], default="image",
                     help="image: float4 per pixel + one all-gather (the headline); voxel: the reference's world-space "
                          "cache, one pass per launch, contributions exchanged pass by pass under the global 256-token rule")
@@ -418,6 +452,8 @@ def main():
                          "frame buffers), so that the next frame's primary hits and first waves fill the GPU while the last "
                          "waves of the previous frame's persistent launch drain; 1 = strictly one frame after the other")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     preset = PRESETS[args.config]
     for key, val in preset.items():
         if getattr(args, key, None) is None:
@@ -497,15 +533,15 @@ def main():
     d_vol = ctx.image_from(vol)
     d_env = ctx.image_from(env, channels=4)
     d_sdf = ctx.image([N, N, N], 1, np.int8, (N, N, N))
-    ctx.sdf_build(d_vol, tf_source, d_sdf)  # warm (allocations)
+    n_layers = ctx.sdf_build(d_vol, tf_source, d_sdf)  # (--full: warm, allocations)
     torch.cuda.synchronize()
     sdf_times = []
-    for _ in range(3 if N <= 512 else 1):
+    for _ in range((3 if N <= 512 else 1) if args.full else 0):
         t0 = time.perf_counter()
         n_layers = ctx.sdf_build(d_vol, tf_source, d_sdf)
         torch.cuda.synchronize()
         sdf_times.append(time.perf_counter() - t0)
-    sdf_build_s = min(sdf_times)
+    sdf_build_s = min(sdf_times) if sdf_times else None
     d_frame = ctx.image([W, H], 4, np.uint8, (H, W, 4))
     kernel = ctx.kernel("ray_marching.cl", "render", tf_source)
 
@@ -559,7 +595,7 @@ def main():
     active = list(range(n_lanes))  # the lanes the frame jobs alternate over
 
     # seeds: the glibc rand() stream the never-seeded reference draws from, one per pass, continuing over the jobs
-    n_jobs_max = WU + 1 + K * (MAX_REGIONS + 6) + 96
+    n_jobs_max = WU + 1 + K * (MAX_REGIONS + 6) + 96 + 2 * len(lane_sets) * (CALIBRATION_STEPS + n_lanes)
     seed_stream = scene.glibc_rand(min(n_jobs_max * SPP, 4_000_000))
 
     def job_seeds(j):
@@ -606,51 +642,67 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
+    n_warm = max(WU + 1, n_lanes)  # warm-up jobs (every lane at least once: its work buffers get their final size)
+    calibrate = len(lane_sets) > 1 and not args.single_region
+    # the jobs a calibration takes: fixed in advance, so that the timed jobs (and their seeds) depend on the arguments only
+    n_calibration = (sum(len(v) for v in lane_sets.values()) + 2 * len(lane_sets) * CALIBRATION_STEPS) if calibrate else 0
     job = 0
     est = []
-    for _ in range(max(WU + 1, n_lanes)):  # warm-up jobs (every lane at least once: its work buffers get their final size)
+    for _ in range(n_warm):
         est.append(timed_region(job, 1))
         job += 1
     lane_calibration = None
-    if len(lane_sets) > 1 and not args.single_region and min(est) < 0.03:  # (jobs of 100 ms and more gain nothing either way)
-        # still warm-up, untimed as far as the result goes: the same K-job region with each set of lanes, twice
+    if calibrate and min(est) < 0.03:  # (jobs of 100 ms and more gain nothing either way)
+        # still warm-up, untimed as far as the result goes: a region of CALIBRATION_STEPS jobs with each set of lanes, twice
         lane_calibration = {}
         for name in list(lane_sets) * 2:
             active[:] = lane_sets[name]
             if name not in lane_calibration:
                 timed_region(job, len(active))  # (every lane of the set once first)
                 job += len(active)
-            t = timed_region(job, K) / K
-            job += K
+            t = timed_region(job, CALIBRATION_STEPS) / CALIBRATION_STEPS
+            job += CALIBRATION_STEPS
             lane_calibration[name] = min(t, lane_calibration.get(name, t))
         active[:] = lane_sets[min(lane_calibration, key=lane_calibration.get)]
     else:
         active[:] = list(range(n_lanes))
     untimed_jobs = job  # warm-up jobs + the lane calibration's
-    est_job = max_over_ranks([min(est)])[0]
-    regions = 1 if args.single_region else max(1, min(MAX_REGIONS, int(math.ceil(MIN_TIMED_SECONDS / max(est_job * K, 1e-6)))))
-    region_s = []
-    for _ in range(regions):
-        region_s.append(timed_region(job, K))
-        job += K
-    # the estimate came from single jobs, which do not overlap: add regions until MIN_TIMED_SECONDS really have been timed
-    # (the decision is taken on a value every rank agrees on)
-    while not args.single_region and len(region_s) < MAX_REGIONS and max_over_ranks([sum(region_s)])[0] < MIN_TIMED_SECONDS:
-        region_s.append(timed_region(job, K))
-        job += K
-    regions = len(region_s)
-    own_ms_headline = statistics.median(own_job_s[-regions:]) * 1e3
-    # kernel durations for the roofline: HIP events around every launch, in a separate region in which the frame jobs run
-    # strictly one after the other on one stream -- with two frames in flight a launch's events would also span the time it
-    # shares the GPU with the other frame's kernels
-    k_serial = max(2, min(K, 10))
-    ctx.set_timing(True)
-    serial_s = timed_region(job, k_serial, serial=True)
-    job += k_serial
-    timers = ctx.timing_read_all()
-    ctx.set_timing(False)
-    region_s = max_over_ranks(region_s)  # every region: the slowest rank's time
-    elapsed = statistics.median(region_s)
+    job = n_warm + n_calibration
+    # ---- the headline: exactly K jobs in one region
+    region_s = max_over_ranks([timed_region(job, K)])  # the slowest rank's time
+    job += K
+    own_ms_headline = own_job_s[-1] * 1e3
+    elapsed = region_s[0]
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed job (every rank holds the whole frame), before anything else runs on its lane
+        last = job - 1
+        dump_outputs(args.dump_outputs, {"frame": lanes[active[last % len(active)]]["frame"].pull()})
+
+    repeated = None
+    timers = None
+    if args.full:
+        if not args.single_region:
+            # the K-step region repeated until MIN_TIMED_SECONDS have been timed (the decision is taken on a value every rank agrees on)
+            rep_s = []
+            while len(rep_s) < MAX_REGIONS and max_over_ranks([sum(rep_s)])[0] < MIN_TIMED_SECONDS:
+                rep_s.append(timed_region(job, K))
+                job += K
+            rep_s = max_over_ranks(rep_s)  # every region: the slowest rank's time
+            med = statistics.median(rep_s)
+            repeated = {"what": "the headline's K-job region repeated until %.1f s had been timed; median region" % MIN_TIMED_SECONDS,
+                        "regions": len(rep_s), "steps_per_region": K, "value": round(W * H * SPP * K / med / 1e6, 3),
+                        "unit": "Msamples/s", "ms_per_step": round(med * 1e3 / K, 4), "seconds_median": round(med, 6),
+                        "seconds_min": round(min(rep_s), 6), "seconds_max": round(max(rep_s), 6),
+                        "seconds_total": round(sum(rep_s), 4)}
+        # kernel durations for the roofline: HIP events around every launch, in a separate region in which the frame jobs run
+        # strictly one after the other on one stream -- with two frames in flight a launch's events would also span the time it
+        # shares the GPU with the other frame's kernels
+        k_serial = max(2, min(K, 10))
+        ctx.set_timing(True)
+        serial_s = timed_region(job, k_serial, serial=True)
+        job += k_serial
+        timers = ctx.timing_read_all()
+        ctx.set_timing(False)
 
     samples_per_job = W * H * SPP
     value = samples_per_job * K / elapsed / 1e6
@@ -688,15 +740,15 @@ def main():
             "frames_in_flight": len(active),
             "persistent_grid_per_launch": ("half of the library's default (CLWH_TUNE_BLOCKS=1024): two launches co-reside" if active and active[0] in half_grid
                                            else os.environ.get("CLWH_TUNE_BLOCKS", "library default (2048 blocks)")),
-            "frames_in_flight_calibration": ({"what": "ms per job of an untimed warm-up region (best of two) with each set of frame lanes; the timed "
-                                              "regions use the fastest; the roofline's kernel durations come from single launches on the default grid",
+            "frames_in_flight_calibration": ({"what": "ms per job of an untimed warm-up region of %d jobs (best of two) with each set of frame lanes; "
+                                                      "the timed region uses the fastest; the roofline's kernel durations come from single launches on "
+                                                      "the default grid" % CALIBRATION_STEPS,
                                               **{k: round(v * 1e3, 4) for k, v in lane_calibration.items()}} if lane_calibration else None),
-            "one_frame_at_a_time": {"steps": k_serial, "ms_per_step": round(max_over_ranks([serial_s])[0] * 1e3 / k_serial, 4),
-                                    "note": "the same jobs strictly serial on one stream; the per-kernel durations of the roofline come from this region"},
-            "timed": {"regions": regions, "steps_per_region": K, "seconds_median": round(elapsed, 6),
-                      "seconds_min": round(min(region_s), 6), "seconds_max": round(max(region_s), 6),
-                      "seconds_total": round(sum(region_s), 4)},
-            "sdf_build_s": round(sdf_build_s, 5),
+            "one_frame_at_a_time": ({"steps": k_serial, "ms_per_step": round(max_over_ranks([serial_s])[0] * 1e3 / k_serial, 4),
+                                     "note": "the same jobs strictly serial on one stream; the per-kernel durations of the roofline come from this region"}
+                                    if args.full else None),
+            "timed": {"regions": 1, "steps_per_region": K, "seconds": round(elapsed, 6)},
+            "sdf_build_s": round(sdf_build_s, 5) if sdf_build_s is not None else None,
             "sdf_layers": n_layers,
             "hbm_in_use_gib": round((torch.cuda.mem_get_info(dev)[1] - torch.cuda.mem_get_info(dev)[0]) / 2 ** 30, 2),
             "derived_scene": dict(zip(("id", "bytes", "contexts_sharing_it"), ctx.scene_info())),
@@ -705,8 +757,11 @@ def main():
         },
     }
 
+    if args.full:
+        result["repeated_regions"] = repeated
+
     # ---- roofline + CPU baseline (oracle = checker / reported baseline only; rank 0)
-    if rank == 0:
+    if args.full and rank == 0:
         from oracle import orc_ffi
 
         sdf_host = d_sdf.pull()
@@ -815,7 +870,7 @@ def main():
         del osc
 
     # ---- the same job from a pose whose frame the volume fills (scene.close_camera): its own value and k_bounce roofline
-    if world == 1 and not args.no_secondary and rank == 0:
+    if args.full and world == 1 and not args.no_secondary and rank == 0:
         view["pos"], view["dir"] = scene.close_camera(N)
         timed_region(job, len(active))  # every lane once: work buffers grow to this view's hit count
         job += len(active)
@@ -856,7 +911,7 @@ def main():
         view["pos"], view["dir"] = pos, cdir
 
     # ---- end to end incl. the final frame readback (SURVEY 8d metric ii); same jobs, frame pulled after each
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         k2 = max(1, min(K, 10))
         # (a blocking pull after every job leaves one job on the GPU at a time: on one GPU they run on lane 0, whose launches take the
         # whole grid, whatever set of lanes the timed regions used)
@@ -869,7 +924,7 @@ def main():
                 "value": round(samples_per_job * k2 / t / 1e6, 3), "unit": "Msamples/s", "steps": k2,
                 "ms_per_step": round(t * 1e3 / k2, 4)}
 
-    if rank == 0 and world == 1 and not args.no_secondary and args.config in (2, 3):
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.config in (2, 3):
         # cap ON: the reference's own accumulation (256 tokens per voxel), the job's SPP passes one per launch
         result["reference_exact_mode"], exact_frame = run_voxel_single(ctx, kernel, d_vol, d_sdf, d_env, d_frame, pos, cdir, N, W, H,
                                                                        job_seeds(0), torch, ffi)

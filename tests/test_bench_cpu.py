@@ -49,3 +49,31 @@ def test_bench_refuses_to_run_without_a_gpu():
                          capture_output=True, text=True, env=env, timeout=600)
     assert two.returncode != 0                       # the self-spawned ranks fail loudly, and so does the parent
     assert "REHEARSAL" in two.stderr                 # fewer GPUs than ranks: it says so before starting them
+
+
+def test_dump_outputs_float32_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: small outputs are written whole in float32; beyond the limit a fixed, seeded sample of pixels + their indices"""
+    import numpy as np
+
+    b = _bench()
+    frame = np.random.default_rng(3).integers(0, 256, (30, 40, 4)).astype(np.uint8)
+    b.dump_outputs(str(tmp_path / "whole"), {"frame": frame})
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.astype(np.float32))
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4000)
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), {"frame": frame})
+    sample, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and sample.nbytes + idx.nbytes <= 4000
+    assert len(np.unique(idx)) == len(idx) > 50
+    assert np.array_equal(sample, frame.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_sample_index.npy"))  # the same pixels every run
+    assert not (tmp_path / "a" / "frame.npy").exists()
+
+
+def test_bench_options():
+    """a plain run times exactly --steps jobs; what else the benchmark measures sits behind --full"""
+    b = _bench()
+    assert b.CALIBRATION_STEPS > 0 and b.DUMP_LIMIT_BYTES == 64 << 20
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout

@@ -1,12 +1,12 @@
 """-m "not gpu": this project's host-side mirrors against the REFERENCE's own code.
 
 oracle/ref/Makefile compiles the reference's app/hdre_loader.cpp (with the stb_image.h it vendors), app/nrrd_loader.cpp
-and common.hpp's Position3D from /root/reference where they lie into oracle/_ref/libref_hostio.so; the tests below
-feed both sides the same files / angles and require identical bytes.  Skipped when neither the library nor the
-reference tree is there (the reference does not travel; the prebuilt library does)."""
+and common.hpp's Position3D into oracle/_ref/libref_hostio.so.  tests/golden/make_ref_hostio_golden.py fed that library
+the files / angles made by the generators below and stored both the input files and what the reference returned for
+them in tests/golden/ref_hostio.npz; the tests below feed this project's loaders the same stored files and require
+identical bytes.  The reference tree is not needed to run them."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,22 +14,16 @@ import pytest
 from cl_volume_renderer_amd import scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libref_hostio.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_hostio.npz")
+
+HDR_CASES = [(True, 64, 17), (False, 64, 17), (True, 5, 3), (True, 300, 9), (True, 1024, 4)]
 
 
 @pytest.fixture(scope="module")
 def ref():
-    if not os.path.exists(REF_LIB):
-        if not os.path.isdir("/root/reference/app"):
-            pytest.skip("oracle/_ref/libref_hostio.so not built and no reference tree to build it from")
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-s"])
-    L = C.CDLL(REF_LIB)
-    L.ref_env_load.restype = C.c_longlong
-    L.ref_env_load.argtypes = [C.c_char_p, C.POINTER(C.c_uint), C.c_void_p, C.c_longlong]
-    L.ref_nrrd_load.restype = C.c_longlong
-    L.ref_nrrd_load.argtypes = [C.c_char_p, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.c_void_p, C.c_longlong]
-    L.ref_camera_direction.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_float)]
-    return L
+    """{key: array}: the input files (`<case>.in`, raw bytes) and the reference's answers for them"""
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
 
 
 @pytest.fixture(scope="module")
@@ -44,133 +38,71 @@ def mine():
     return L
 
 
-def _both_env(ref, mine, path, w, h):
-    out_r = np.zeros((h, w, 4), np.uint8)
-    out_m = np.zeros((h, w, 4), np.uint8)
-    dr, dm = (C.c_uint * 2)(), (C.c_uint * 2)()
-    assert ref.ref_env_load(path.encode(), dr, out_r.ctypes.data, out_r.nbytes) == out_r.nbytes
-    assert mine.clvr_host_hdr_probe(path.encode(), dm, out_m.ctypes.data, out_m.nbytes) == out_m.nbytes
-    assert (dr[0], dr[1]) == (dm[0], dm[1]) == (w, h)
-    return out_r, out_m
+# ---- the inputs (tests/golden/make_ref_hostio_golden.py writes them with these functions)
 
 
-@pytest.mark.parametrize("rle,w,h", [(True, 64, 17), (False, 64, 17), (True, 5, 3), (True, 300, 9), (True, 1024, 4)])
-def test_hdr_environment_maps_decode_like_the_reference(ref, mine, tmp_path, rle, w, h):
-    """Radiance .hdr -> gamma-2.2 RGBA8 (app/hdre_loader.cpp:7-24 through stb_image): pins app/hdre_loader.cpp here"""
+def hdr_input(path, rle, w, h):
     rng = np.random.default_rng(w * 7 + h)
     rgb = (rng.random((h, w, 3), dtype=np.float32) ** 3 * 6.0).astype(np.float32)
     rgb[:, : w // 3] = rgb[:, :1]
     rgb[0, 0] = 0.0
     rgb[-1, -1] = [1e-6, 300.0, 1.0]  # tiny and over-range values
-    path = str(tmp_path / "env.hdr")
     scene.write_hdr(path, scene.float_to_rgbe(rgb), rle=rle)
-    out_r, out_m = _both_env(ref, mine, path, w, h)
-    assert np.array_equal(out_m, out_r)
-    assert out_r[..., :3].std() > 10
+    return w, h
 
 
-def test_png_environment_maps_decode_like_the_reference(ref, mine, tmp_path):
-    """every PNG flavour of tests/test_host_mirror.py through the reference's stb_image: pins app/png_reader.cpp"""
-    from tests.test_host_mirror import PNG_CASES, _png_bytes
+def png_cases():
+    from tests.test_host_mirror import PNG_CASES
 
-    for color, depth, interlace in PNG_CASES:
-        rng = np.random.default_rng(color * 100 + depth + interlace)
-        w, h = 37, 19
-        ch = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[color]
-        palette = trns = None
-        if color == 3:
-            n_pal = 1 << depth
-            palette = rng.integers(0, 256, (n_pal, 3)).astype(np.uint8)
-            trns = rng.integers(0, 256, n_pal // 2).astype(np.uint8).tolist()
-            img = rng.integers(0, n_pal, (h, w, 1))
-        else:
-            img = rng.integers(0, 1 << depth, (h, w, ch))
-        if color == 0:
-            trns = [0, int(img[3, 7, 0])] if depth <= 8 else [int(img[3, 7, 0]) >> 8, int(img[3, 7, 0]) & 255]
-        if color == 2:
-            k = img[2, 9].tolist()
-            trns = [k[0] >> 8, k[0] & 255, k[1] >> 8, k[1] & 255, k[2] >> 8, k[2] & 255]
-        path = str(tmp_path / ("c%d_d%d_i%d.png" % (color, depth, interlace)))
-        open(path, "wb").write(_png_bytes(img, color, depth, interlace, palette, trns))
-        out_r, out_m = _both_env(ref, mine, path, w, h)
-        assert np.array_equal(out_m, out_r), (color, depth, interlace)
+    return PNG_CASES
 
 
-def _both_nrrd(ref, mine, path, n):
-    res = []
-    for fn in (ref.ref_nrrd_load, mine.clvr_host_nrrd_load):
-        counts, sizes = (C.c_uint * 3)(), (C.c_float * 3)()
-        out = np.zeros(n, np.int16)
-        got = fn(path.encode(), counts, sizes, out.ctypes.data, n)
-        assert got == n
-        res.append((tuple(counts), tuple(sizes), out))
-    return res
+def png_input(path, color, depth, interlace):
+    """every PNG flavour of tests/test_host_mirror.py"""
+    from tests.test_host_mirror import _png_bytes
+
+    rng = np.random.default_rng(color * 100 + depth + interlace)
+    w, h = 37, 19
+    ch = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[color]
+    palette = trns = None
+    if color == 3:
+        n_pal = 1 << depth
+        palette = rng.integers(0, 256, (n_pal, 3)).astype(np.uint8)
+        trns = rng.integers(0, 256, n_pal // 2).astype(np.uint8).tolist()
+        img = rng.integers(0, n_pal, (h, w, 1))
+    else:
+        img = rng.integers(0, 1 << depth, (h, w, ch))
+    if color == 0:
+        trns = [0, int(img[3, 7, 0])] if depth <= 8 else [int(img[3, 7, 0]) >> 8, int(img[3, 7, 0]) & 255]
+    if color == 2:
+        k = img[2, 9].tolist()
+        trns = [k[0] >> 8, k[0] & 255, k[1] >> 8, k[1] & 255, k[2] >> 8, k[2] & 255]
+    open(path, "wb").write(_png_bytes(img, color, depth, interlace, palette, trns))
+    return w, h
 
 
-@pytest.mark.parametrize("gz", [True, False])
-def test_nrrd_volumes_load_like_the_reference(ref, mine, tmp_path, gz):
-    """app/nrrd_loader.cpp: counts, relative voxel sizes and every voxel"""
+def nrrd_volume():
     rng = np.random.default_rng(11)
-    vol = rng.integers(-2000, 4000, (9, 14, 23)).astype(np.int16)
-    path = str(tmp_path / "v.nrrd")
+    return rng.integers(-2000, 4000, (9, 14, 23)).astype(np.int16)
+
+
+def nrrd_input(path, gz):
+    vol = nrrd_volume()
     scene.write_nrrd(path, vol, use_gzip=gz)
-    (cr, sr, vr), (cm, sm, vm) = _both_nrrd(ref, mine, path, vol.size)
-    assert cr == cm == (23, 14, 9)
-    assert sr == sm
-    assert np.array_equal(vr, vm) and np.array_equal(vm, vol.reshape(-1))
+    return vol
 
 
-def test_nrrd_anisotropic_header_and_the_reference_test_block(ref, mine, tmp_path):
-    golden = os.path.join(ROOT, "tests", "golden", "sdf_testdata.nrrd")
-    dims = scene.read_nrrd(golden).shape  # the reference's own test volume (tests/sdf/testdata.nrrd)
-    n = int(np.prod(dims))
-    (cr, sr, vr), (cm, sm, vm) = _both_nrrd(ref, mine, golden, n)
-    assert cr == cm == (dims[2], dims[1], dims[0]) and sr == sm and np.array_equal(vr, vm)
-    # anisotropic spacing: voxel sizes are kept relative to x
+def anisotropic_nrrd_input(path):
     vol = np.arange(4 * 3 * 5, dtype=np.int16).reshape(4, 3, 5)
-    path = str(tmp_path / "a.nrrd")
     hdr = ("NRRD0004\n# comment\ntype: short\ndimension: 3\nsizes: 5 3 4\n"
            "space directions: (0.5,0,0) (0,0.75,0) (0,0,2.5)\nendian: little\nencoding: raw\n\n")
     open(path, "wb").write(hdr.encode() + vol.astype("<i2").tobytes())
-    (cr, sr, vr), (cm, sm, vm) = _both_nrrd(ref, mine, path, vol.size)
-    assert cr == cm == (5, 3, 4)
-    assert sr == sm and sr[0] == 1.0 and sr[1] == pytest.approx(1.5) and sr[2] == pytest.approx(5.0)
-    assert np.array_equal(vr, vm)
+    return vol
 
 
-def test_camera_direction_matches_position3d(ref, mine, orc):
-    """Position3D(alpha, beta, 0, {1,0,0}) (app/common.hpp, renderer.cpp:140): the python helper, the oracle's
-    orc_camera_direction and the C++ host mirror all give the reference's bits"""
+def camera_angles():
     rng = np.random.default_rng(2)
-    angles = [(0.9, 6.183), (0.0, 0.0), (0.3, 6.1), (-1.2, 3.0)] + [tuple(rng.uniform(-7, 7, 2)) for _ in range(200)]
-    mine.clvr_host_camera_direction.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
-    for a, b in angles:
-        a32, b32 = np.float32(a), np.float32(b)  # ui_state keeps the look angles as floats
-        want = (C.c_float * 3)()
-        ref.ref_camera_direction(float(a32), float(b32), want)
-        want = np.array(want[:], np.float32)
-        assert np.array_equal(scene.camera_direction(a32, b32), want), (a, b)
-        got = (C.c_float * 3)()
-        mine.clvr_host_camera_direction(a32, b32, got)
-        assert np.array_equal(np.array(got[:], np.float32), want)
-        o = (C.c_float * 3)()
-        orc.lib().orc_camera_direction(float(a32), float(b32), o)
-        assert np.array_equal(np.array(o[:], np.float32), want)
-
-
-def _ref_decode_in_child(path, w, h):
-    """the reference's loader exits the process on a file it rejects, so JPEG files go through it in a child"""
-    code = ("import ctypes as C, numpy as np, sys\n"
-            "L = C.CDLL(%r)\n"
-            "L.ref_env_load.restype = C.c_longlong\n"
-            "L.ref_env_load.argtypes = [C.c_char_p, C.POINTER(C.c_uint), C.c_void_p, C.c_longlong]\n"
-            "out = np.zeros((%d, %d, 4), np.uint8); d = (C.c_uint * 2)()\n"
-            "n = L.ref_env_load(%r.encode(), d, out.ctypes.data, out.nbytes)\n"
-            "assert n == out.nbytes and (d[0], d[1]) == (%d, %d), (n, d[0], d[1])\n"
-            "np.save(%r, out)\n") % (REF_LIB, h, w, path, w, h, path + ".ref.npy")
-    r = subprocess.run([os.sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "the reference's decoder rejected the test stream: " + r.stderr[-400:]
-    return np.load(path + ".ref.npy")
+    return [(0.9, 6.183), (0.0, 0.0), (0.3, 6.1), (-1.2, 3.0)] + [tuple(rng.uniform(-7, 7, 2)) for _ in range(200)]
 
 
 def _jpeg_scene(w, h, n, seed):
@@ -209,11 +141,7 @@ JPEG_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", JPEG_CASES, ids=[c[0] for c in JPEG_CASES])
-def test_jpeg_environment_maps_decode_like_the_reference(ref, mine, tmp_path, case):
-    """JPEG env maps (reference README.md:29) through app/jpeg_reader.cpp vs the reference's stb_image: baseline and
-    progressive streams, every upsampling path, restart intervals, 16-bit quantisation tables, JFIF / Adobe colour
-    handling (RGB, YCbCr, CMYK, YCCK) -- identical RGBA8 bytes."""
+def jpeg_input(path, case):
     from tests.jpeg_writer import Encoder, quant_table
 
     name, (w, h), samp, progressive, restart, style, interleaved, extra = case
@@ -231,12 +159,131 @@ def test_jpeg_environment_maps_decode_like_the_reference(ref, mine, tmp_path, ca
                   progressive=progressive, restart=restart, style=style, markers=markers, ids=extra.get("ids"),
                   script=extra.get("script"))
     data = enc.encode_progressive() if progressive else enc.encode_baseline(interleaved)
-    path = str(tmp_path / (name + ".jpg"))
     open(path, "wb").write(data)
-    want = _ref_decode_in_child(path, w, h)
+    return w, h
+
+
+# ---- golden keys
+
+
+def hdr_key(rle, w, h):
+    return "hdr_rle%d_%dx%d" % (rle, w, h)
+
+
+def png_key(color, depth, interlace):
+    return "png_c%d_d%d_i%d" % (color, depth, interlace)
+
+
+def nrrd_key(gz):
+    return "nrrd_gz%d" % gz
+
+
+# ---- the tests
+
+
+def _stored(ref, tmp_path, key, suffix):
+    """the stored input file of case `key`, written back to disk for the loaders"""
+    path = str(tmp_path / (key + suffix))
+    open(path, "wb").write(ref[key + ".in"].tobytes())
+    return path
+
+
+def _mine_env(mine, path, w, h):
     out = np.zeros((h, w, 4), np.uint8)
     d = (C.c_uint * 2)()
     assert mine.clvr_host_hdr_probe(path.encode(), d, out.ctypes.data, out.nbytes) == out.nbytes
     assert (d[0], d[1]) == (w, h)
+    return out
+
+
+@pytest.mark.parametrize("rle,w,h", HDR_CASES)
+def test_hdr_environment_maps_decode_like_the_reference(ref, mine, tmp_path, rle, w, h):
+    """Radiance .hdr -> gamma-2.2 RGBA8 (app/hdre_loader.cpp:7-24 through stb_image): pins app/hdre_loader.cpp here"""
+    key = hdr_key(rle, w, h)
+    out_r = ref[key]
+    assert out_r.shape == (h, w, 4)
+    out_m = _mine_env(mine, _stored(ref, tmp_path, key, ".hdr"), w, h)
+    assert np.array_equal(out_m, out_r)
+    assert out_r[..., :3].std() > 10
+
+
+def test_png_environment_maps_decode_like_the_reference(ref, mine, tmp_path):
+    """every PNG flavour of tests/test_host_mirror.py through the reference's stb_image: pins app/png_reader.cpp"""
+    for color, depth, interlace in png_cases():
+        key = png_key(color, depth, interlace)
+        out_r = ref[key]
+        h, w = out_r.shape[:2]
+        assert (w, h) == (37, 19)
+        out_m = _mine_env(mine, _stored(ref, tmp_path, key, ".png"), w, h)
+        assert np.array_equal(out_m, out_r), (color, depth, interlace)
+
+
+def _mine_nrrd(mine, path, n):
+    counts, sizes = (C.c_uint * 3)(), (C.c_float * 3)()
+    out = np.zeros(n, np.int16)
+    assert mine.clvr_host_nrrd_load(path.encode(), counts, sizes, out.ctypes.data, n) == n
+    return tuple(counts), tuple(sizes), out
+
+
+def _ref_nrrd(ref, key):
+    return tuple(int(v) for v in ref[key + ".counts"]), tuple(float(v) for v in ref[key + ".sizes"]), ref[key + ".voxels"]
+
+
+@pytest.mark.parametrize("gz", [True, False])
+def test_nrrd_volumes_load_like_the_reference(ref, mine, tmp_path, gz):
+    """app/nrrd_loader.cpp: counts, relative voxel sizes and every voxel"""
+    vol = nrrd_volume()
+    key = nrrd_key(gz)
+    cr, sr, vr = _ref_nrrd(ref, key)
+    cm, sm, vm = _mine_nrrd(mine, _stored(ref, tmp_path, key, ".nrrd"), vol.size)
+    assert cr == cm == (23, 14, 9)
+    assert sr == sm
+    assert np.array_equal(vr, vm) and np.array_equal(vm, vol.reshape(-1))
+
+
+def test_nrrd_anisotropic_header_and_the_reference_test_block(ref, mine, tmp_path):
+    golden = os.path.join(ROOT, "tests", "golden", "sdf_testdata.nrrd")
+    dims = scene.read_nrrd(golden).shape  # the reference's own test volume (tests/sdf/testdata.nrrd)
+    n = int(np.prod(dims))
+    cr, sr, vr = _ref_nrrd(ref, "nrrd_testdata")
+    cm, sm, vm = _mine_nrrd(mine, golden, n)
+    assert cr == cm == (dims[2], dims[1], dims[0]) and sr == sm and np.array_equal(vr, vm)
+    # anisotropic spacing: voxel sizes are kept relative to x
+    vol = anisotropic_nrrd_input(str(tmp_path / "a.nrrd"))
+    cr, sr, vr = _ref_nrrd(ref, "nrrd_anisotropic")
+    cm, sm, vm = _mine_nrrd(mine, _stored(ref, tmp_path, "nrrd_anisotropic", ".nrrd"), vol.size)
+    assert cr == cm == (5, 3, 4)
+    assert sr == sm and sr[0] == 1.0 and sr[1] == pytest.approx(1.5) and sr[2] == pytest.approx(5.0)
+    assert np.array_equal(vr, vm)
+
+
+def test_camera_direction_matches_position3d(ref, mine, orc):
+    """Position3D(alpha, beta, 0, {1,0,0}) (app/common.hpp, renderer.cpp:140): the python helper, the oracle's
+    orc_camera_direction and the C++ host mirror all give the reference's bits"""
+    angles = camera_angles()
+    wants = ref["camera_direction"]
+    assert wants.shape == (len(angles), 3) and wants.dtype == np.float32
+    mine.clvr_host_camera_direction.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
+    for (a, b), want in zip(angles, wants):
+        a32, b32 = np.float32(a), np.float32(b)  # ui_state keeps the look angles as floats
+        assert np.array_equal(scene.camera_direction(a32, b32), want), (a, b)
+        got = (C.c_float * 3)()
+        mine.clvr_host_camera_direction(a32, b32, got)
+        assert np.array_equal(np.array(got[:], np.float32), want)
+        o = (C.c_float * 3)()
+        orc.lib().orc_camera_direction(float(a32), float(b32), o)
+        assert np.array_equal(np.array(o[:], np.float32), want)
+
+
+@pytest.mark.parametrize("case", JPEG_CASES, ids=[c[0] for c in JPEG_CASES])
+def test_jpeg_environment_maps_decode_like_the_reference(ref, mine, tmp_path, case):
+    """JPEG env maps (reference README.md:29) through app/jpeg_reader.cpp vs the reference's stb_image: baseline and
+    progressive streams, every upsampling path, restart intervals, 16-bit quantisation tables, JFIF / Adobe colour
+    handling (RGB, YCbCr, CMYK, YCCK) -- identical RGBA8 bytes."""
+    name, (w, h) = case[0], case[1]
+    key = "jpeg_" + name
+    want = ref[key]
+    assert want.shape == (h, w, 4)
+    out = _mine_env(mine, _stored(ref, tmp_path, key, ".jpg"), w, h)
     assert np.array_equal(out, want), "first difference at %s" % (np.argwhere(out != want)[:3].tolist(),)
     assert want[..., :3].std() > 5 and (want[..., 3] == 255).all()

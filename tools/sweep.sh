@@ -8,7 +8,7 @@ i=0
 for FLAGS in "$@" ""; do
   i=$((i+1))
   CLVR_EXTRA_HIPCC_FLAGS="$FLAGS" python3 -m cl_volume_renderer_amd.build --force > "$OUT/build$i.log" 2>&1 || { tail -5 "$OUT/build$i.log"; exit 1; }
-  python3 bench.py --no-cpu-baseline --no-secondary $BENCH_ARGS > "$OUT/bench$i.json" 2> "$OUT/bench$i.err" || { tail -5 "$OUT/bench$i.err"; exit 1; }
+  python3 bench.py --full --no-cpu-baseline --no-secondary $BENCH_ARGS > "$OUT/bench$i.json" 2> "$OUT/bench$i.err" || { tail -5 "$OUT/bench$i.err"; exit 1; }
   python3 - "$OUT/bench$i.json" "$FLAGS" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

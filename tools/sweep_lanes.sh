@@ -5,7 +5,7 @@ out=${1:-gpurun_out/lanes}
 mkdir -p "$out"
 for cfg in 2 5 4; do
   for f in 1 2 3; do
-    python bench.py --config $cfg --frames-in-flight $f --no-secondary --no-cpu-baseline > "$out/config${cfg}_lanes${f}.json" 2> "$out/config${cfg}_lanes${f}.err" || exit 1
+    python bench.py --full --config $cfg --frames-in-flight $f --no-secondary --no-cpu-baseline > "$out/config${cfg}_lanes${f}.json" 2> "$out/config${cfg}_lanes${f}.err" || exit 1
     python - "$out/config${cfg}_lanes${f}.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

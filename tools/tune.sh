@@ -1,6 +1,6 @@
 #!/bin/bash
 # sweeps k_bounce's scheduling knobs on the headline workload (one frame at a time); run on the GPU box:  bash tools/tune.sh
-run() { python bench.py --no-cpu-baseline --no-secondary --frames-in-flight 1 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-24s %9.1f Msamples/s  k_bounce %.4f ms' % ('$1', d['value'], d['roofline']['avg_launch_ms']))"; }
+run() { python bench.py --full --no-cpu-baseline --no-secondary --frames-in-flight 1 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-24s %9.1f Msamples/s  k_bounce %.4f ms' % ('$1', d['value'], d['roofline']['avg_launch_ms']))"; }
 run "default"
 for R in 8 16 24 32; do
   for T in 8 16 24 32; do
