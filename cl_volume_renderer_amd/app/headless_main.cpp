@@ -1,13 +1,18 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
-// Prints one JSON line with the frame time and a checksum of the last frame.
+// Usage: clvr_headless [--projection=max|min|mean] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
+// the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <string>
+#include <vector>
+
+#include <clwh.h>
 
 #include "common_defines.hpp"
 #include "hdre_loader.hpp"
@@ -15,9 +20,26 @@
 #include "renderer.hpp"
 #include "tf_part.hpp"
 
-int main(int argc, char const *argv[]) {
+int main(int argc_in, char const *argv_in[]) {
+  int projection = -1;  // clwh_projection, or -1: path-traced frames
+  std::vector<const char *> args{argv_in[0]};
+  for (int i = 1; i < argc_in; ++i) {
+    const std::string a = argv_in[i];
+    if (a.rfind("--projection=", 0) == 0) {
+      const std::string m = a.substr(13);
+      projection = m == "max" ? CLWH_PROJ_MAX : m == "min" ? CLWH_PROJ_MIN : m == "mean" ? CLWH_PROJ_MEAN : -2;
+      if (projection == -2) {
+        std::cout << "Unknown projection '" << m << "' (max, min or mean)\n";
+        return 1;
+      }
+    } else {
+      args.push_back(argv_in[i]);
+    }
+  }
+  const int argc = (int)args.size();
+  char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -54,7 +76,10 @@ int main(int argc, char const *argv[]) {
   for (int f = 0; f < frames; ++f) {
     bool changed = false;
     state.cam_changed = true;  // progressive refinement: keep sampling the same view
-    frame = static_cast<const unsigned char *>(emitter->render_frame(state, changed));
+    if (projection >= 0)
+      frame = static_cast<const unsigned char *>(r.render_projection(state, projection, 0.0f, 4000.0f));
+    else
+      frame = static_cast<const unsigned char *>(emitter->render_frame(state, changed));
   }
   const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
@@ -70,8 +95,10 @@ int main(int argc, char const *argv[]) {
     for (int y = height - 1; y >= 0; --y)  // row 0 is the bottom of the screen
       for (int x = 0; x < width; ++x) ppm.write(reinterpret_cast<const char *>(frame + ((size_t)y * SCREEN_WIDTH + x) * 4), 3);
   }
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"}\n",
-              frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum);
+  static const char *const kProjectionNames[] = {"max", "min", "mean"};
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s}\n",
+              frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
+              projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "");
   for (tf_selection *s : selection) delete s;
   return 0;
 }

@@ -79,6 +79,17 @@ void clvr_host_render_frame_device(clvr_host *h, const float pos[3], const float
   h->rend.render_frame_device(h->state, target, passes);
 }
 
+// renderer::render_projection from the same camera arguments as clvr_host_render_frame: the RGBA8 frame (SCREEN_WIDTH x SCREEN_HEIGHT)
+const void *clvr_host_render_projection(clvr_host *h, const float pos[3], const float look[2], int width, int height, int mode,
+                                        float center, float window_width, float step) {
+  h->state.position = Position3D(pos[0], pos[1], pos[2]);
+  h->state.direction_look[0] = look[0];
+  h->state.direction_look[1] = look[1];
+  h->state.width = width;
+  h->state.height = height;
+  return h->rend.render_projection(h->state, mode, center, window_width, step);
+}
+
 size_t clvr_host_cache_len(clvr_host *h) { return h->rend.voxel_cache().size(); }
 void clvr_host_pull_cache(clvr_host *h, unsigned short *out) {
   auto &c = h->rend.voxel_cache();

@@ -29,6 +29,12 @@ class renderer : public frame_emitter {
   // token cap).
   void render_frame_device(struct ui_state &state, const clw_foreign_memory &target, int passes = 1);
 
+  // not in the reference: a maximum / minimum / mean intensity projection of the volume (mode = CLWH_PROJ_MAX / MIN / MEAN) without a
+  // transfer function, from render_frame's camera into the same frame image, so that it lines up with the path-traced frame pixel for
+  // pixel (a preview while the path tracer converges).  `center` / `width` window the value to grey; `step` is the sample spacing in
+  // voxels.  Pulls the frame and returns its host copy.
+  void *render_projection(struct ui_state &state, int mode, float center, float width, float step = 0.5f);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }

@@ -239,6 +239,31 @@ hipError_t launch_bilateral_filter(const int16_t *src, int X, int Y, int Z, int1
 hipError_t launch_apply_clip(const int16_t *src, int SX, int SY, int SZ, int16_t *dst, int DX, int DY, int DZ,
                              const uint32_t *start, const uint32_t *len, hipStream_t s);
 
+// ---- intensity projections (projection_kernels.hip): the caller's S16 image in brick order (packed_volume.hpp inner_index,
+// one 4^3 sub-brick = one 128-byte line) plus a {min, max} int16 pair per 8^3 brick, built by k_proj_repack
+struct ProjRepackArgs {
+  const int16_t *volume;  // the caller's image, x fastest
+  int32_t X, Y, Z, NBX, NBY, NBZ;
+  int16_t *bricks;        // NBX * NBY * NBZ * 512 voxels
+  uint32_t *table;        // per brick: (uint16)min | (uint16)max << 16, over the brick's real voxels
+};
+struct ProjArgs {
+  const int16_t *bricks;
+  const uint32_t *table;
+  int32_t X, Y, Z, NBX, NBY;
+  uint32_t *frame;        // RGBA8 packed, row-major, frame_w x frame_h
+  int32_t frame_w, frame_h;
+  int32_t launch_w, launch_h, tiles_x, num_tiles;
+  float cam_pos[3], cam_dir[3];
+  float step, t_near, t_far;
+  float window_center, window_width;
+  int32_t k_cap;          // every kept sample has k < k_cap (clwh_render_projection checks the camera distance / step)
+  float *values;          // optional, row-major launch_w x launch_h
+  float *t_extreme;       // optional, same
+};
+hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s);
+hipError_t launch_projection(const ProjArgs &a, int mode, bool dense, hipStream_t s);
+
 // ---- derived scene data (step bytes + hit records + per-brick minima + exit-certificate table), ONE copy per device however many
 // contexts (frame lanes, callers) render the same (volume content, SDF content, transfer function): contexts hold it by
 // shared_ptr and find it in a process-wide registry (clwh_runtime.hip); the memory goes when the last context lets go of it.
@@ -346,6 +371,14 @@ struct clwh_ctx {
   // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per
   // brick), the macro-cell table -- shared with every other context of the device that renders the same scene
   std::shared_ptr<clvr::PackedScene> scene;
+  // intensity projections: the volume in brick order + the per-brick {min, max} table (one allocation, per context), and the key
+  // of the content it was built from (device pointer, shared content version, dims)
+  uint8_t *proj_data = nullptr;
+  size_t proj_bytes = 0;
+  bool proj_valid = false;
+  const void *proj_vol = nullptr;
+  uint64_t proj_vol_ver = 0;
+  size_t proj_dims[3] = {0, 0, 0};
 
   // timing: one HIP event pair per clwh_render, recorded on the context's stream around the
   // dominant kernel and read back (without a sync per pass) by clwh_ctx_timing_read

@@ -306,6 +306,14 @@ __device__ __forceinline__ uint32_t tone_map_rgba8(uint32_t sr, uint32_t sg, uin
 // ------------------------------------------------------------------------------------------------
 // image-tile ownership: 8x8 pixel tiles, owner = (tx + ty) % world; a rank's tiles are numbered
 // slot = ty * tiles_per_row + tx / world  (tile-major accumulation / scratch layout)
+// blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of tile slots so
+// that neighbouring tiles (which walk neighbouring voxels) share one L2
+__device__ __forceinline__ uint32_t xcd_contiguous_slot(uint32_t b, uint32_t nblocks) {
+  const uint32_t per = nblocks >> 3;
+  if (per == 0u || b >= (per << 3)) return b;
+  return (b & 7u) * per + (b >> 3);
+}
+
 __device__ __forceinline__ bool tile_from_slot(const RenderArgs &a, uint32_t slot, int &tx, int &ty) {
   ty = (int)(slot / (uint32_t)a.tiles_per_row);
   const int k = (int)(slot % (uint32_t)a.tiles_per_row);

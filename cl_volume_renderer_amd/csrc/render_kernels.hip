@@ -33,14 +33,6 @@
 
 namespace clvr {
 
-// blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of tile slots so
-// that neighbouring tiles (which walk neighbouring voxels) share one L2
-__device__ __forceinline__ uint32_t xcd_contiguous_slot(uint32_t b, uint32_t nblocks) {
-  const uint32_t per = nblocks >> 3;
-  if (per == 0u || b >= (per << 3)) return b;
-  return (b & 7u) * per + (b >> 3);
-}
-
 __device__ __forceinline__ VolumePacked make_volume(const RenderArgs &a) {
   return VolumePacked{a.grec, a.stepb, a.volume_lin, a.sdf_lin, a.X, a.Y, a.Z, a.NBX, a.NBY};
 }

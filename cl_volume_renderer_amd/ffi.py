@@ -17,7 +17,9 @@ OK = 0
 ELEM_S8, ELEM_S16, ELEM_S32, ELEM_U8, ELEM_U16, ELEM_U32, ELEM_F32 = range(7)
 ARG_MEM, ARG_I32, ARG_U32, ARG_F32, ARG_I64, ARG_U64, ARG_F64 = range(7)
 ACCUM_VOXEL_CACHE, ACCUM_IMAGE_SPACE = 0, 1
-DERIVED_SCENE, DERIVED_CAMERA = 1, 2
+DERIVED_SCENE, DERIVED_CAMERA, DERIVED_PROJECTION = 1, 2, 4
+PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2
+PROJ_DENSE = 1
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -75,6 +77,18 @@ class RenderDesc(C.Structure):
     ]
 
 
+class ProjectionDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("volume", C.c_void_p),
+        ("cam_pos", C.c_float * 3), ("cam_dir", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("mode", C.c_int32), ("flags", C.c_int32),
+        ("step", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float),
+        ("window_center", C.c_float), ("window_width", C.c_float),
+        ("values", C.c_void_p), ("t_extreme", C.c_void_p),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -109,6 +123,7 @@ _PROTOTYPES = [
     ("clwh_frame_from_tiles", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("clwh_ctx_invalidate_derived", C.c_int, [C.c_void_p, C.c_int]),
     ("clwh_ctx_scene_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    ("clwh_render_projection", C.c_int, [C.c_void_p, C.POINTER(ProjectionDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -343,9 +358,27 @@ class Context:
     def frame_from_tiles(self, tiles_all: Mem, tile_world, width, height, frame: Mem):
         _check(lib().clwh_frame_from_tiles(self.h, tiles_all.h, tile_world, width, height, frame.h), "clwh_frame_from_tiles")
 
-    def invalidate_derived(self, scene=True, camera=True):
-        what = (DERIVED_SCENE if scene else 0) | (DERIVED_CAMERA if camera else 0)
+    def invalidate_derived(self, scene=True, camera=True, projection=False):
+        what = (DERIVED_SCENE if scene else 0) | (DERIVED_CAMERA if camera else 0) | (DERIVED_PROJECTION if projection else 0)
         _check(lib().clwh_ctx_invalidate_derived(self.h, what), "clwh_ctx_invalidate_derived")
+
+    def render_projection(self, frame: Mem, volume: Mem, cam_pos, cam_dir, width, height, mode=PROJ_MAX, step=0.5,
+                          window=(0.0, 1.0), t_near=0.0, t_far=float("inf"), values: Mem = None, t_extreme: Mem = None,
+                          dense=False):
+        """maximum / minimum / mean intensity projection of `volume` (S16) into `frame` (RGBA8) with clwh_render's camera rays;
+        window = (center, width) maps the projected value to grey.  values / t_extreme: optional float32[height][width] buffers."""
+        d = ProjectionDesc()
+        d.frame, d.volume = frame.h, volume.h
+        for k in range(3):
+            d.cam_pos[k] = float(cam_pos[k])
+            d.cam_dir[k] = float(cam_dir[k])
+        d.width, d.height = int(width), int(height)
+        d.mode, d.flags = int(mode), PROJ_DENSE if dense else 0
+        d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
+        d.window_center, d.window_width = float(window[0]), float(window[1])
+        d.values = values.h if values is not None else None
+        d.t_extreme = t_extreme.h if t_extreme is not None else None
+        _check(lib().clwh_render_projection(self.h, C.byref(d)), "clwh_render_projection")
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -209,12 +209,48 @@ int clwh_frame_from_tiles(clwh_ctx *ctx, clwh_mem *tiles_all_ranks, int32_t tile
  *                        (volume content, SDF content, transfer function) share it -- 9 bytes per voxel, 72 GiB at
  *                        2048^3 -- and it is freed when the last of them lets go.  Invalidating makes THIS context
  *                        rebuild; contexts already sharing the old copy keep it until their own inputs change.
- *   CLWH_DERIVED_CAMERA  primary hits (function of the camera and of the scene), per context */
-enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2 };
+ *   CLWH_DERIVED_CAMERA  primary hits (function of the camera and of the scene), per context
+ *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table of clwh_render_projection, per
+ *                        context (2 bytes per voxel + 4 per 8^3 brick) */
+enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2, CLWH_DERIVED_PROJECTION = 4 };
 int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what);
 /* which copy of the derived scene data the context renders from (after its last clwh_render): a process-wide unique id
  * of the content (0: none yet), its size in bytes, and how many contexts hold it right now */
 int clwh_ctx_scene_info(clwh_ctx *ctx, uint64_t *scene_id, uint64_t *bytes, int32_t *holders);
+
+/* ---- intensity projections: a view of the caller's S16 image without a transfer function (not in the reference).
+ * For pixel (x, y) of the launched region the ray is the camera ray of clwh_render (generate_ray with the frame IMAGE's dims as totals):
+ * origin o = cam_pos, normalised direction d.  Sample k >= 0 sits at t_k = (float)k * step, p_k = o + d * t_k (per component one float
+ * multiply, then one float add), and is KEPT iff t_near <= t_k <= t_far and 0 <= p_k.c < dim_c on all three axes (NaN never; -0.0
+ * counts as 0).  Its value is the voxel V[floor(p.z)][floor(p.y)][floor(p.x)] (x fastest).
+ *   CLWH_PROJ_MAX   value = the largest kept value; t_extreme = t_k of the smallest k that attains it
+ *   CLWH_PROJ_MIN   the same with the smallest kept value
+ *   CLWH_PROJ_MEAN  value = (float)((double)sum / (double)count) with an int64 sum; t_extreme = NaN
+ * A pixel without a kept sample has value = t_extreme = NaN and frame pixel (0, 0, 0, 0).  Otherwise, in float32 and in this order,
+ * u = ((value - window_center) / window_width + 0.5f) * 255.0f + 0.5f, grey = (int)fminf(fmaxf(u, 0), 255), and the frame pixel is
+ * (grey, grey, grey, 255).  CLWH_PROJ_DENSE reads every kept sample; without it MAX / MIN step over 8^3 bricks whose {min, max} cannot
+ * change the result: same bytes, by the contract.
+ * Errors: a NULL or wrong-kind handle, a bad mode or flags, a step that is not finite and > 0 (or so small that the camera's farthest
+ * volume corner lies 2^29 steps away or more), a window that is not finite with window_width > 0, or a slab that is not
+ * t_near <= t_far with t_near < +inf: CLWH_ERR_INVALID_VALUE.  A region that is empty, not a multiple of 8, larger than the frame or
+ * than 65535: CLWH_ERR_BAD_NDRANGE.  An optional output smaller than 4 * width * height bytes: CLWH_ERR_SIZE_MISMATCH.
+ * Asynchronous and ordered on the context's stream like clwh_render.  The first projection of a volume content builds the derived
+ * data (CLWH_DERIVED_PROJECTION); a push, clwh_mem_mark_dirty or a rewrite through any clwh_mem of the same pointer rebuilds it. */
+enum clwh_projection { CLWH_PROJ_MAX = 0, CLWH_PROJ_MIN = 1, CLWH_PROJ_MEAN = 2 };
+enum clwh_projection_flags { CLWH_PROJ_DENSE = 1 };  /* no brick skipping: same result by contract; for tests and timing */
+typedef struct clwh_projection_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image; its dims are generate_ray's totals (as clwh_render_desc.frame) */
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  float cam_pos[3], cam_dir[3];
+  uint32_t width, height;     /* launched region: multiples of 8, <= frame dims, <= 65535 (same rule as clwh_render) */
+  int32_t mode, flags;
+  float step;                 /* h > 0, finite */
+  float t_near, t_far;        /* slab along the ray; 0 and +INFINITY = whole volume */
+  float window_center, window_width;  /* window_width > 0, finite */
+  clwh_mem *values;           /* optional float32[height][width]: the projected value */
+  clwh_mem *t_extreme;        /* optional float32[height][width] */
+} clwh_projection_desc;
+int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc *desc);
 
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
