@@ -1,14 +1,9 @@
-// clwh_internal.hpp -- structures shared by the host runtime and the HIP kernels.
+// clwh_internal.hpp -- what the host runtime and the HIP kernels share: argument structs and launcher prototypes.
+// Host-only types (contexts, memory objects, owners of device memory) are in clwh_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <atomic>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
 
 #include "../../include/clwh.h"
 
@@ -97,7 +92,7 @@ struct RenderArgs {
   uint32_t num_tile_slots; // tile slots of this rank
   int32_t n_seeds;
   int32_t seeds[CLWH_MAX_SEEDS];
-  // scheduling knobs of k_bounce (defaults in clwh_runtime.hip; CLWH_TUNE_* override for experiments)
+  // scheduling knobs of k_bounce (defaults in clwh_host.hpp, Tuning; CLWH_TUNE_* override for experiments)
   int32_t step_min_lanes;    // keep stepping while at least this many lanes march
   int32_t refill_min_lanes;  // idle lanes fetch new items once this many are idle (64: only an empty wave refills)
   int32_t force_long_launch; // tests: schedule every launch like a long one (thresholds 16 / 16, exit certificates)
@@ -138,15 +133,6 @@ struct SdfArgs {
   TfDev tf;
 };
 
-// hiprtc fallback for TF source outside the rule grammar (tf_jit.cpp)
-int tf_jit_compile(const char *user_source, std::vector<char> &code, std::string &log);
-struct JitTf {
-  std::string source;
-  std::vector<char> code;
-  hipModule_t module = nullptr;
-  hipFunction_t classify = nullptr;
-};
-
 // host-side launchers implemented in the .hip files
 hipError_t launch_repack(const RepackArgs &a, hipStream_t s);
 // log2 of the macro cell's edge: 16 voxels up to 512^3, then growing with the volume so that the table (8 B per cell) stays at a
@@ -166,6 +152,10 @@ inline int macro_cell_shift(int X, int Y, int Z, int forced) {
 hipError_t launch_macro_table(const uint32_t *brick_min, int NBX, int NBY, int NBZ, uint8_t *macro, int X, int Y, int Z, int shift, hipStream_t s);
 hipError_t launch_primary(const RenderArgs &a, hipStream_t s);
 hipError_t launch_bounce(const RenderArgs &a, hipStream_t s);
+// the bounce kernel's queue arithmetic needs ceil(hits / 64) x seeds below 2^24 (64 seeds: 16.7 M hit pixels); udivmod24
+inline bool bounce_queues_fit(uint32_t n_hits, int32_t unit_block_log2, int32_t n_seeds) {
+  return (uint64_t)(((n_hits + 63u) >> 6) + 8u * (1u << unit_block_log2)) * (uint64_t)n_seeds < (1ull << 24);
+}
 hipError_t launch_env_fixup(const RenderArgs &a, hipStream_t s);
 hipError_t launch_commit(const RenderArgs &a, hipStream_t s);
 // planned voxel-cache launches: sort keys of the camera's hits (their cache entries), the token deal of one launch, the launch's sums into the cache
@@ -264,164 +254,4 @@ struct ProjArgs {
 hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s);
 hipError_t launch_projection(const ProjArgs &a, int mode, bool dense, hipStream_t s);
 
-// ---- derived scene data (step bytes + hit records + per-brick minima + exit-certificate table), ONE copy per device however many
-// contexts (frame lanes, callers) render the same (volume content, SDF content, transfer function): contexts hold it by
-// shared_ptr and find it in a process-wide registry (clwh_runtime.hip); the memory goes when the last context lets go of it.
-struct PackedScene {
-  int device = 0;
-  uint8_t *data = nullptr;
-  size_t bytes = 0;
-  const void *vol = nullptr, *sdf = nullptr;
-  uint64_t vol_ver = 0, sdf_ver = 0;
-  TfDev tf{};
-  std::string tf_identity;   // opaque (hiprtc) transfer functions: the source text -- two sources may share a palette
-  int32_t macro_shift = 0;
-  uint64_t generation = 0;   // process-wide unique id of this content (part of the primary-hit key)
-  hipEvent_t ready = nullptr;  // recorded on the building stream after the last build kernel; adopters make their stream wait for it
-  bool stale = false;        // clwh_ctx_invalidate_derived: nobody adopts it any more
-  ~PackedScene();
-};
-
-// content version of a device allocation, shared by every clwh_mem that names the same device pointer (the owner and all
-// wraps): a push, a rebuild or clwh_mem_mark_dirty through ANY of them is seen by all
-struct VersionCell {
-  std::atomic<uint64_t> v{0};
-};
-
 }  // namespace clvr
-
-// ---- opaque handle layouts (host only)
-struct clwh_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipEvent_t handoff_event = nullptr;  // clwh_ctx_acquire_from / clwh_ctx_release_to
-  // per-camera primary hits (derived data, rebuilt when the key below changes)
-  uint32_t *pix_slot = nullptr;
-  size_t pix_slot_bytes = 0;
-  clvr::HitRec *hits = nullptr;
-  size_t hits_bytes = 0;
-  uint32_t *render_counters = nullptr;  // kRenderCounters x u32 on the device
-  static constexpr size_t kRenderCounters = 32 * 9;
-  uint32_t *fixups = nullptr;
-  size_t fixups_bytes = 0;
-  unsigned long long *delta = nullptr;
-  size_t delta_bytes = 0;
-  // planned voxel-cache launches: the camera's hits grouped by voxel (sorted once per camera), this launch's grants
-  uint8_t *vox_plan = nullptr;     // keys_in | keys_sorted (int64 each) | iota | order | grants (u32 each), n_capacity elements each
-  size_t vox_plan_bytes = 0;
-  void *vox_temp = nullptr;
-  size_t vox_temp_bytes = 0;
-  bool vox_plan_valid = false;
-  uint32_t vox_plan_n = 0;         // elements sorted (the hit count, or its bound when the plan was made)
-  // hiprtc-compiled transfer functions, by source text; and the class bytes of the current (volume, source)
-  std::map<std::string, std::shared_ptr<clvr::JitTf>> jit_cache;
-  uint8_t *jit_cls = nullptr;
-  size_t jit_cls_bytes = 0;
-  unsigned long long *jit_palette = nullptr;  // CLWH_TF_MAX_RULES keys + 1 error word
-  const void *jit_vol = nullptr;
-  uint64_t jit_vol_ver = 0;
-  std::string jit_source;
-  clvr::TfDev jit_tf{};
-  bool fixup_overflow_pending = false;
-  uint32_t *sticky_flags = nullptr;  // [0] fix-up buffer overflow: set by kernels, cleared only when the host has read it
-  // measured on MI355X (round 1, git history: profiles/r01_tune_*.txt): a wave that runs its 64 samples to completion with
-  // steps and events in separate wave-wide phases beats mid-flight refills (12.5 vs 7.6 Gsamples/s)
-  int32_t tune_step_min_lanes = 0;    // 0: chosen per launch (launch_bounce)
-  int32_t tune_refill_min_lanes = 0;  // 0: chosen per launch (launch_bounce)
-  int32_t tune_macro_shift = 0;       // CLWH_TUNE_MACRO_SHIFT: 4..8 forces the macro cell's edge to 2^n voxels (0: by volume size)
-  int32_t tune_bounce_rays = 1;       // CLWH_TUNE_BOUNCE_RAYS=2: k_bounce2 for long launches
-  int32_t tune_force_long_launch = 0; // CLWH_TUNE_LONG_LAUNCH=1: every launch is scheduled like a long one (the parity tests use it)
-  int32_t tune_literal_gradient = 0;
-  int32_t tune_unit_block_log2 = 4;
-  int32_t tune_unit_group = 1, tune_unit_affinity = 0, tune_unit_queues = 8;
-  int32_t tune_cert_min_step = -1;  // CLWH_TUNE_CERT: 0 = exit certificates off; -1 = by volume size (12 at 512^3, 24 at 1024^3, 48 at 2048^3:
-                                    // the best of the sweeps in profiles/r02_sweep_k_bounce_lds_state.txt)
-  uint32_t tune_bounce_max_blocks = 2048;  // CLWH_TUNE_BLOCKS
-  bool primary_valid = false;
-  uint32_t primary_n_hits = 0;
-  bool primary_n_hits_known = false;  // false: the count of this camera's hits is only on the device so far
-  // the count travels to the host behind the camera's k_primary without anybody waiting for it: a 4-byte copy into page-locked
-  // memory + an event; later launches of the same camera pick it up once the event has completed (hipEventQuery)
-  uint32_t *host_n_hits = nullptr;
-  hipEvent_t n_hits_event = nullptr;
-  bool n_hits_in_flight = false;
-  uint32_t last_known_n_hits = 0;     // of any earlier camera of this context (0: none yet): sizes work buffers while the count is unknown
-  struct PrimaryKey {
-    float cam_pos[3], cam_dir[3];
-    int32_t frame_w, frame_h, launch_w, launch_h, tile_rank, tile_world;
-    int64_t cache_entries;
-    int32_t mode, shading;
-    uint64_t packed_generation;
-    // miss pixels keep the environment colour of their camera ray: the env map's identity and content are part of the key
-    const void *env;
-    uint64_t env_version;
-    int32_t env_w, env_h;
-  } primary_key{};
-  float *bilateral_weights = nullptr;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)
-  int32_t *sdf_counters = nullptr;  // 160 ints: settled voxels per layer
-  uint8_t *sdf_flags = nullptr;     // 4 x tiles bytes (current / next / being cleared / done)
-  size_t sdf_flags_bytes = 0;
-  uint32_t *sdf_bits = nullptr;     // bit-parallel build: event bits, two reached-set buffers, block states
-  size_t sdf_bits_bytes = 0;
-  int32_t tune_sdfbit_waves = 8;    // CLWH_TUNE_SDFBIT_WAVES: 8 or 16 waves per block of the bit-parallel build
-  int32_t tune_sdfbit_grid = 512;   // CLWH_TUNE_SDFBIT_GRID: its persistent grid
-  int32_t tune_sdfbit_rec_lds = 0;  // CLWH_TUNE_SDFBIT_REC=lds: the layer records in LDS, three blocks of eight waves per CU (grid x 3 / 2)
-  int32_t tune_sdf_front = 0;       // CLWH_TUNE_SDF=front: the byte-front build (one launch per layer) instead of the bit-parallel one
-  // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per
-  // brick), the macro-cell table -- shared with every other context of the device that renders the same scene
-  std::shared_ptr<clvr::PackedScene> scene;
-  // intensity projections: the volume in brick order + the per-brick {min, max} table (one allocation, per context), and the key
-  // of the content it was built from (device pointer, shared content version, dims)
-  uint8_t *proj_data = nullptr;
-  size_t proj_bytes = 0;
-  bool proj_valid = false;
-  const void *proj_vol = nullptr;
-  uint64_t proj_vol_ver = 0;
-  size_t proj_dims[3] = {0, 0, 0};
-
-  // timing: one HIP event pair per clwh_render, recorded on the context's stream around the
-  // dominant kernel and read back (without a sync per pass) by clwh_ctx_timing_read
-  bool timing = false;
-  std::vector<hipEvent_t> ev_begin, ev_end;
-  std::vector<int> ev_which;  // enum clwh_timer of each pair
-  size_t ev_used = 0;
-};
-
-struct clwh_mem {
-  clwh_ctx *ctx = nullptr;
-  void *dptr = nullptr;
-  size_t bytes = 0;
-  bool owned = false;
-  bool is_image = false;
-  size_t dims[3] = {1, 1, 1};
-  int channels = 1;
-  int elem_kind = CLWH_ELEM_U8;
-  int flags = 0;
-  std::shared_ptr<clvr::VersionCell> cell;  // shared with every other clwh_mem of the same device pointer
-  uint64_t version() const { return cell ? cell->v.load(std::memory_order_relaxed) : 0; }
-};
-
-// a new content version for the object's device memory (seen through every clwh_mem that names the same pointer)
-void clwh_touch(clwh_mem *m);
-
-enum clwh_kernel_id {
-  CLWH_K_EMPTY = 0,
-  CLWH_K_RENDER,
-  CLWH_K_SDF_BASE,
-  CLWH_K_SDF_LAYER,
-  CLWH_K_BUFFER_RESET,
-  CLWH_K_FETCH_STATS,
-  CLWH_K_APPLY_CLIP,
-  CLWH_K_TF_SORT_VALUES,
-  CLWH_K_TF_FLUSH_COLOR_FRAME,
-  CLWH_K_BILATERAL_FILTER
-};
-
-struct clwh_kernel {
-  clwh_ctx *ctx = nullptr;
-  int id = CLWH_K_EMPTY;
-  clwh_tf tf{};
-  bool has_tf = false;
-  std::shared_ptr<clvr::JitTf> jit;  // set when the source is outside the rule grammar
-};

@@ -1,0 +1,96 @@
+// clwh_projection.hip -- clwh_render_projection on the host: intensity projections of the volume.
+// The kernels are in projection_kernels.hip.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "clwh_host.hpp"
+
+using namespace clvr;
+
+// the volume in brick order + the per-brick {min, max} table, rebuilt when the key (device pointer, shared content version, dims)
+// changes -- the dims are part of it, so two wraps of one pointer with permuted dims never share a layout
+static int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, ProjArgs &a) {
+  ProjectionData &p = ctx->proj;
+  const int X = (int)volume->dims[0], Y = (int)volume->dims[1], Z = (int)volume->dims[2];
+  const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 7) / 8;
+  const size_t n_bricks = (size_t)NBX * NBY * NBZ;
+  const size_t off_table = n_bricks * 512u * sizeof(int16_t);
+  const size_t bytes = off_table + n_bricks * sizeof(uint32_t);
+  const bool same = p.valid && p.vol == volume->dptr && p.vol_ver == volume->version() &&
+                    p.dims[0] == volume->dims[0] && p.dims[1] == volume->dims[1] && p.dims[2] == volume->dims[2];
+  if (!same) {
+    p.valid = false;
+    CLWH_TRY(p.data.reserve(ctx->stream, bytes));
+    ProjRepackArgs r;
+    r.volume = (const int16_t *)volume->dptr;
+    r.X = X; r.Y = Y; r.Z = Z;
+    r.NBX = NBX; r.NBY = NBY; r.NBZ = NBZ;
+    r.bricks = p.data.as<int16_t>();
+    r.table = reinterpret_cast<uint32_t *>(p.data.as<uint8_t>() + off_table);
+    HIP_TRY(launch_proj_repack(r, ctx->stream));
+    p.valid = true;
+    p.vol = volume->dptr;
+    p.vol_ver = volume->version();
+    for (int q = 0; q < 3; ++q) p.dims[q] = volume->dims[q];
+  }
+  a.bricks = p.data.as<int16_t>();
+  a.table = reinterpret_cast<const uint32_t *>(p.data.as<uint8_t>() + off_table);
+  a.X = X; a.Y = Y; a.Z = Z;
+  a.NBX = NBX; a.NBY = NBY;
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc *d) {
+  if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
+  if (!is_image(d->frame, 2, 4, CLWH_ELEM_U8) || !is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;
+  if (d->mode != CLWH_PROJ_MAX && d->mode != CLWH_PROJ_MIN && d->mode != CLWH_PROJ_MEAN) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_PROJ_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->t_near <= d->t_far) || d->t_near == INFINITY) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
+  if (!dims_fit_int32(d->volume)) return CLWH_ERR_INVALID_VALUE;
+  // every kept sample lies in the volume's box, at most `far` from the camera: k < 2^30 once far / step < 2^29 (|d| = 1 within
+  // float rounding), which bounds the kernels' 32-bit sample indices (ProjArgs::k_cap)
+  double far = 0.0;
+  for (int c = 0; c < 8; ++c) {
+    double s2 = 0.0;
+    for (int q = 0; q < 3; ++q) {
+      const double corner = (c >> q) & 1 ? (double)d->volume->dims[q] : 0.0;
+      s2 += (corner - (double)d->cam_pos[q]) * (corner - (double)d->cam_pos[q]);
+    }
+    far = std::max(far, std::sqrt(s2));
+  }
+  if (!(far / (double)d->step < 536870912.0)) return CLWH_ERR_INVALID_VALUE;  // (false for a NaN or infinite camera)
+  if (!launch_size_ok(d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > 65535u || d->height > 65535u) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > d->frame->dims[0] || d->height > d->frame->dims[1]) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if ((d->values && d->values->bytes < out_bytes) || (d->t_extreme && d->t_extreme->bytes < out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  ProjArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a));
+  a.frame = (uint32_t *)d->frame->dptr;
+  a.frame_w = (int32_t)d->frame->dims[0];
+  a.frame_h = (int32_t)d->frame->dims[1];
+  a.launch_w = (int32_t)d->width;
+  a.launch_h = (int32_t)d->height;
+  a.tiles_x = a.launch_w / 8;
+  a.num_tiles = a.tiles_x * (a.launch_h / 8);
+  for (int q = 0; q < 3; ++q) {
+    a.cam_pos[q] = d->cam_pos[q];
+    a.cam_dir[q] = d->cam_dir[q];
+  }
+  a.step = d->step;
+  a.t_near = d->t_near;
+  a.t_far = d->t_far;
+  a.window_center = d->window_center;
+  a.window_width = d->window_width;
+  a.k_cap = 1 << 30;
+  a.values = d->values ? (float *)d->values->dptr : nullptr;
+  a.t_extreme = d->t_extreme ? (float *)d->t_extreme->dptr : nullptr;
+  HIP_TRY(launch_projection(a, d->mode, (d->flags & CLWH_PROJ_DENSE) != 0, ctx->stream));
+  return CLWH_OK;
+}

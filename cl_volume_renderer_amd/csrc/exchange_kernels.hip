@@ -16,7 +16,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "clwh_internal.hpp"
+#include "clwh_host.hpp"
 #include "device_math.hpp"
 
 struct clwh_exchange_plan {
@@ -81,22 +81,16 @@ hipError_t sort_entry_pairs(void *temp, size_t &temp_bytes, const int64_t *keys_
 
 using namespace clvr;
 
-#define HIP_TRY_X(expr)                                                          \
-  do {                                                                           \
-    hipError_t _e = (expr);                                                      \
-    if (_e != hipSuccess) return _e == hipErrorOutOfMemory ? CLWH_ERR_OUT_OF_MEMORY : CLWH_ERR_HIP; \
-  } while (0)
-
 extern "C" {
 
 int clwh_debug_float_conversions(clwh_ctx *ctx, clwh_mem *floats_in, uint64_t n, clwh_mem *i32_out, clwh_mem *u32_out) {
   if (!ctx || !floats_in || !i32_out || !u32_out) return CLWH_ERR_INVALID_VALUE;
   if (floats_in->bytes < n * 4 || i32_out->bytes < n * 8 || u32_out->bytes < n * 8 || n >= (1ull << 31)) return CLWH_ERR_SIZE_MISMATCH;
   if (n == 0) return CLWH_OK;
-  HIP_TRY_X(hipSetDevice(ctx->device));
+  HIP_TRY(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_debug_conversions, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, (const float *)floats_in->dptr, n,
                      (int32_t *)i32_out->dptr, (uint32_t *)u32_out->dptr);
-  HIP_TRY_X(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return CLWH_OK;
 }
 
@@ -104,9 +98,9 @@ int clwh_debug_wave_min(clwh_ctx *ctx, clwh_mem *u32_in, uint64_t n, clwh_mem *u
   if (!ctx || !u32_in || !u32_out) return CLWH_ERR_INVALID_VALUE;
   if ((n & 63u) != 0 || u32_in->bytes < n * 4 || u32_out->bytes < (n / 64) * 8 || n >= (1ull << 37)) return CLWH_ERR_SIZE_MISMATCH;
   if (n == 0) return CLWH_OK;
-  HIP_TRY_X(hipSetDevice(ctx->device));
+  HIP_TRY(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_debug_wave_min, dim3((unsigned)(n / 64)), dim3(64), 0, ctx->stream, (const uint32_t *)u32_in->dptr, n / 64, (uint32_t *)u32_out->dptr);
-  HIP_TRY_X(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return CLWH_OK;
 }
 
@@ -124,39 +118,33 @@ int clwh_cache_exchange_plan(clwh_ctx *ctx, clwh_mem *entries, uint64_t n, clwh_
   if (!ctx || !entries || !out) return CLWH_ERR_INVALID_VALUE;
   *out = nullptr;
   if (n >= (1ull << 32) || entries->bytes < n * sizeof(int64_t)) return CLWH_ERR_SIZE_MISMATCH;
-  HIP_TRY_X(hipSetDevice(ctx->device));
+  HIP_TRY(hipSetDevice(ctx->device));
   clwh_exchange_plan *p = new (std::nothrow) clwh_exchange_plan();
   if (!p) return CLWH_ERR_OUT_OF_MEMORY;
   p->ctx = ctx;
   p->n = n;
   *out = p;
   if (n == 0) return CLWH_OK;
-  uint32_t *iota = nullptr;
-  void *temp = nullptr;
-  size_t temp_bytes = 0;
-  int rc = CLWH_OK;
+  DeviceBuffer iota, temp;  // the sort's scratch goes with this call
   auto fail = [&](int code) {
-    if (iota) (void)hipFree(iota);
-    if (temp) (void)hipFree(temp);
     (void)clwh_cache_exchange_plan_release(p);
     *out = nullptr;
     return code;
   };
   if (hipMalloc((void **)&p->sorted_entries, n * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&p->order, n * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void **)&iota, n * sizeof(uint32_t)) != hipSuccess)
+      iota.reserve(ctx->stream, n * sizeof(uint32_t)) != CLWH_OK)
     return fail(CLWH_ERR_OUT_OF_MEMORY);
-  hipLaunchKernelGGL(k_iota, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, iota, n);
+  hipLaunchKernelGGL(k_iota, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, iota.as<uint32_t>(), n);
   const int64_t *keys_in = (const int64_t *)entries->dptr;
+  size_t temp_bytes = 0;
   // radix sorts are stable: equal entries keep the caller's (rank, pixel) order
-  if (rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, p->sorted_entries, iota, p->order, (size_t)n, 0u, 64u, ctx->stream) != hipSuccess)
+  if (rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, p->sorted_entries, iota.as<uint32_t>(), p->order, (size_t)n, 0u, 64u, ctx->stream) != hipSuccess)
     return fail(CLWH_ERR_HIP);
-  if (hipMalloc(&temp, temp_bytes ? temp_bytes : 16) != hipSuccess) return fail(CLWH_ERR_OUT_OF_MEMORY);
-  if (rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, p->sorted_entries, iota, p->order, (size_t)n, 0u, 64u, ctx->stream) != hipSuccess)
+  if (temp.reserve(ctx->stream, temp_bytes ? temp_bytes : 16) != CLWH_OK) return fail(CLWH_ERR_OUT_OF_MEMORY);
+  if (rocprim::radix_sort_pairs(temp.ptr, temp_bytes, keys_in, p->sorted_entries, iota.as<uint32_t>(), p->order, (size_t)n, 0u, 64u, ctx->stream) != hipSuccess)
     return fail(CLWH_ERR_HIP);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(CLWH_ERR_HIP);  // once per camera; the scratch goes here
-  (void)hipFree(iota);
-  (void)hipFree(temp);
-  return rc;
+  return CLWH_OK;
 }
 
 int clwh_cache_apply_contributions(clwh_ctx *ctx, clwh_exchange_plan *plan, clwh_mem *buffer_volume, clwh_mem *rgb, int32_t rgb_stride) {
@@ -164,11 +152,11 @@ int clwh_cache_apply_contributions(clwh_ctx *ctx, clwh_exchange_plan *plan, clwh
   if (rgb_stride < 3) return CLWH_ERR_INVALID_VALUE;
   if (rgb->bytes < plan->n * (uint64_t)rgb_stride * sizeof(int32_t) || buffer_volume->bytes < 8) return CLWH_ERR_SIZE_MISMATCH;
   if (plan->n == 0) return CLWH_OK;
-  HIP_TRY_X(hipSetDevice(ctx->device));
+  HIP_TRY(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_apply_contributions, dim3((unsigned)((plan->n + 255u) / 256u)), dim3(256), 0, ctx->stream, plan->sorted_entries,
                      plan->order, plan->n, (const int32_t *)rgb->dptr, (int)rgb_stride, (uint32_t *)buffer_volume->dptr,
                      (int64_t)(buffer_volume->bytes / 8));
-  HIP_TRY_X(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   clwh_touch(buffer_volume);
   return CLWH_OK;
 }

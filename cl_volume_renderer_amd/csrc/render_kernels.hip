@@ -1558,7 +1558,7 @@ hipError_t launch_bounce(const RenderArgs &a_in, hipStream_t s) {
   // is bound by its longest chain of dependent fetches, where the look-up is one more of them: 0.263 ms per pass without, 0.277 with
   a.cert_min_lanes = kCertPhaseMinLanes;
   if (!long_launch) a.cert_min_step = 0;
-  if ((uint64_t)(((a.n_hits + 63u) >> 6) + 8u * (1u << a.unit_block_log2)) * (uint64_t)a.n_seeds >= (1ull << 24)) return hipErrorInvalidValue;  // udivmod24
+  if (!bounce_queues_fit(a.n_hits, a.unit_block_log2, a.n_seeds)) return hipErrorInvalidValue;
   const bool g = a.tf.uses_gradient != 0;
   // fewer than 2^23 bricks (up to ~1600^3): every step byte has a 32-bit offset -> the march's 32-bit addressing, with
   // the index terms of the three axes in LDS tables

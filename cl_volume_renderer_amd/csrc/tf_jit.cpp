@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "clwh_internal.hpp"
+#include "clwh_host.hpp"
 
 namespace clvr {
 

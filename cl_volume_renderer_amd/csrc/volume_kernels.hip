@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void k_apply_clip8(const int16_t *__restrict__
 // 5x5x5 bilateral filter of the short volume (sigma_s 0.6, sigma_r 1).  The weight of a tap is
 // exp(-r2/(2*0.6^2) - d^2/2) with r2 the squared integer offset (13 values) and d the integer difference
 // to the centre voxel; it rounds to zero for |d| >= 16, so all weights the kernel can ever use are a
-// 13 x 17 table the host evaluates once in binary64 (`weights`, clwh_runtime.hip) -- no transcendental on
+// 13 x 17 table the host evaluates once in binary64 (`weights`, clwh_launch.hip) -- no transcendental on
 // the device.  A block filters an 8x8x8 brick out of a 12^3 LDS tile (3.4 KB); the 125 taps are
 // accumulated in the reference's z, y, x order, un-contracted, so the two float sums round identically.
 // HBM traffic is one read and one write of the volume; the kernel is LDS/VALU bound (125 taps per voxel).
