@@ -1,8 +1,10 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--projection=max|min|mean] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
+// --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
+// ambient 0.3 when shaded).
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +24,7 @@
 
 int main(int argc_in, char const *argv_in[]) {
   int projection = -1;  // clwh_projection, or -1: path-traced frames
+  int composite = -1;   // 0: plain, 1: shaded, or -1
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
     const std::string a = argv_in[i];
@@ -32,14 +35,25 @@ int main(int argc_in, char const *argv_in[]) {
         std::cout << "Unknown projection '" << m << "' (max, min or mean)\n";
         return 1;
       }
+    } else if (a == "--composite" || a == "--composite=plain") {
+      composite = 0;
+    } else if (a == "--composite=shaded") {
+      composite = 1;
+    } else if (a.rfind("--composite", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' (--composite or --composite=shaded)\n";
+      return 1;
     } else {
       args.push_back(argv_in[i]);
     }
   }
+  if (projection >= 0 && composite >= 0) {
+    std::cout << "--projection and --composite exclude each other\n";
+    return 1;
+  }
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -64,6 +78,9 @@ int main(int argc_in, char const *argv_in[]) {
   emitter->next_event_code_set(tf_generate_source(rv.get_volume_stats(), selection));
   emitter->flush_changes();
 
+  const int lut_first = -1024, lut_len = 4096;
+  const std::vector<float> lut = tf_composite_lut(selection, lut_first, lut_len, 0.05f);
+
   ui_state state{argv[1], true, height, width, Position3D(-200, 200, -200), {0.9f, 6.183f}, true};
   const double scale = rv.get_volume_size()[0] / 512.0;  // the default camera is placed for a 512^3 volume
   state.position = Position3D(-200 * scale, 200 * scale, -200 * scale);
@@ -76,7 +93,10 @@ int main(int argc_in, char const *argv_in[]) {
   for (int f = 0; f < frames; ++f) {
     bool changed = false;
     state.cam_changed = true;  // progressive refinement: keep sampling the same view
-    if (projection >= 0)
+    if (composite >= 0)
+      frame = static_cast<const unsigned char *>(
+          r.render_composite(state, lut, lut_first, lut_len, 0.5f, 0.95f, composite == 1 ? CLWH_COMP_SHADE : 0, 0.3f));
+    else if (projection >= 0)
       frame = static_cast<const unsigned char *>(r.render_projection(state, projection, 0.0f, 4000.0f));
     else
       frame = static_cast<const unsigned char *>(emitter->render_frame(state, changed));
@@ -96,9 +116,10 @@ int main(int argc_in, char const *argv_in[]) {
       for (int x = 0; x < width; ++x) ppm.write(reinterpret_cast<const char *>(frame + ((size_t)y * SCREEN_WIDTH + x) * 4), 3);
   }
   static const char *const kProjectionNames[] = {"max", "min", "mean"};
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s}\n",
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s}\n",
               frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
-              projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "");
+              projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "",
+              composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "");
   for (tf_selection *s : selection) delete s;
   return 0;
 }

@@ -90,6 +90,30 @@ const void *clvr_host_render_projection(clvr_host *h, const float pos[3], const 
   return h->rend.render_projection(h->state, mode, center, window_width, step);
 }
 
+// renderer::render_composite from the same camera arguments: lut = float32[lut_len][4]; the RGBA8 frame (SCREEN_WIDTH x SCREEN_HEIGHT)
+const void *clvr_host_render_composite(clvr_host *h, const float pos[3], const float look[2], int width, int height, const float *lut,
+                                       int lut_first, int lut_len, float step, float alpha_stop, int flags, float ambient) {
+  h->state.position = Position3D(pos[0], pos[1], pos[2]);
+  h->state.direction_look[0] = look[0];
+  h->state.direction_look[1] = look[1];
+  h->state.width = width;
+  h->state.height = height;
+  const std::vector<float> table(lut, lut + (size_t)(lut_len > 0 ? lut_len : 0) * 4);
+  return h->rend.render_composite(h->state, table, lut_first, lut_len, step, alpha_stop, flags, ambient);
+}
+// tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
+void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
+  std::vector<tf_selection *> sel;
+  for (int i = 0; i < n; ++i) {
+    auto *r = new tf_rect_selection((unsigned)i, rects[i * 8 + 0], rects[i * 8 + 1], rects[i * 8 + 2], rects[i * 8 + 3]);
+    for (int c = 0; c < 4; ++c) r->color[c] = rects[i * 8 + 4 + c];
+    sel.push_back(r);
+  }
+  const std::vector<float> lut = tf_composite_lut(sel, lut_first, lut_len, opacity);
+  for (auto *s : sel) delete s;
+  if (!lut.empty()) std::memcpy(out, lut.data(), lut.size() * sizeof(float));
+}
+
 size_t clvr_host_cache_len(clvr_host *h) { return h->rend.voxel_cache().size(); }
 void clvr_host_pull_cache(clvr_host *h, unsigned short *out) {
   auto &c = h->rend.voxel_cache();

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <set>
 
@@ -20,6 +21,7 @@ renderer::renderer(clw_context &c)
       frame(ctx, std::vector<unsigned char>((size_t)SCREEN_WIDTH * SCREEN_HEIGHT * 4), {SCREEN_WIDTH, SCREEN_HEIGHT, 1}),
       buffer_volume(ctx, std::vector<unsigned short>(8 * 4)),
       tfframe(ctx, std::vector<unsigned char>(2 * 2 * 4), {2, 2, 1}),
+      composite_lut(ctx, std::vector<float>(4)),
       sdf(ctx) {}
 
 void renderer::image_set(const reference_volume *rv, const env_map *map) {
@@ -110,6 +112,40 @@ void *renderer::render_projection(struct ui_state &state, int mode, float center
   d.window_center = center;
   d.window_width = width;
   clw_fail_hard_on_error(clwh_render_projection(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
+void *renderer::render_composite(struct ui_state &state, const std::vector<float> &lut, int lut_first, int lut_len, float step,
+                                 float alpha_stop, int flags, float ambient) {
+  if (lut_len < 1 || lut.size() < (size_t)lut_len * 4) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);
+  // a new table only when the contents changed: the push gives the device memory a new content version, which rebuilds the
+  // library's derived prefix table
+  const bool same = composite_lut.size() == lut.size() && std::memcmp(&composite_lut[0], lut.data(), lut.size() * sizeof(float)) == 0;
+  if (!same || !composite_lut_pushed) {
+    composite_lut = clw_vector<float>(ctx, std::vector<float>(lut), true);
+    composite_lut_pushed = true;
+  }
+  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
+  clwh_composite_desc d{};
+  d.frame = frame.get_device_reference();
+  d.volume = volume->get_reference_volume().get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    d.cam_pos[q] = (float)state.position.val[q];
+    d.cam_dir[q] = (float)vec.val[q];
+  }
+  d.width = (uint32_t)state.width;
+  d.height = (uint32_t)state.height;
+  d.flags = flags;
+  d.step = step;
+  d.t_near = 0.0f;
+  d.t_far = INFINITY;
+  d.lut = composite_lut.get_device_reference();
+  d.lut_first = lut_first;
+  d.lut_len = lut_len;
+  d.alpha_stop = alpha_stop;
+  d.ambient = ambient;
+  clw_fail_hard_on_error(clwh_render_composite(ctx.get_handle(), &d));
   frame.pull();
   return &frame[0];
 }

@@ -2,6 +2,7 @@
 // public methods as the reference's app/renderer.hpp:10-29, so `ui::run(&renderer)` is a drop-in.
 #pragma once
 #include <string>
+#include <vector>
 
 #include <clw_context.hpp>
 #include <clw_foreign_memory.hpp>
@@ -35,6 +36,14 @@ class renderer : public frame_emitter {
   // voxels.  Pulls the frame and returns its host copy.
   void *render_projection(struct ui_state &state, int mode, float center, float width, float step = 0.5f);
 
+  // not in the reference: direct volume rendering -- the samples of every camera ray composited front to back through the
+  // colour/opacity table `lut` (float32[lut_len][4], entry 0 = voxel value lut_first; tf_composite_lut makes one from the editor's
+  // selections), converged after this one launch.  Same camera and frame image as render_frame, so it lines up with the path-traced
+  // frame pixel for pixel.  flags: CLWH_COMP_DENSE | CLWH_COMP_SHADE (`ambient` is read with the latter).  The table is pushed when
+  // it differs from the last call's.  Pulls the frame (premultiplied RGBA8) and returns its host copy.
+  void *render_composite(struct ui_state &state, const std::vector<float> &lut, int lut_first, int lut_len, float step = 0.5f,
+                         float alpha_stop = 0.95f, int flags = 0, float ambient = 0.3f);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }
@@ -45,6 +54,8 @@ class renderer : public frame_emitter {
   clw_image<unsigned char, 4> frame;         // RGBA8 frame the caller blits
   clw_vector<unsigned short> buffer_volume;  // world-space radiance cache, 4 x u16 per voxel
   clw_image<unsigned char, 4> tfframe;
+  clw_vector<float> composite_lut;           // render_composite's table on the device (host copy = the last one pushed)
+  bool composite_lut_pushed = false;
   const reference_volume *volume = nullptr;  // borrowed
   const env_map *emap = nullptr;             // borrowed
   signed_distance_field sdf;

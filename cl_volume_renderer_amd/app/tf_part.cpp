@@ -24,3 +24,20 @@ std::string tf_generate_source(Volume_Stats stats, const std::vector<tf_selectio
   code += "  \n  return false;\n}\n";
   return code;
 }
+
+std::vector<float> tf_composite_lut(const std::vector<tf_selection *> &selections, int lut_first, int lut_len, float opacity) {
+  std::vector<float> lut((size_t)(lut_len > 0 ? lut_len : 0) * 4, 0.0f);
+  for (int i = 0; i < lut_len; ++i) {
+    const float v = (float)(lut_first + i);
+    for (const tf_selection *s : selections) {
+      const auto *r = dynamic_cast<const tf_rect_selection *>(s);
+      if (!r || !(r->min_v <= v && v <= r->max_v)) continue;
+      lut[(size_t)i * 4 + 0] = r->color[0];
+      lut[(size_t)i * 4 + 1] = r->color[1];
+      lut[(size_t)i * 4 + 2] = r->color[2];
+      lut[(size_t)i * 4 + 3] = r->color[3] * opacity;
+      break;
+    }
+  }
+  return lut;
+}

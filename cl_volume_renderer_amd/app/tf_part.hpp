@@ -26,5 +26,11 @@ class tf_rect_selection : public tf_selection {
   unsigned id;
 };
 
+/// not in the reference: the colour/opacity table renderer::render_composite (clwh_render_composite) reads, from the editor's
+/// rectangles: float32[lut_len][4], entry i for voxel value v = lut_first + i = (color[0], color[1], color[2], color[3] * opacity) of
+/// the FIRST tf_rect_selection with min_v <= v <= max_v (the order is_event_gen tests them in), zeros when there is none.  The
+/// gradient bounds are ignored (the table is indexed by value alone) and so are selections of other kinds.  Host only.
+std::vector<float> tf_composite_lut(const std::vector<tf_selection *> &selections, int lut_first, int lut_len, float opacity);
+
 /// "inline bool is_event_gen(short value, short gradient, int4 *color){ ... return false; }"
 std::string tf_generate_source(Volume_Stats stats, const std::vector<tf_selection *> &selections);

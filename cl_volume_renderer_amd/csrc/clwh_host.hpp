@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip).
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections and compositing).
 // No kernel needs this header.
 #pragma once
 
@@ -204,14 +204,21 @@ struct SdfScratch {
 #endif
 };
 
-// intensity projections: the volume in brick order + the per-brick {min, max} table (one allocation, per context), and the key
-// of the content it was built from (device pointer, shared content version, dims)
+// intensity projections and compositing: the volume in brick order + the per-brick {min, max} table (one allocation, per context,
+// shared by clwh_render_projection and clwh_render_composite), and the key of the content it was built from (device pointer, shared
+// content version, dims).  Beside it the derived data of compositing's colour/opacity table: the prefix count of entries with
+// a > 0, keyed the same way (device pointer, shared content version, length).
 struct ProjectionData {
   DeviceBuffer data;
   bool valid = false;  // cleared by clwh_ctx_invalidate_derived (projection)
   const void *vol = nullptr;
   uint64_t vol_ver = 0;
   size_t dims[3] = {0, 0, 0};
+  DeviceBuffer lut_prefix;
+  bool lut_valid = false;  // cleared by clwh_ctx_invalidate_derived (projection)
+  const void *lut = nullptr;
+  uint64_t lut_ver = 0;
+  int32_t lut_len = 0;
 };
 
 // timing: one HIP event pair per timed region, recorded on the context's stream and read back (without a sync per pass) by

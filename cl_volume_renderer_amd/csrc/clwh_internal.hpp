@@ -254,4 +254,27 @@ struct ProjArgs {
 hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s);
 hipError_t launch_projection(const ProjArgs &a, int mode, bool dense, hipStream_t s);
 
+// ---- compositing through a colour/opacity table (composite_kernels.hip): the projections' bricked copy and {min, max} table plus
+// the table's prefix count of entries with a > 0, built by k_comp_prefix
+struct CompArgs {
+  const int16_t *bricks;
+  const uint32_t *table;
+  int32_t X, Y, Z, NBX, NBY;
+  uint32_t *frame;        // RGBA8 packed, row-major, frame_w x frame_h
+  int32_t frame_w, frame_h;
+  int32_t launch_w, launch_h, tiles_x, num_tiles;
+  float cam_pos[3], cam_dir[3];
+  float step, t_near, t_far;
+  int32_t k_cap;          // as ProjArgs::k_cap
+  const float4 *lut;      // lut_len entries (r, g, b, a), 16-byte aligned
+  const uint32_t *prefix; // prefix[i] = number of entries j <= i with a > 0
+  int32_t lut_first, lut_len;
+  float alpha_stop, ambient;
+  float4 *rgba;           // optional, row-major launch_w x launch_h
+  float *t_first;         // optional, same
+  float *t_stop;          // optional, same
+};
+hipError_t launch_comp_prefix(const float4 *lut, int32_t lut_len, uint32_t *prefix, hipStream_t s);
+hipError_t launch_composite(const CompArgs &a, bool shade, bool dense, hipStream_t s);
+
 }  // namespace clvr

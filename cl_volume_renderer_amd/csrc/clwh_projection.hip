@@ -1,5 +1,6 @@
-// clwh_projection.hip -- clwh_render_projection on the host: intensity projections of the volume.
-// The kernels are in projection_kernels.hip.
+// clwh_projection.hip -- clwh_render_projection and clwh_render_composite on the host: intensity projections of the volume and
+// compositing through a colour/opacity table.  Both march the same bricked copy of the volume (ensure_projection_data).
+// The kernels are in projection_kernels.hip and composite_kernels.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,7 +11,8 @@ using namespace clvr;
 
 // the volume in brick order + the per-brick {min, max} table, rebuilt when the key (device pointer, shared content version, dims)
 // changes -- the dims are part of it, so two wraps of one pointer with permuted dims never share a layout
-static int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, ProjArgs &a) {
+template <class Args>
+static int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, Args &a) {
   ProjectionData &p = ctx->proj;
   const int X = (int)volume->dims[0], Y = (int)volume->dims[1], Z = (int)volume->dims[2];
   const int NBX = (X + 7) / 8, NBY = (Y + 7) / 8, NBZ = (Z + 7) / 8;
@@ -41,6 +43,20 @@ static int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, ProjArg
   return CLWH_OK;
 }
 
+// distance from the camera to the farthest corner of the volume's box (infinite for an infinite camera)
+static double farthest_corner(const clwh_mem *volume, const float cam_pos[3]) {
+  double far = 0.0;
+  for (int c = 0; c < 8; ++c) {
+    double s2 = 0.0;
+    for (int q = 0; q < 3; ++q) {
+      const double corner = (c >> q) & 1 ? (double)volume->dims[q] : 0.0;
+      s2 += (corner - (double)cam_pos[q]) * (corner - (double)cam_pos[q]);
+    }
+    far = std::max(far, std::sqrt(s2));
+  }
+  return far;
+}
+
 extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc *d) {
   if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
   if (!is_image(d->frame, 2, 4, CLWH_ELEM_U8) || !is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;
@@ -52,16 +68,7 @@ extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc 
   if (!dims_fit_int32(d->volume)) return CLWH_ERR_INVALID_VALUE;
   // every kept sample lies in the volume's box, at most `far` from the camera: k < 2^30 once far / step < 2^29 (|d| = 1 within
   // float rounding), which bounds the kernels' 32-bit sample indices (ProjArgs::k_cap)
-  double far = 0.0;
-  for (int c = 0; c < 8; ++c) {
-    double s2 = 0.0;
-    for (int q = 0; q < 3; ++q) {
-      const double corner = (c >> q) & 1 ? (double)d->volume->dims[q] : 0.0;
-      s2 += (corner - (double)d->cam_pos[q]) * (corner - (double)d->cam_pos[q]);
-    }
-    far = std::max(far, std::sqrt(s2));
-  }
-  if (!(far / (double)d->step < 536870912.0)) return CLWH_ERR_INVALID_VALUE;  // (false for a NaN or infinite camera)
+  if (!(farthest_corner(d->volume, d->cam_pos) / (double)d->step < 536870912.0)) return CLWH_ERR_INVALID_VALUE;  // (false for an infinite camera)
   if (!launch_size_ok(d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
   if (d->width > 65535u || d->height > 65535u) return CLWH_ERR_BAD_NDRANGE;
   if (d->width > d->frame->dims[0] || d->height > d->frame->dims[1]) return CLWH_ERR_BAD_NDRANGE;
@@ -92,5 +99,77 @@ extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc 
   a.values = d->values ? (float *)d->values->dptr : nullptr;
   a.t_extreme = d->t_extreme ? (float *)d->t_extreme->dptr : nullptr;
   HIP_TRY(launch_projection(a, d->mode, (d->flags & CLWH_PROJ_DENSE) != 0, ctx->stream));
+  return CLWH_OK;
+}
+
+// the prefix count of "a > 0" over the table, rebuilt when the key (device pointer, shared content version, length) changes
+static int ensure_lut_prefix(clwh_ctx *ctx, const clwh_mem *lut, int32_t lut_len, CompArgs &a) {
+  ProjectionData &p = ctx->proj;
+  const bool same = p.lut_valid && p.lut == lut->dptr && p.lut_ver == lut->version() && p.lut_len == lut_len;
+  if (!same) {
+    p.lut_valid = false;
+    CLWH_TRY(p.lut_prefix.reserve(ctx->stream, (size_t)lut_len * sizeof(uint32_t)));
+    HIP_TRY(launch_comp_prefix((const float4 *)lut->dptr, lut_len, p.lut_prefix.as<uint32_t>(), ctx->stream));
+    p.lut_valid = true;
+    p.lut = lut->dptr;
+    p.lut_ver = lut->version();
+    p.lut_len = lut_len;
+  }
+  a.prefix = p.lut_prefix.as<uint32_t>();
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *d) {
+  if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
+  if (!is_image(d->frame, 2, 4, CLWH_ELEM_U8) || !is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;
+  if (!d->lut || !d->lut->dptr || (reinterpret_cast<uintptr_t>(d->lut->dptr) & 15u) != 0u) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~(CLWH_COMP_DENSE | CLWH_COMP_SHADE)) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->lut_len < 1 || d->lut_len > 65536 || d->lut_first < -65536 || d->lut_first > 65535) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->alpha_stop > 0.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN; +inf never stops early)
+  const bool shade = (d->flags & CLWH_COMP_SHADE) != 0;
+  if (shade && !(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->t_near <= d->t_far) || d->t_near == INFINITY) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
+  if (!dims_fit_int32(d->volume)) return CLWH_ERR_INVALID_VALUE;
+  // (std::max in farthest_corner drops a NaN distance, so a camera that is not finite is refused by name)
+  if (!(std::isfinite(d->cam_pos[0]) && std::isfinite(d->cam_pos[1]) && std::isfinite(d->cam_pos[2]))) return CLWH_ERR_INVALID_VALUE;
+  if (!(farthest_corner(d->volume, d->cam_pos) / (double)d->step < 536870912.0)) return CLWH_ERR_INVALID_VALUE;  // as the projections
+  if (!launch_size_ok(d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > 65535u || d->height > 65535u) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > d->frame->dims[0] || d->height > d->frame->dims[1]) return CLWH_ERR_BAD_NDRANGE;
+  if (d->lut->bytes < (size_t)d->lut_len * 16u) return CLWH_ERR_SIZE_MISMATCH;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (d->rgba && d->rgba->bytes < 4u * out_bytes) return CLWH_ERR_SIZE_MISMATCH;
+  if ((d->t_first && d->t_first->bytes < out_bytes) || (d->t_stop && d->t_stop->bytes < out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  CompArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a));
+  CLWH_TRY(ensure_lut_prefix(ctx, d->lut, d->lut_len, a));
+  a.frame = (uint32_t *)d->frame->dptr;
+  a.frame_w = (int32_t)d->frame->dims[0];
+  a.frame_h = (int32_t)d->frame->dims[1];
+  a.launch_w = (int32_t)d->width;
+  a.launch_h = (int32_t)d->height;
+  a.tiles_x = a.launch_w / 8;
+  a.num_tiles = a.tiles_x * (a.launch_h / 8);
+  for (int q = 0; q < 3; ++q) {
+    a.cam_pos[q] = d->cam_pos[q];
+    a.cam_dir[q] = d->cam_dir[q];
+  }
+  a.step = d->step;
+  a.t_near = d->t_near;
+  a.t_far = d->t_far;
+  a.k_cap = 1 << 30;
+  a.lut = (const float4 *)d->lut->dptr;
+  a.lut_first = d->lut_first;
+  a.lut_len = d->lut_len;
+  a.alpha_stop = d->alpha_stop;
+  a.ambient = d->ambient;
+  a.rgba = d->rgba ? (float4 *)d->rgba->dptr : nullptr;
+  a.t_first = d->t_first ? (float *)d->t_first->dptr : nullptr;
+  a.t_stop = d->t_stop ? (float *)d->t_stop->dptr : nullptr;
+  HIP_TRY(launch_composite(a, shade, (d->flags & CLWH_COMP_DENSE) != 0, ctx->stream));
   return CLWH_OK;
 }

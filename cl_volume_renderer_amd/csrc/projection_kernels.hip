@@ -1,14 +1,6 @@
 // projection_kernels.hip -- maximum / minimum / mean intensity projections of the caller's S16 image (clwh_render_projection).
 //
-// The contract (include/clwh.h) is exact so that it can be tested bit for bit: sample k of a pixel's ray sits at t_k = (float)k * h,
-// p_k = o + d * t_k (per component one multiply, then one add; the library is built without contraction), and is KEPT iff
-// t_near <= t_k <= t_far and 0 <= p_k.c < dim_c on all three axes; its value is the voxel at floor(p_k).
-//
-// Why the kernels may bound loops by boxes: float multiply and add are monotone, so each coordinate of p_k is monotone in k (and t_k
-// too).  Every condition of "kept" therefore switches at most once along the ray, and the kept samples of a ray form ONE contiguous
-// range of k; so do the kept samples inside any axis-aligned box, such as an 8^3 brick, and once the march has left a brick it never
-// comes back to it.  Box intersections in float only give a starting guess for a search; the exact per-sample test decides every
-// boundary (first_false below), so the sample set is the dense loop's whatever the guess.
+// The exact sample set of a ray and the brick walk over it are in projection_device.hpp (shared with composite_kernels.hip).
 //
 //   k_proj_repack            the caller's image -> brick order (packed_volume.hpp inner_index: one 4^3 sub-brick of int16 = one 128-byte
 //                            line) + a {min, max} pair per 8^3 brick over its real voxels
@@ -17,7 +9,7 @@
 //                            running extreme -- max <= best for MAX, min >= best for MIN -- is stepped over without reading it.  A tie
 //                            cannot move t_extreme (the first sample that attains the extreme wins and the walk runs front to back), so
 //                            the result is bit-identical to the dense walk.
-#include "render_device.hpp"
+#include "projection_device.hpp"
 
 namespace clvr {
 
@@ -88,83 +80,6 @@ __global__ __launch_bounds__(256) void k_proj_repack(const ProjRepackArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// the exact sample test
-struct ProjRay {
-  f3 o, d;
-  float h, t_near, t_far;
-  float dx, dy, dz;  // volume dims
-};
-
-__device__ __forceinline__ f3 proj_sample(const ProjRay &r, int k, float &t) {
-  t = (float)k * r.h;
-  return f3{r.o.x + r.d.x * t, r.o.y + r.d.y * t, r.o.z + r.d.z * t};
-}
-// "kept" split into the conditions that can only switch from false to true as k grows (rising) and those that can only switch from
-// true to false (falling): kept(k) = rising(k) && falling(k), so the kept range is [first rising k, last falling k].  An axis the ray
-// does not move along (d.c == +-0, or NaN) keeps p.c == o.c while t is finite: its test is falling (an infinite t makes it NaN).
-__device__ __forceinline__ bool axis_rising(float p, float d, float dim) { return d > 0.0f ? p >= 0.0f : (d < 0.0f ? p < dim : true); }
-__device__ __forceinline__ bool axis_falling(float p, float d, float dim) {
-  return d > 0.0f ? p < dim : (d < 0.0f ? p >= 0.0f : (p >= 0.0f && p < dim));
-}
-__device__ __forceinline__ bool proj_rising(const ProjRay &r, int k) {
-  float t;
-  const f3 p = proj_sample(r, k, t);
-  return t >= r.t_near && axis_rising(p.x, r.d.x, r.dx) && axis_rising(p.y, r.d.y, r.dy) && axis_rising(p.z, r.d.z, r.dz);
-}
-__device__ __forceinline__ bool proj_falling(const ProjRay &r, int k) {
-  float t;
-  const f3 p = proj_sample(r, k, t);
-  return t <= r.t_far && axis_falling(p.x, r.d.x, r.dx) && axis_falling(p.y, r.d.y, r.dy) && axis_falling(p.z, r.d.z, r.dz);
-}
-
-// The smallest k in (lo, hi] with pred(k) false, given pred(lo) true and pred true-then-false on [lo, hi]; hi + 1 if there is none.
-// `guess` (a float estimate of the answer) only decides where the search starts: gallop away from it, then bisect.
-template <class Pred>
-__device__ __forceinline__ int first_false(int lo, int hi, int guess, Pred pred) {
-  int f = hi + 1;  // pred is false at f, or f lies past the range
-  const int g = guess <= lo ? lo + 1 : (guess > f ? f : guess);
-  if (g < f && pred(g)) {
-    lo = g;
-    for (int s = 1; lo + s < f; s <<= 1) {
-      if (!pred(lo + s)) { f = lo + s; break; }
-      lo += s;
-    }
-  } else {
-    f = g;
-    for (int s = 1; f - s > lo; s <<= 1) {
-      if (pred(f - s)) { lo = f - s; break; }
-      f -= s;
-    }
-  }
-  while (f - lo > 1) {
-    const int m = lo + ((f - lo) >> 1);
-    if (pred(m)) lo = m; else f = m;
-  }
-  return f;
-}
-
-// a float sample index as a search start in [0, cap] (NaN -> 0)
-__device__ __forceinline__ int index_guess(float kf, int cap) { return (int)fminf(fmaxf(kf, 0.0f), (float)cap); }
-
-// the ray's kept range [ka, kb]; false if it is empty
-__device__ __forceinline__ bool proj_kept_range(const ProjRay &r, int k_cap, int &ka, int &kb) {
-  float te = r.t_near, tx = r.t_far;  // slab estimate of the entry and exit
-  const float dv[3] = {r.d.x, r.d.y, r.d.z}, ov[3] = {r.o.x, r.o.y, r.o.z}, dim[3] = {r.dx, r.dy, r.dz};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (dv[c] != 0.0f) {
-      const float a = (0.0f - ov[c]) / dv[c], b = (dim[c] - ov[c]) / dv[c];
-      te = fmaxf(te, fminf(a, b));
-      tx = fminf(tx, fmaxf(a, b));
-    }
-  }
-  if (!proj_falling(r, 0)) return false;
-  kb = first_false(0, k_cap - 1, index_guess(floorf(tx / r.h) + 1.0f, k_cap), [&](int k) { return proj_falling(r, k); }) - 1;
-  ka = proj_rising(r, 0) ? 0 : first_false(0, kb, index_guess(ceilf(te / r.h), k_cap), [&](int k) { return !proj_rising(r, k); });
-  return ka <= kb;
-}
-
 enum : int { PROJ_MAX = CLWH_PROJ_MAX, PROJ_MIN = CLWH_PROJ_MIN, PROJ_MEAN = CLWH_PROJ_MEAN };
 
 template <int MODE, bool SKIP>
@@ -191,16 +106,7 @@ __global__ __launch_bounds__(64) void k_projection(const ProjArgs a) {
       const f3 p = proj_sample(r, k, t);  // kept: 0 <= p < dim, so the conversions are floors
       const unsigned bx = (unsigned)(int)p.x >> 3, by = (unsigned)(int)p.y >> 3, bz = (unsigned)(int)p.z >> 3;
       const size_t brick = ((size_t)bz * (size_t)a.NBY + (size_t)by) * (size_t)a.NBX + (size_t)bx;
-      // where the ray leaves the brick's box (the guess), then the exact first sample outside it
-      float tb = INFINITY;
-      if (r.d.x != 0.0f) tb = fminf(tb, ((float)((bx + (r.d.x > 0.0f ? 1u : 0u)) * 8u) - r.o.x) / r.d.x);
-      if (r.d.y != 0.0f) tb = fminf(tb, ((float)((by + (r.d.y > 0.0f ? 1u : 0u)) * 8u) - r.o.y) / r.d.y);
-      if (r.d.z != 0.0f) tb = fminf(tb, ((float)((bz + (r.d.z > 0.0f ? 1u : 0u)) * 8u) - r.o.z) / r.d.z);
-      const int k_end = first_false(k, kb, index_guess(floorf(tb / r.h) + 1.0f, a.k_cap), [&](int j) {
-        float tj;
-        const f3 q = proj_sample(r, j, tj);
-        return ((unsigned)(int)q.x >> 3) == bx && ((unsigned)(int)q.y >> 3) == by && ((unsigned)(int)q.z >> 3) == bz;
-      });
+      const int k_end = proj_brick_exit(r, k, kb, bx, by, bz, a.k_cap);
       bool skip = false;
       if constexpr (SKIP) {
         const uint32_t mm = a.table[brick];

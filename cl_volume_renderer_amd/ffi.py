@@ -20,6 +20,7 @@ ACCUM_VOXEL_CACHE, ACCUM_IMAGE_SPACE = 0, 1
 DERIVED_SCENE, DERIVED_CAMERA, DERIVED_PROJECTION = 1, 2, 4
 PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2
 PROJ_DENSE = 1
+COMP_DENSE, COMP_SHADE = 1, 2
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -89,6 +90,19 @@ class ProjectionDesc(C.Structure):
     ]
 
 
+class CompositeDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("volume", C.c_void_p),
+        ("cam_pos", C.c_float * 3), ("cam_dir", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("flags", C.c_int32),
+        ("step", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float),
+        ("lut", C.c_void_p), ("lut_first", C.c_int32), ("lut_len", C.c_int32),
+        ("alpha_stop", C.c_float), ("ambient", C.c_float),
+        ("rgba", C.c_void_p), ("t_first", C.c_void_p), ("t_stop", C.c_void_p),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -124,6 +138,7 @@ _PROTOTYPES = [
     ("clwh_ctx_invalidate_derived", C.c_int, [C.c_void_p, C.c_int]),
     ("clwh_ctx_scene_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     ("clwh_render_projection", C.c_int, [C.c_void_p, C.POINTER(ProjectionDesc)]),
+    ("clwh_render_composite", C.c_int, [C.c_void_p, C.POINTER(CompositeDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -379,6 +394,29 @@ class Context:
         d.values = values.h if values is not None else None
         d.t_extreme = t_extreme.h if t_extreme is not None else None
         _check(lib().clwh_render_projection(self.h, C.byref(d)), "clwh_render_projection")
+
+    def render_composite(self, frame: Mem, volume: Mem, cam_pos, cam_dir, width, height, lut: Mem, lut_first, lut_len=None, step=0.5,
+                         alpha_stop=0.95, flags=0, ambient=0.3, t_near=0.0, t_far=float("inf"), rgba: Mem = None,
+                         t_first: Mem = None, t_stop: Mem = None):
+        """front-to-back compositing of `volume` (S16) through the colour/opacity table `lut` (float32[lut_len][4], entry 0 = voxel
+        value lut_first) into `frame` (RGBA8, premultiplied) with clwh_render's camera rays.  flags: COMP_DENSE | COMP_SHADE.
+        rgba / t_first / t_stop: optional float32 buffers over the launched region.  lut_len defaults to the whole buffer."""
+        d = CompositeDesc()
+        d.frame, d.volume = frame.h, volume.h
+        for k in range(3):
+            d.cam_pos[k] = float(cam_pos[k])
+            d.cam_dir[k] = float(cam_dir[k])
+        d.width, d.height = int(width), int(height)
+        d.flags = int(flags)
+        d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
+        d.lut = lut.h if lut is not None else None
+        d.lut_first = int(lut_first)
+        d.lut_len = int(lut_len if lut_len is not None else (lut.nbytes // 16 if lut is not None else 0))
+        d.alpha_stop, d.ambient = float(alpha_stop), float(ambient)
+        d.rgba = rgba.h if rgba is not None else None
+        d.t_first = t_first.h if t_first is not None else None
+        d.t_stop = t_stop.h if t_stop is not None else None
+        _check(lib().clwh_render_composite(self.h, C.byref(d)), "clwh_render_composite")
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -210,8 +210,9 @@ int clwh_frame_from_tiles(clwh_ctx *ctx, clwh_mem *tiles_all_ranks, int32_t tile
  *                        2048^3 -- and it is freed when the last of them lets go.  Invalidating makes THIS context
  *                        rebuild; contexts already sharing the old copy keep it until their own inputs change.
  *   CLWH_DERIVED_CAMERA  primary hits (function of the camera and of the scene), per context
- *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table of clwh_render_projection, per
- *                        context (2 bytes per voxel + 4 per 8^3 brick) */
+ *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table that clwh_render_projection and
+ *                        clwh_render_composite share, per context (ONE copy: 2 bytes per voxel + 4 per 8^3 brick), and with it the
+ *                        prefix count over clwh_render_composite's colour/opacity table (4 bytes per entry): both are dropped */
 enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2, CLWH_DERIVED_PROJECTION = 4 };
 int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what);
 /* which copy of the derived scene data the context renders from (after its last clwh_render): a process-wide unique id
@@ -251,6 +252,63 @@ typedef struct clwh_projection_desc {
   clwh_mem *t_extreme;        /* optional float32[height][width] */
 } clwh_projection_desc;
 int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc *desc);
+
+/* ---- direct volume rendering: emission-absorption compositing of a ray's samples through a colour/opacity table, front to back, in
+ * one launch (not in the reference).  Camera rays, step, t_near, t_far, the launched region and the meaning of KEPT sample are those
+ * of clwh_render_projection, word for word: sample k >= 0 sits at t_k = (float)k * step, p_k = o + d * t_k (per component one float
+ * multiply, then one float add), kept iff t_near <= t_k <= t_far and 0 <= p_k.c < dim_c on all three axes; its voxel is
+ * v = V[floor(p.z)][floor(p.y)][floor(p.x)].
+ * The table `lut` holds float32[lut_len][4] (r, g, b, a) on the device, 16-byte aligned, in at least 16 * lut_len bytes; lut_first is
+ * the voxel value of entry 0, and a value's entry is i = min(max((int)v - lut_first, 0), lut_len - 1).  The table's contents are NOT
+ * checked (that would need a device round trip); the arithmetic below defines the result for any bit pattern.
+ * Per pixel, in float32, without contraction, with C = (0, 0, 0), A = 0, t_first = t_stop = NaN, for the kept samples in increasing k:
+ *   1. (r, g, b, a) = lut[i].  If !(a > 0) (so also for NaN) the sample changes nothing; go to the next.
+ *   2. With CLWH_COMP_SHADE only: gx = (float)(V(x+1,y,z) - V(x-1,y,z)), likewise gy, gz, the differences taken in int32 with each
+ *      neighbour coordinate clamped to [0, dim-1]; l2 = (gx*gx + gy*gy) + gz*gz; if l2 > 0:
+ *      c = fabsf((gx*d.x + gy*d.y) + gz*d.z) / sqrtf(l2), s = ambient + (1.0f - ambient) * fminf(c, 1.0f), else s = 1.0f; then
+ *      r = r*s, g = g*s, b = b*s (sqrtf and / correctly rounded).  Two-sided headlight shading: the light is the camera ray.
+ *   3. w = (1.0f - A) * a; C.c = C.c + w * c_c for r, g, b (one multiply, then one add); A = A + w.
+ *   4. If t_first is NaN, t_first = t_k.  If A >= alpha_stop: t_stop = t_k and the ray ends; no later sample is read.
+ * Outputs: frame pixel (q(C.r), q(C.g), q(C.b), q(A)) with q(x) = (int)fminf(fmaxf(x * 255.0f + 0.5f, 0.0f), 255.0f), where fmaxf and
+ * fminf return the other operand for a NaN (premultiplied colour; a pixel without a contributing sample is (0, 0, 0, 0), as in the
+ * projections).  Optional rgba (float32[height][width][4] = C.r, C.g, C.b, A; a NaN is stored as the quiet NaN 0x7FC00000, since
+ * IEEE 754 leaves a NaN's sign and payload to the implementation), t_first, t_stop (float32[height][width]), all row-major over the
+ * launched region.  Pixels of the frame outside the region are not touched.
+ * A sample with !(a > 0) is a no-op by step 1, so without CLWH_COMP_DENSE the kernel steps over an 8^3 brick when no table entry in
+ * [clamp(min - lut_first), clamp(max - lut_first)] has a > 0 (clamping is monotone, so every voxel of the brick maps into that
+ * range): same bytes, by the contract.  Early termination (step 4) is part of the contract, not an optimisation: CLWH_COMP_DENSE
+ * reads every kept sample up to t_stop.  No opacity correction for the step size: the caller scales the table.
+ * Errors: a NULL or wrong-kind handle (lut NULL or not 16-byte aligned included), unknown flag bits, lut_len outside [1, 65536],
+ * lut_first outside [-65536, 65535], !(alpha_stop > 0) (+inf is allowed: never stop early), ambient outside [0, 1] or NaN when
+ * CLWH_COMP_SHADE is set, and every step / slab / camera-distance / volume-dims condition of clwh_render_projection:
+ * CLWH_ERR_INVALID_VALUE (a zero-initialised descriptor is rejected: step == 0).  The region conditions of the projections:
+ * CLWH_ERR_BAD_NDRANGE.  A lut smaller than 16 * lut_len bytes, rgba smaller than 16 * width * height or t_first / t_stop smaller than
+ * 4 * width * height bytes: CLWH_ERR_SIZE_MISMATCH.
+ * Asynchronous and ordered on the context's stream; no host wait.  The derived data (CLWH_DERIVED_PROJECTION) is the projections'
+ * bricked copy of the volume, shared with them, plus a prefix count of "a > 0" over the table, keyed on the table's device pointer,
+ * its shared content version and lut_len: a push, clwh_mem_mark_dirty or a write through another clwh_mem of the same pointer
+ * rebuilds it. */
+enum clwh_composite_flags {
+  CLWH_COMP_DENSE = 1,  /* no brick skipping: same result by contract; for tests and timing */
+  CLWH_COMP_SHADE = 2   /* step 2 */
+};
+typedef struct clwh_composite_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image; its dims are generate_ray's totals (as clwh_render_desc.frame) */
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  float cam_pos[3], cam_dir[3];
+  uint32_t width, height;     /* launched region: multiples of 8, <= frame dims, <= 65535 */
+  int32_t flags;
+  float step;                 /* h > 0, finite */
+  float t_near, t_far;        /* slab along the ray; 0 and +INFINITY = whole volume */
+  clwh_mem *lut;              /* float32[lut_len][4] */
+  int32_t lut_first, lut_len;
+  float alpha_stop;           /* > 0; +INFINITY = never stop early */
+  float ambient;              /* [0, 1]; read with CLWH_COMP_SHADE only */
+  clwh_mem *rgba;             /* optional float32[height][width][4] */
+  clwh_mem *t_first;          /* optional float32[height][width] */
+  clwh_mem *t_stop;           /* optional float32[height][width] */
+} clwh_composite_desc;
+int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *desc);
 
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
