@@ -1,11 +1,14 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
 // ambient 0.3 when shaded).
+// --isosurface=VALUE[,below]: the frames show the isosurface of the trilinear field at VALUE (renderer::render_isosurface: step 0.5,
+// 8 refinement steps, white, ambient 0.3; ",below": the first position at or below VALUE).
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +28,8 @@
 int main(int argc_in, char const *argv_in[]) {
   int projection = -1;  // clwh_projection, or -1: path-traced frames
   int composite = -1;   // 0: plain, 1: shaded, or -1
+  bool isosurface = false, iso_below = false;
+  float iso_value = 0.0f;
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
     const std::string a = argv_in[i];
@@ -42,6 +47,27 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--composite", 0) == 0) {
       std::cout << "Unknown option '" << a << "' (--composite or --composite=shaded)\n";
       return 1;
+    } else if (a.rfind("--isosurface=", 0) == 0) {
+      std::string v = a.substr(13);
+      const size_t comma = v.find(',');
+      if (comma != std::string::npos) {
+        if (v.substr(comma + 1) != "below") {
+          std::cout << "Unknown option '" << a << "' (--isosurface=VALUE or --isosurface=VALUE,below)\n";
+          return 1;
+        }
+        iso_below = true;
+        v = v.substr(0, comma);
+      }
+      char *end = nullptr;
+      iso_value = std::strtof(v.c_str(), &end);
+      if (v.empty() || *end != '\0' || !std::isfinite(iso_value)) {
+        std::cout << "Bad isosurface value '" << v << "'\n";
+        return 1;
+      }
+      isosurface = true;
+    } else if (a.rfind("--isosurface", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' (--isosurface=VALUE or --isosurface=VALUE,below)\n";
+      return 1;
     } else {
       args.push_back(argv_in[i]);
     }
@@ -50,10 +76,14 @@ int main(int argc_in, char const *argv_in[]) {
     std::cout << "--projection and --composite exclude each other\n";
     return 1;
   }
+  if (isosurface && (projection >= 0 || composite >= 0)) {
+    std::cout << "--isosurface excludes --projection and --composite\n";
+    return 1;
+  }
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -93,7 +123,9 @@ int main(int argc_in, char const *argv_in[]) {
   for (int f = 0; f < frames; ++f) {
     bool changed = false;
     state.cam_changed = true;  // progressive refinement: keep sampling the same view
-    if (composite >= 0)
+    if (isosurface)
+      frame = static_cast<const unsigned char *>(r.render_isosurface(state, iso_value, iso_below ? CLWH_ISO_BELOW : 0));
+    else if (composite >= 0)
       frame = static_cast<const unsigned char *>(
           r.render_composite(state, lut, lut_first, lut_len, 0.5f, 0.95f, composite == 1 ? CLWH_COMP_SHADE : 0, 0.3f));
     else if (projection >= 0)
@@ -116,10 +148,11 @@ int main(int argc_in, char const *argv_in[]) {
       for (int x = 0; x < width; ++x) ppm.write(reinterpret_cast<const char *>(frame + ((size_t)y * SCREEN_WIDTH + x) * 4), 3);
   }
   static const char *const kProjectionNames[] = {"max", "min", "mean"};
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s}\n",
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s}\n",
               frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
               projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "",
-              composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "");
+              composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "",
+              isosurface ? (", \"isosurface\": " + std::to_string(iso_value) + ", \"below\": " + (iso_below ? "true" : "false")).c_str() : "");
   for (tf_selection *s : selection) delete s;
   return 0;
 }

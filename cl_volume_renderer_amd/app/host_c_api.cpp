@@ -101,6 +101,16 @@ const void *clvr_host_render_composite(clvr_host *h, const float pos[3], const f
   const std::vector<float> table(lut, lut + (size_t)(lut_len > 0 ? lut_len : 0) * 4);
   return h->rend.render_composite(h->state, table, lut_first, lut_len, step, alpha_stop, flags, ambient);
 }
+// renderer::render_isosurface from the same camera arguments: color = float[3]; the RGBA8 frame (SCREEN_WIDTH x SCREEN_HEIGHT)
+const void *clvr_host_render_isosurface(clvr_host *h, const float pos[3], const float look[2], int width, int height, float iso,
+                                        int flags, float step, int refine, float ambient, const float color[3]) {
+  h->state.position = Position3D(pos[0], pos[1], pos[2]);
+  h->state.direction_look[0] = look[0];
+  h->state.direction_look[1] = look[1];
+  h->state.width = width;
+  h->state.height = height;
+  return h->rend.render_isosurface(h->state, iso, flags, step, refine, ambient, color[0], color[1], color[2]);
+}
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

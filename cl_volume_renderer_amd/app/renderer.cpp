@@ -150,6 +150,33 @@ void *renderer::render_composite(struct ui_state &state, const std::vector<float
   return &frame[0];
 }
 
+void *renderer::render_isosurface(struct ui_state &state, float iso, int flags, float step, int refine, float ambient, float red,
+                                  float green, float blue) {
+  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
+  clwh_isosurface_desc d{};
+  d.frame = frame.get_device_reference();
+  d.volume = volume->get_reference_volume().get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    d.cam_pos[q] = (float)state.position.val[q];
+    d.cam_dir[q] = (float)vec.val[q];
+  }
+  d.width = (uint32_t)state.width;
+  d.height = (uint32_t)state.height;
+  d.flags = flags;
+  d.step = step;
+  d.t_near = 0.0f;
+  d.t_far = INFINITY;
+  d.iso = iso;
+  d.refine = refine;
+  d.color[0] = red;
+  d.color[1] = green;
+  d.color[2] = blue;
+  d.ambient = ambient;
+  clw_fail_hard_on_error(clwh_render_isosurface(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
 // reference :45-124 -- the 2-D (value, |gradient|) histogram texture of the transfer-function editor:
 // bin the volume, quantise the counts on the host so that small counts stay distinguishable, rank the
 // distinct counts, colour each bin by its rank.  (The reference declares render_tf(width, height) and

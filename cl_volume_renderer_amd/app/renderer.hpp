@@ -44,6 +44,13 @@ class renderer : public frame_emitter {
   void *render_composite(struct ui_state &state, const std::vector<float> &lut, int lut_first, int lut_len, float step = 0.5f,
                          float alpha_stop = 0.95f, int flags = 0, float ambient = 0.3f);
 
+  // not in the reference: the isosurface of the volume's trilinear field at value `iso` (with CLWH_ISO_BELOW: the first position at or
+  // below it), shaded by a two-sided headlight in `color`, after one launch.  Same camera and frame image as render_frame, so it lines
+  // up with the path-traced frame pixel for pixel.  `refine`: bisection steps between the last outside and the first inside sample.
+  // flags: CLWH_ISO_DENSE | CLWH_ISO_BELOW.  Pulls the frame (a miss is 0, 0, 0, 0) and returns its host copy.
+  void *render_isosurface(struct ui_state &state, float iso, int flags = 0, float step = 0.5f, int refine = 8, float ambient = 0.3f,
+                          float red = 1.0f, float green = 1.0f, float blue = 1.0f);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }

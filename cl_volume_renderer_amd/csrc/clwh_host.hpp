@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections and compositing).
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing and isosurfaces).
 // No kernel needs this header.
 #pragma once
 
@@ -214,6 +214,10 @@ struct ProjectionData {
   const void *vol = nullptr;
   uint64_t vol_ver = 0;
   size_t dims[3] = {0, 0, 0};
+  // clwh_render_isosurface only: the {min, max} table of the bricks dilated by one voxel (and of the cells of 4^3 bricks behind it),
+  // built from `data` by the first isosurface call after `data` was (re)built -- valid only while `valid` is and for the same key
+  DeviceBuffer dilated;
+  bool dilated_valid = false;  // cleared whenever `data` is rebuilt and by clwh_ctx_invalidate_derived (projection)
   DeviceBuffer lut_prefix;
   bool lut_valid = false;  // cleared by clwh_ctx_invalidate_derived (projection)
   const void *lut = nullptr;

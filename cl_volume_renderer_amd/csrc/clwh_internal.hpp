@@ -277,4 +277,30 @@ struct CompArgs {
 hipError_t launch_comp_prefix(const float4 *lut, int32_t lut_len, uint32_t *prefix, hipStream_t s);
 hipError_t launch_composite(const CompArgs &a, bool shade, bool dense, hipStream_t s);
 
+// ---- isosurface of the trilinear field (isosurface_kernels.hip): the projections' bricked copy plus a {min, max} pair per 8^3 brick
+// over the brick DILATED by one voxel (clamped at the volume's faces), built by k_iso_dilate, and the same pair per cell of 4^3 bricks
+struct IsoArgs {
+  const int16_t *bricks;
+  const uint32_t *table;   // the projections' {min, max} table (not read by k_isosurface)
+  const uint32_t *dilated; // per brick: (uint16)min | (uint16)max << 16 over the voxels within one voxel of the brick
+  int32_t X, Y, Z, NBX, NBY;
+  uint32_t *frame;         // RGBA8 packed, row-major, frame_w x frame_h
+  int32_t frame_w, frame_h;
+  int32_t launch_w, launch_h, tiles_x, num_tiles;
+  float cam_pos[3], cam_dir[3];
+  float step, t_near, t_far;
+  int32_t k_cap;           // as ProjArgs::k_cap
+  int64_t threshold;       // T = floor(iso * 2^24)
+  int32_t skip_bound;      // a brick is stepped over iff dmax < skip_bound (ceil(T / 2^24)), BELOW: iff dmin > skip_bound (floor(T / 2^24))
+  int32_t refine;
+  float color[3], ambient;
+  float *t_hit;            // optional, row-major launch_w x launch_h
+  float4 *normal;          // optional, same
+  const uint32_t *coarse;  // the same pair per cell of 4^3 bricks (CNX x CNY x CNZ cells), stored behind `dilated`
+  int32_t CNX, CNY;
+};
+// `dilated` holds NBX * NBY * NBZ entries followed by ceil(NBX / 4) * ceil(NBY / 4) * ceil(NBZ / 4) cell entries
+hipError_t launch_iso_dilate(const int16_t *bricks, int X, int Y, int Z, int NBX, int NBY, int NBZ, uint32_t *dilated, hipStream_t s);
+hipError_t launch_isosurface(const IsoArgs &a, bool below, bool dense, hipStream_t s);
+
 }  // namespace clvr

@@ -1,6 +1,7 @@
-// clwh_projection.hip -- clwh_render_projection and clwh_render_composite on the host: intensity projections of the volume and
-// compositing through a colour/opacity table.  Both march the same bricked copy of the volume (ensure_projection_data).
-// The kernels are in projection_kernels.hip and composite_kernels.hip.
+// clwh_projection.hip -- clwh_render_projection, clwh_render_composite and clwh_render_isosurface on the host: intensity projections
+// of the volume, compositing through a colour/opacity table and the isosurface of the trilinear field.  All march the same bricked
+// copy of the volume (ensure_projection_data).  The kernels are in projection_kernels.hip, composite_kernels.hip and
+// isosurface_kernels.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,7 +23,7 @@ static int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, Args &a
   const bool same = p.valid && p.vol == volume->dptr && p.vol_ver == volume->version() &&
                     p.dims[0] == volume->dims[0] && p.dims[1] == volume->dims[1] && p.dims[2] == volume->dims[2];
   if (!same) {
-    p.valid = false;
+    p.valid = p.dilated_valid = false;  // (the dilated table is derived from this copy)
     CLWH_TRY(p.data.reserve(ctx->stream, bytes));
     ProjRepackArgs r;
     r.volume = (const int16_t *)volume->dptr;
@@ -171,5 +172,77 @@ extern "C" int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *d
   a.t_first = d->t_first ? (float *)d->t_first->dptr : nullptr;
   a.t_stop = d->t_stop ? (float *)d->t_stop->dptr : nullptr;
   HIP_TRY(launch_composite(a, shade, (d->flags & CLWH_COMP_DENSE) != 0, ctx->stream));
+  return CLWH_OK;
+}
+
+// the {min, max} table of the bricks dilated by one voxel and, behind it, of the cells of 4^3 bricks, built from the bricked copy
+// (which ensure_projection_data has just made current: a rebuild of the copy has cleared dilated_valid) by the first isosurface
+// call of a volume content
+static int ensure_dilated_table(clwh_ctx *ctx, IsoArgs &a) {
+  ProjectionData &p = ctx->proj;
+  if (!p.dilated_valid) {
+    const int NBZ = (a.Z + 7) / 8;
+    const size_t n_bricks = (size_t)a.NBX * a.NBY * NBZ, n_cells = (size_t)((a.NBX + 3) / 4) * ((a.NBY + 3) / 4) * ((NBZ + 3) / 4);
+    CLWH_TRY(p.dilated.reserve(ctx->stream, (n_bricks + n_cells) * sizeof(uint32_t)));
+    HIP_TRY(launch_iso_dilate(a.bricks, a.X, a.Y, a.Z, a.NBX, a.NBY, NBZ, p.dilated.as<uint32_t>(), ctx->stream));
+    p.dilated_valid = true;
+  }
+  a.dilated = p.dilated.as<uint32_t>();
+  a.coarse = a.dilated + (size_t)a.NBX * a.NBY * ((a.Z + 7) / 8);
+  a.CNX = (a.NBX + 3) / 4;
+  a.CNY = (a.NBY + 3) / 4;
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc *d) {
+  if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
+  if (!is_image(d->frame, 2, 4, CLWH_ELEM_U8) || !is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~(CLWH_ISO_DENSE | CLWH_ISO_BELOW)) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->iso) && std::fabs(d->iso) <= 65536.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (d->refine < 0 || d->refine > 24) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
+  if (!(std::isfinite(d->color[0]) && std::isfinite(d->color[1]) && std::isfinite(d->color[2]))) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->t_near <= d->t_far) || d->t_near == INFINITY) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
+  if (!dims_fit_int32(d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->cam_pos[0]) && std::isfinite(d->cam_pos[1]) && std::isfinite(d->cam_pos[2]))) return CLWH_ERR_INVALID_VALUE;  // as the compositor
+  if (!(farthest_corner(d->volume, d->cam_pos) / (double)d->step < 536870912.0)) return CLWH_ERR_INVALID_VALUE;  // as the projections
+  if (!launch_size_ok(d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > 65535u || d->height > 65535u) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > d->frame->dims[0] || d->height > d->frame->dims[1]) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if ((d->t_hit && d->t_hit->bytes < out_bytes) || (d->normal && d->normal->bytes < 4u * out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  IsoArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a));
+  CLWH_TRY(ensure_dilated_table(ctx, a));
+  const bool dense = (d->flags & CLWH_ISO_DENSE) != 0, below = (d->flags & CLWH_ISO_BELOW) != 0;
+  a.frame = (uint32_t *)d->frame->dptr;
+  a.frame_w = (int32_t)d->frame->dims[0];
+  a.frame_h = (int32_t)d->frame->dims[1];
+  a.launch_w = (int32_t)d->width;
+  a.launch_h = (int32_t)d->height;
+  a.tiles_x = a.launch_w / 8;
+  a.num_tiles = a.tiles_x * (a.launch_h / 8);
+  for (int q = 0; q < 3; ++q) {
+    a.cam_pos[q] = d->cam_pos[q];
+    a.cam_dir[q] = d->cam_dir[q];
+    a.color[q] = d->color[q];
+  }
+  a.step = d->step;
+  a.t_near = d->t_near;
+  a.t_far = d->t_far;
+  a.k_cap = 1 << 30;
+  // T = floor(iso * 2^24): the product is exact in binary64 (24 significant bits, |.| <= 2^40)
+  a.threshold = (int64_t)std::floor((double)d->iso * 16777216.0);
+  // dmax * 2^24 < T  <=>  dmax < ceil(T / 2^24);  dmin * 2^24 > T  <=>  dmin > floor(T / 2^24)  (>> of a negative int64 is arithmetic)
+  a.skip_bound = below ? (int32_t)(a.threshold >> 24) : (int32_t)(-((-a.threshold) >> 24));
+  a.refine = d->refine;
+  a.ambient = d->ambient;
+  a.t_hit = d->t_hit ? (float *)d->t_hit->dptr : nullptr;
+  a.normal = d->normal ? (float4 *)d->normal->dptr : nullptr;
+  HIP_TRY(launch_isosurface(a, below, dense, ctx->stream));
   return CLWH_OK;
 }

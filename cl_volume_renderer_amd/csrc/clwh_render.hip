@@ -533,7 +533,7 @@ int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what) {
     if (ctx->scene.use_count() > 1) ctx->scene.reset();  // the only holder keeps the allocation and rebuilds in place
   }
   if (what & (CLWH_DERIVED_SCENE | CLWH_DERIVED_CAMERA)) ctx->primary.valid = false;
-  if (what & CLWH_DERIVED_PROJECTION) ctx->proj.valid = ctx->proj.lut_valid = false;
+  if (what & CLWH_DERIVED_PROJECTION) ctx->proj.valid = ctx->proj.lut_valid = ctx->proj.dilated_valid = false;
   return CLWH_OK;
 }
 

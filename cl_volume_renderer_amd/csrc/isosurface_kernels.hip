@@ -1,0 +1,285 @@
+// isosurface_kernels.hip -- the first position along a camera ray where the TRILINEAR field of the volume reaches a value, with its
+// depth, normal and headlight shading (clwh_render_isosurface).  The sample set, the bricked int16 copy of the volume and the brick walk
+// are the projections' (projection_device.hpp, k_proj_repack).  The field is the contract's fixed-point one (include/clwh.h): per axis
+// an 8-bit weight, the 8 corners combined in integers, S = value * 2^24 exactly -- so the hit decision S >= T holds whatever the order
+// of evaluation, and the result can be tested bit for bit.
+//
+//   k_iso_dilate             the derived data: per 8^3 brick the {min, max} over the brick dilated by one voxel (10^3 voxels, clamped at
+//                            the volume's faces), read from the bricked copy; one wave per brick.
+//   k_iso_coarse             the same pair per cell of 4^3 bricks, from k_iso_dilate's table (stored behind it).
+//   k_isosurface<BELOW, SKIP> one wave per 8x8 pixel tile, tiles in XCD-contiguous order (as k_projection); each lane walks its ray's
+//                            kept range brick by brick and ends at the first inside sample.  SKIP (without CLWH_ISO_DENSE): a brick
+//                            whose dilated {min, max} cannot reach T is stepped over unread.  A sample whose voxel floor(p) = v lies in
+//                            the brick has i0 in {v - 1, v} per axis, so its clamped corners lie in the dilated box, and S is a
+//                            combination of their values with non-negative integer weights summing to 2^24: dmin * 2^24 <= S <=
+//                            dmax * 2^24, hence the bytes are the dense walk's.  The walk asks the cell of 4^3 bricks first: its pair
+//                            bounds every brick in it, so a cell that cannot reach T is left by ONE exit search (measured: 1.25-1.55x
+//                            on the surface from outside, 3.2-3.5x where every brick is skipped).  Refinement and the
+//                            normal run once per hit lane, after the march.
+//
+// The sampler (iso_field) is the hot path: 8 two-byte gathers per sample.  A sample's 2x2x2 cell lies inside one 4^3 sub-brick -- one
+// 128-byte line -- unless an axis sits at offset 3 of its sub-brick (58 % of the cells do); the eight indices are formed from per-axis
+// terms without a branch (iso_corners).  The x and y stages of the blend fit int32 (|.| <= 2^31 is reached only by -32768 everywhere);
+// the z stage is one 64-bit multiply-add.
+#include "projection_device.hpp"
+
+namespace clvr {
+
+// ------------------------------------------------------------------------------------------------
+// k_iso_dilate
+__global__ __launch_bounds__(256) void k_iso_dilate(const int16_t *__restrict__ bricks, int X, int Y, int Z, int NBX, int NBY, int NBZ,
+                                                    uint32_t *__restrict__ dilated) {
+  const size_t n_bricks = (size_t)NBX * (size_t)NBY * (size_t)NBZ;
+  const size_t brick = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6);  // uniform over the wave
+  if (brick >= n_bricks) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const int bx = (int)(brick % (size_t)NBX), by = (int)((brick / (size_t)NBX) % (size_t)NBY), bz = (int)(brick / ((size_t)NBX * (size_t)NBY));
+  uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;  // unsigned minima of v + 32768 and 32767 - v, as k_proj_repack
+  for (unsigned i = lane; i < 1000u; i += 64u) {
+    const int hx = (int)(i % 10u), hy = (int)((i / 10u) % 10u), hz = (int)(i / 100u);
+    // a coordinate clamped into the volume names a voxel of the dilated, clamped box again: duplicates do not move a minimum
+    const int x = min(max(bx * 8 - 1 + hx, 0), X - 1), y = min(max(by * 8 - 1 + hy, 0), Y - 1), z = min(max(bz * 8 - 1 + hz, 0), Z - 1);
+    const int v = bricks[VolumePacked::record_index(x, y, z, NBX, NBY)];
+    lo = min(lo, (uint32_t)(v + 32768));
+    hi = min(hi, (uint32_t)(32767 - v));
+  }
+  lo = wave_min_u32(lo);
+  hi = wave_min_u32(hi);
+  if (lane == 0u) {
+    const int vmin = (int)lo - 32768, vmax = 32767 - (int)hi;
+    dilated[brick] = (uint32_t)(uint16_t)vmin | ((uint32_t)(uint16_t)vmax << 16);
+  }
+}
+
+// k_iso_coarse: the second level -- per cell of 4^3 bricks (32^3 voxels) the {min, max} over its bricks' dilated entries, i.e. over the
+// union of their dilated boxes; one thread per cell
+__global__ __launch_bounds__(256) void k_iso_coarse(const uint32_t *__restrict__ dilated, int NBX, int NBY, int NBZ, uint32_t *__restrict__ coarse) {
+  const int CNX = (NBX + 3) / 4, CNY = (NBY + 3) / 4, CNZ = (NBZ + 3) / 4;
+  const size_t cell = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (cell >= (size_t)CNX * CNY * CNZ) return;
+  const int cx = (int)(cell % (size_t)CNX), cy = (int)((cell / (size_t)CNX) % (size_t)CNY), cz = (int)(cell / ((size_t)CNX * CNY));
+  int lo = 32767, hi = -32768;
+  for (int z = cz * 4; z < min(cz * 4 + 4, NBZ); ++z)
+    for (int y = cy * 4; y < min(cy * 4 + 4, NBY); ++y)
+      for (int x = cx * 4; x < min(cx * 4 + 4, NBX); ++x) {
+        const uint32_t mm = dilated[((size_t)z * NBY + y) * NBX + x];
+        lo = min(lo, (int)(int16_t)(mm & 0xFFFFu));
+        hi = max(hi, (int)(int16_t)(mm >> 16));
+      }
+  coarse[cell] = (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16);
+}
+// proj_brick_exit for the box of a coarse cell (32^3 voxels)
+__device__ __forceinline__ int iso_cell_exit(const ProjRay &r, int k, int kb, unsigned cx, unsigned cy, unsigned cz, int k_cap) {
+  float tb = INFINITY;
+  if (r.d.x != 0.0f) tb = fminf(tb, ((float)((cx + (r.d.x > 0.0f ? 1u : 0u)) * 32u) - r.o.x) / r.d.x);
+  if (r.d.y != 0.0f) tb = fminf(tb, ((float)((cy + (r.d.y > 0.0f ? 1u : 0u)) * 32u) - r.o.y) / r.d.y);
+  if (r.d.z != 0.0f) tb = fminf(tb, ((float)((cz + (r.d.z > 0.0f ? 1u : 0u)) * 32u) - r.o.z) / r.d.z);
+  return first_false(k, kb, index_guess(floorf(tb / r.h) + 1.0f, k_cap), [&](int j) {
+    float tj;
+    const f3 q = proj_sample(r, j, tj);
+    return ((unsigned)(int)q.x >> 5) == cx && ((unsigned)(int)q.y >> 5) == cy && ((unsigned)(int)q.z >> 5) == cz;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the field
+struct IsoCell {
+  int ix, iy, iz;  // i0 per axis (-1 .. dim - 1), before clamping
+  int wx, wy, wz;  // weights of the upper corners, 0 .. 255
+};
+__device__ __forceinline__ void iso_axis(float p, int &i0, int &w) {
+  const float q = p - 0.5f, f = floorf(q);
+  i0 = (int)f;
+  w = min((int)((q - f) * 256.0f), 255);
+}
+__device__ __forceinline__ IsoCell iso_cell(const f3 p) {
+  IsoCell c;
+  iso_axis(p.x, c.ix, c.wx);
+  iso_axis(p.y, c.iy, c.wy);
+  iso_axis(p.z, c.iz, c.wz);
+  return c;
+}
+struct IsoCorners {
+  int v000, v100, v010, v110, v001, v101, v011, v111;
+};
+// the 8 corner values of a cell
+__device__ __forceinline__ IsoCorners iso_corners(const IsoArgs &a, const IsoCell &c) {
+  const int16_t *__restrict__ vb = a.bricks;
+  IsoCorners v;
+  // The brick index is separable (packed_volume.hpp): brick number = bx + by + bz, in-brick offset = ix | iy | iz, with per-axis terms.
+  // Six terms per axis pair and one add + one or per corner serve every cell alike -- clamped, straddling or inside one sub-brick --
+  // so the wave never diverges here (measured against a lean path for cells inside one 4^3 sub-brick plus eight record_index calls
+  // for the rest: the wave nearly always held lanes of both kinds and paid for both).
+  const unsigned x0 = (unsigned)max(c.ix, 0), x1 = (unsigned)min(c.ix + 1, a.X - 1), y0 = (unsigned)max(c.iy, 0), y1 = (unsigned)min(c.iy + 1, a.Y - 1);
+  const unsigned z0 = (unsigned)max(c.iz, 0), z1 = (unsigned)min(c.iz + 1, a.Z - 1);
+  const unsigned nbx = (unsigned)a.NBX, nbxy = (unsigned)a.NBX * (unsigned)a.NBY;
+  const unsigned bx0 = x0 >> 3, bx1 = x1 >> 3, by0 = (y0 >> 3) * nbx, by1 = (y1 >> 3) * nbx, bz0 = (z0 >> 3) * nbxy, bz1 = (z1 >> 3) * nbxy;
+  const unsigned ix0 = VolumePacked::inner_index(x0, 0u, 0u), ix1 = VolumePacked::inner_index(x1, 0u, 0u);
+  const unsigned iy0 = VolumePacked::inner_index(0u, y0, 0u), iy1 = VolumePacked::inner_index(0u, y1, 0u);
+  const unsigned iz0 = VolumePacked::inner_index(0u, 0u, z0), iz1 = VolumePacked::inner_index(0u, 0u, z1);
+  const unsigned b00 = by0 + bz0, b10 = by1 + bz0, b01 = by0 + bz1, b11 = by1 + bz1;
+  const unsigned i00 = iy0 | iz0, i10 = iy1 | iz0, i01 = iy0 | iz1, i11 = iy1 | iz1;
+  v.v000 = vb[((size_t)(bx0 + b00) << 9) + (ix0 | i00)]; v.v100 = vb[((size_t)(bx1 + b00) << 9) + (ix1 | i00)];
+  v.v010 = vb[((size_t)(bx0 + b10) << 9) + (ix0 | i10)]; v.v110 = vb[((size_t)(bx1 + b10) << 9) + (ix1 | i10)];
+  v.v001 = vb[((size_t)(bx0 + b01) << 9) + (ix0 | i01)]; v.v101 = vb[((size_t)(bx1 + b01) << 9) + (ix1 | i01)];
+  v.v011 = vb[((size_t)(bx0 + b11) << 9) + (ix0 | i11)]; v.v111 = vb[((size_t)(bx1 + b11) << 9) + (ix1 | i11)];
+  return v;
+}
+// S from the corners and the weights
+__device__ __forceinline__ long long iso_blend(const IsoCorners &v, const IsoCell &c) {
+  const int ux = 256 - c.wx, uy = 256 - c.wy;
+  const int a00 = v.v000 * ux + v.v100 * c.wx, a10 = v.v010 * ux + v.v110 * c.wx;  // |.| <= 2^23
+  const int a01 = v.v001 * ux + v.v101 * c.wx, a11 = v.v011 * ux + v.v111 * c.wx;
+  const int b0 = a00 * uy + a10 * c.wy, b1 = a01 * uy + a11 * c.wy;                // |.| <= 2^31, reached only as -2^31
+  return (long long)b0 * (long long)(256 - c.wz) + (long long)b1 * (long long)c.wz;
+}
+// S(p) for a position inside the volume
+__device__ __forceinline__ long long iso_field(const IsoArgs &a, const f3 p) {
+  const IsoCell c = iso_cell(p);
+  return iso_blend(iso_corners(a, c), c);
+}
+
+template <bool BELOW>
+__device__ __forceinline__ bool iso_inside(long long S, long long T) { return BELOW ? S <= T : S >= T; }
+
+// G at p: the corners' clamped central differences under the corners' weights (once per hit lane)
+__device__ __forceinline__ void iso_gradient(const int16_t *__restrict__ vb, int X, int Y, int Z, int NBX, int NBY, const IsoCell c,
+                                          long long &Gx, long long &Gy, long long &Gz) {
+  Gx = Gy = Gz = 0;
+  for (int corner = 0; corner < 8; ++corner) {
+    const int ox = corner & 1, oy = (corner >> 1) & 1, oz = corner >> 2;
+    const int x = min(max(c.ix + ox, 0), X - 1), y = min(max(c.iy + oy, 0), Y - 1), z = min(max(c.iz + oz, 0), Z - 1);
+    const int w = (ox ? c.wx : 256 - c.wx) * (oy ? c.wy : 256 - c.wy) * (oz ? c.wz : 256 - c.wz);  // <= 2^24
+    const int xm = max(x - 1, 0), xp = min(x + 1, X - 1), ym = max(y - 1, 0), yp = min(y + 1, Y - 1), zm = max(z - 1, 0), zp = min(z + 1, Z - 1);
+    const int dx = (int)vb[VolumePacked::record_index(xp, y, z, NBX, NBY)] - (int)vb[VolumePacked::record_index(xm, y, z, NBX, NBY)];
+    const int dy = (int)vb[VolumePacked::record_index(x, yp, z, NBX, NBY)] - (int)vb[VolumePacked::record_index(x, ym, z, NBX, NBY)];
+    const int dz = (int)vb[VolumePacked::record_index(x, y, zp, NBX, NBY)] - (int)vb[VolumePacked::record_index(x, y, zm, NBX, NBY)];
+    Gx += (long long)w * (long long)dx;
+    Gy += (long long)w * (long long)dy;
+    Gz += (long long)w * (long long)dz;
+  }
+}
+
+__device__ __forceinline__ uint32_t iso_quantise(float x) { return (uint32_t)(int)fminf(fmaxf(x * 255.0f + 0.5f, 0.0f), 255.0f); }
+// IEEE 754 leaves a NaN's sign and payload to the implementation; the contract stores every NaN as 0x7FC00000
+__device__ __forceinline__ float iso_canonical(float x) { return x == x ? x : __builtin_nanf(""); }
+
+template <bool BELOW, bool SKIP>
+__global__ __launch_bounds__(64) void k_isosurface(const IsoArgs a) {
+  const uint32_t slot = xcd_contiguous_slot(blockIdx.x, (uint32_t)a.num_tiles);
+  const uint32_t tx = slot % (uint32_t)a.tiles_x, ty = slot / (uint32_t)a.tiles_x;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+
+  const f3 cam_o = f3{a.cam_pos[0], a.cam_pos[1], a.cam_pos[2]};
+  const f3 cam_d = f3{a.cam_dir[0], a.cam_dir[1], a.cam_dir[2]};
+  const Ray ray = generate_ray(cam_o, cam_d, (int)x, (int)y, a.frame_w, a.frame_h);
+  const ProjRay r{ray.origin, ray.direction, a.step, a.t_near, a.t_far, (float)a.X, (float)a.Y, (float)a.Z};
+  const long long T = a.threshold;
+
+  bool hit = false;
+  int k_hit = 0, k_first = 0;
+  long long S_hit = 0;
+  int k, kb;
+  if (proj_kept_range(r, a.k_cap, k, kb)) {
+    k_first = k;
+    while (k <= kb && !hit) {  // one brick per iteration, front to back
+      float t;
+      const f3 p = proj_sample(r, k, t);  // kept: 0 <= p < dim, so the conversions are floors
+      const unsigned bx = (unsigned)(int)p.x >> 3, by = (unsigned)(int)p.y >> 3, bz = (unsigned)(int)p.z >> 3;
+      if constexpr (SKIP) {  // a whole cell of 4^3 bricks that cannot hold the surface: one exit search for up to ~55 voxels of ray
+        const uint32_t cm = a.coarse[((size_t)(bz >> 2) * (size_t)a.CNY + (size_t)(by >> 2)) * (size_t)a.CNX + (size_t)(bx >> 2)];
+        if (BELOW ? (int)(int16_t)(cm & 0xFFFFu) > a.skip_bound : (int)(int16_t)(cm >> 16) < a.skip_bound) {
+          k = iso_cell_exit(r, k, kb, bx >> 2, by >> 2, bz >> 2, a.k_cap);
+          continue;
+        }
+      }
+      const int k_end = proj_brick_exit(r, k, kb, bx, by, bz, a.k_cap);
+      bool skip = false;
+      if constexpr (SKIP) {
+        const size_t brick = ((size_t)bz * (size_t)a.NBY + (size_t)by) * (size_t)a.NBX + (size_t)bx;
+        const uint32_t mm = a.dilated[brick];
+        skip = BELOW ? (int)(int16_t)(mm & 0xFFFFu) > a.skip_bound : (int)(int16_t)(mm >> 16) < a.skip_bound;
+      }
+      if (!skip) {
+        for (int j = k; j < k_end; ++j) {
+          float tj;
+          const f3 q = proj_sample(r, j, tj);
+          const long long S = iso_field(a, q);
+          if (iso_inside<BELOW>(S, T)) {
+            hit = true;
+            k_hit = j;
+            S_hit = S;
+            break;
+          }
+        }
+      }
+      k = k_end;
+    }
+  }
+
+  uint32_t px = 0u;  // a miss: (0, 0, 0, 0)
+  float t_hit = __builtin_nanf("");
+  float4 nrm = float4{t_hit, t_hit, t_hit, t_hit};
+  if (hit) {
+    float hi = (float)k_hit * r.h;
+    if (k_hit > k_first) {  // k_hit - 1 is kept and outside
+      float lo = (float)(k_hit - 1) * r.h;
+      for (int i = 0; i < a.refine; ++i) {
+        const float m = lo + (hi - lo) * 0.5f;
+        const f3 p = f3{r.o.x + r.d.x * m, r.o.y + r.d.y * m, r.o.z + r.d.z * m};  // between two kept samples: inside the volume
+        const long long S = iso_field(a, p);
+        if (iso_inside<BELOW>(S, T)) {
+          hi = m;
+          S_hit = S;
+        } else {
+          lo = m;
+        }
+      }
+    }
+    t_hit = hi;
+    const f3 p = f3{r.o.x + r.d.x * t_hit, r.o.y + r.d.y * t_hit, r.o.z + r.d.z * t_hit};
+    long long Gx, Gy, Gz;
+    iso_gradient(a.bricks, a.X, a.Y, a.Z, a.NBX, a.NBY, iso_cell(p), Gx, Gy, Gz);
+    const float gx = (float)(double)Gx, gy = (float)(double)Gy, gz = (float)(double)Gz;  // exact in binary64: one rounding
+    const float l2 = (gx * gx + gy * gy) + gz * gz;
+    float s = 1.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (l2 > 0.0f) {
+      const float len = sqrtf(l2);
+      nx = gx / len;
+      ny = gy / len;
+      nz = gz / len;
+      const float c = fabsf((gx * r.d.x + gy * r.d.y) + gz * r.d.z) / len;
+      s = a.ambient + (1.0f - a.ambient) * fminf(c, 1.0f);
+    }
+    px = iso_quantise(a.color[0] * s) | (iso_quantise(a.color[1] * s) << 8) | (iso_quantise(a.color[2] * s) << 16) | 0xFF000000u;
+    nrm = float4{iso_canonical(nx), iso_canonical(ny), iso_canonical(nz), (float)(double)S_hit * 5.9604644775390625e-08f};
+  }
+  a.frame[(size_t)y * (size_t)a.frame_w + x] = px;
+  const size_t o = (size_t)y * (size_t)a.launch_w + x;
+  if (a.t_hit) a.t_hit[o] = t_hit;
+  if (a.normal) a.normal[o] = nrm;
+}
+
+hipError_t launch_iso_dilate(const int16_t *bricks, int X, int Y, int Z, int NBX, int NBY, int NBZ, uint32_t *dilated, hipStream_t s) {
+  const size_t n_bricks = (size_t)NBX * (size_t)NBY * (size_t)NBZ;
+  hipLaunchKernelGGL(k_iso_dilate, dim3((unsigned)((n_bricks + 3u) / 4u)), dim3(256), 0, s, bricks, X, Y, Z, NBX, NBY, NBZ, dilated);
+  const size_t n_cells = (size_t)((NBX + 3) / 4) * (size_t)((NBY + 3) / 4) * (size_t)((NBZ + 3) / 4);
+  hipLaunchKernelGGL(k_iso_coarse, dim3((unsigned)((n_cells + 255u) / 256u)), dim3(256), 0, s, dilated, NBX, NBY, NBZ, dilated + n_bricks);
+  return hipGetLastError();
+}
+
+hipError_t launch_isosurface(const IsoArgs &a, bool below, bool dense, hipStream_t s) {
+  const dim3 grid((unsigned)a.num_tiles), block(64);
+  if (below && dense)
+    hipLaunchKernelGGL((k_isosurface<true, false>), grid, block, 0, s, a);
+  else if (below)
+    hipLaunchKernelGGL((k_isosurface<true, true>), grid, block, 0, s, a);
+  else if (dense)
+    hipLaunchKernelGGL((k_isosurface<false, false>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_isosurface<false, true>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace clvr

@@ -21,6 +21,7 @@ DERIVED_SCENE, DERIVED_CAMERA, DERIVED_PROJECTION = 1, 2, 4
 PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2
 PROJ_DENSE = 1
 COMP_DENSE, COMP_SHADE = 1, 2
+ISO_DENSE, ISO_BELOW = 1, 2
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -103,6 +104,19 @@ class CompositeDesc(C.Structure):
     ]
 
 
+class IsosurfaceDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("volume", C.c_void_p),
+        ("cam_pos", C.c_float * 3), ("cam_dir", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("flags", C.c_int32),
+        ("step", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float),
+        ("iso", C.c_float), ("refine", C.c_int32),
+        ("color", C.c_float * 3), ("ambient", C.c_float),
+        ("t_hit", C.c_void_p), ("normal", C.c_void_p),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -139,6 +153,7 @@ _PROTOTYPES = [
     ("clwh_ctx_scene_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     ("clwh_render_projection", C.c_int, [C.c_void_p, C.POINTER(ProjectionDesc)]),
     ("clwh_render_composite", C.c_int, [C.c_void_p, C.POINTER(CompositeDesc)]),
+    ("clwh_render_isosurface", C.c_int, [C.c_void_p, C.POINTER(IsosurfaceDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -417,6 +432,25 @@ class Context:
         d.t_first = t_first.h if t_first is not None else None
         d.t_stop = t_stop.h if t_stop is not None else None
         _check(lib().clwh_render_composite(self.h, C.byref(d)), "clwh_render_composite")
+
+    def render_isosurface(self, frame: Mem, volume: Mem, cam_pos, cam_dir, width, height, iso, step=0.5, refine=8, flags=0,
+                          color=(1.0, 1.0, 1.0), ambient=0.3, t_near=0.0, t_far=float("inf"), t_hit: Mem = None, normal: Mem = None):
+        """the isosurface of the trilinear field of `volume` (S16) at value `iso` into `frame` (RGBA8), shaded by a two-sided
+        headlight, with clwh_render's camera rays.  flags: ISO_DENSE | ISO_BELOW.  t_hit (float32[height][width]) / normal
+        (float32[height][width][4] = n, value at the hit): optional buffers over the launched region."""
+        d = IsosurfaceDesc()
+        d.frame, d.volume = frame.h, volume.h
+        for k in range(3):
+            d.cam_pos[k] = float(cam_pos[k])
+            d.cam_dir[k] = float(cam_dir[k])
+            d.color[k] = float(color[k])
+        d.width, d.height = int(width), int(height)
+        d.flags = int(flags)
+        d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
+        d.iso, d.refine, d.ambient = float(iso), int(refine), float(ambient)
+        d.t_hit = t_hit.h if t_hit is not None else None
+        d.normal = normal.h if normal is not None else None
+        _check(lib().clwh_render_isosurface(self.h, C.byref(d)), "clwh_render_isosurface")
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -212,7 +212,8 @@ int clwh_frame_from_tiles(clwh_ctx *ctx, clwh_mem *tiles_all_ranks, int32_t tile
  *   CLWH_DERIVED_CAMERA  primary hits (function of the camera and of the scene), per context
  *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table that clwh_render_projection and
  *                        clwh_render_composite share, per context (ONE copy: 2 bytes per voxel + 4 per 8^3 brick), and with it the
- *                        prefix count over clwh_render_composite's colour/opacity table (4 bytes per entry): both are dropped */
+ *                        prefix count over clwh_render_composite's colour/opacity table (4 bytes per entry) and the dilated
+ *                        {min, max} tables of clwh_render_isosurface (4 bytes per brick and per 4^3 bricks): all are dropped */
 enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2, CLWH_DERIVED_PROJECTION = 4 };
 int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what);
 /* which copy of the derived scene data the context renders from (after its last clwh_render): a process-wide unique id
@@ -309,6 +310,69 @@ typedef struct clwh_composite_desc {
   clwh_mem *t_stop;           /* optional float32[height][width] */
 } clwh_composite_desc;
 int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *desc);
+
+/* ---- isosurface rendering: the first position along each camera ray where the TRILINEAR field of the volume reaches a value, shaded
+ * by a two-sided headlight from the interpolated gradient, together with its depth and normal (not in the reference).  Camera rays,
+ * step, t_near, t_far, the launched region and the meaning of KEPT sample are those of clwh_render_projection, word for word: sample
+ * k >= 0 sits at t_k = (float)k * step, p_k = o + d * t_k (per component one float multiply, then one float add), kept iff
+ * t_near <= t_k <= t_far and 0 <= p_k.c < dim_c on all three axes.
+ * The field, in fixed point (so that the result does not depend on the order of evaluation and is exact without any float rule): for a
+ * position p with 0 <= p.c < dim_c, per axis c
+ *   q = p.c - 0.5f (voxel centres sit at integer + 0.5), f = floorf(q), i0 = (int)f, w = min((int)((q - f) * 256.0f), 255)
+ * (float32, in this order; w is in [0, 255]); the axis' two corner coordinates are i0 and i0 + 1, each clamped to [0, dim_c - 1], with
+ * the weights 256 - w and w.  S(p) = sum over the 8 corners of wx * wy * wz * V(corner), an exact integer: the interpolated value
+ * times 2^24, |S| <= 2^39.  The threshold is T = (int64)floor((double)iso * 16777216.0) (exact).  A position is INSIDE iff S(p) >= T,
+ * with CLWH_ISO_BELOW iff S(p) <= T.  No float comparison takes part in a hit decision.
+ * Per pixel:
+ *   1. k_hit = the smallest kept k with p_k inside.  None: the pixel is a MISS.
+ *   2. Refinement, only if k_hit is not the ray's first kept sample (then k_hit - 1 is kept and outside): lo = t_{k_hit-1},
+ *      hi = t_{k_hit}; `refine` times: m = lo + (hi - lo) * 0.5f, p = o + d * m; if p is inside then hi = m, else lo = m.  Float
+ *      multiply and add are monotone, so lo <= m <= hi and every coordinate of p(m) lies between those of the two kept samples p_{k_hit-1}
+ *      and p_{k_hit}: p(m) is inside the volume and S(p(m)) is defined.  t_hit = hi (= t_{k_hit} without refinement), p_hit = o + d * t_hit.
+ *   3. Normal at p_hit, with p_hit's 8 (clamped) corners and weights: G_c = sum over the corners of wx * wy * wz * (V(corner + e_c) -
+ *      V(corner - e_c)), each neighbour coordinate clamped to [0, dim_c - 1] again; an exact integer, |G_c| < 2^41.  g_c = (float)G_c
+ *      with ONE rounding to nearest-even (every G_c is exact in binary64: (float)(double)G_c).  l2 = (gx*gx + gy*gy) + gz*gz.  If l2 > 0:
+ *      n_c = g_c / sqrtf(l2), c = fabsf((gx*d.x + gy*d.y) + gz*d.z) / sqrtf(l2), s = ambient + (1.0f - ambient) * fminf(c, 1.0f)
+ *      (float32, without contraction, sqrtf and / correctly rounded: the compositor's words); otherwise n = (0, 0, 0) and s = 1.0f.
+ * Outputs: frame pixel (q(color[0]*s), q(color[1]*s), q(color[2]*s), 255) with clwh_render_composite's q; a miss is (0, 0, 0, 0);
+ * pixels of the frame outside the region are not touched.  Optional t_hit (float32[height][width]; NaN for a miss) and normal
+ * (float32[height][width][4] = n.x, n.y, n.z, (float)S(p_hit) * 2^-24, the (float) again one rounding of an integer that is exact in
+ * binary64; every NaN is stored as 0x7FC00000, and a miss is four of them), row-major over the launched region.
+ * CLWH_ISO_DENSE tests every kept sample up to the hit.  Without it the kernel steps over an 8^3 brick unread when the {min, max} of
+ * the brick DILATED BY ONE VOXEL (clamped at the volume's faces) proves that no sample in it is inside: dmax * 2^24 < T, with
+ * CLWH_ISO_BELOW dmin * 2^24 > T.  Proof: a sample whose voxel floor(p) = v lies in the brick has i0 in {v - 1, v} on every axis, so all
+ * its clamped corners lie within one voxel of the brick, inside the dilated box; S is a combination of their values with non-negative
+ * integer weights that sum to 2^24, so dmin * 2^24 <= S <= dmax * 2^24.  (A second table holds the same pair per cell of 4^3
+ * bricks, the minimum and maximum over the cell's bricks; it bounds every brick of the cell and lets the walk leave a whole cell at
+ * once.)  Same bytes as the dense walk, by the contract.
+ * Errors: a NULL or wrong-kind handle, unknown flag bits, iso not finite or |iso| > 65536, refine outside [0, 24], ambient outside
+ * [0, 1] or NaN, a colour component that is not finite, a camera position that is not finite, and every step / slab / camera-distance /
+ * volume-dims condition of clwh_render_projection: CLWH_ERR_INVALID_VALUE (a zero-initialised descriptor is rejected: step == 0).  The
+ * region conditions of the projections: CLWH_ERR_BAD_NDRANGE.  t_hit smaller than 4 * width * height bytes or normal smaller than
+ * 16 * width * height: CLWH_ERR_SIZE_MISMATCH.
+ * Asynchronous and ordered on the context's stream; no host wait.  The derived data (CLWH_DERIVED_PROJECTION) is the projections'
+ * bricked copy of the volume, shared with them, plus the dilated {min, max} tables (4 bytes per brick and per cell of 4^3 bricks),
+ * built by the first isosurface call of a volume content and keyed like the copy: projections and composites never build them. */
+enum clwh_isosurface_flags {
+  CLWH_ISO_DENSE = 1,  /* no brick skipping: same result by contract; for tests and timing */
+  CLWH_ISO_BELOW = 2   /* inside iff S <= T */
+};
+typedef struct clwh_isosurface_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image; its dims are generate_ray's totals (as clwh_render_desc.frame) */
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  float cam_pos[3], cam_dir[3];
+  uint32_t width, height;     /* launched region: multiples of 8, <= frame dims, <= 65535 */
+  int32_t flags;
+  float step;                 /* h > 0, finite */
+  float t_near, t_far;        /* slab along the ray; 0 and +INFINITY = whole volume */
+  float iso;                  /* finite, |iso| <= 65536 */
+  int32_t refine;             /* bisection steps between the last outside and the first inside sample, 0..24 */
+  float color[3];             /* finite */
+  float ambient;              /* [0, 1] */
+  clwh_mem *t_hit;            /* optional float32[height][width] */
+  clwh_mem *normal;           /* optional float32[height][width][4] */
+} clwh_isosurface_desc;
+int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc *desc);
 
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
