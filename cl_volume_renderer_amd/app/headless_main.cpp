@@ -1,12 +1,15 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
 // ambient 0.3 when shaded).
 // --isosurface=VALUE[,below]: the frames show the isosurface of the trilinear field at VALUE (renderer::render_isosurface: step 0.5,
 // 8 refinement steps, white, ambient 0.3; ",below": the first position at or below VALUE).
+// --slice=ORIENTATION[,POSITION][,slab=N][,max|min|mean]: the frames show the axial, coronal or sagittal plane of the trilinear field
+// at POSITION (voxel centres along the plane's normal; default: the middle of the volume), or the maximum / minimum / mean of a slab
+// of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -30,6 +33,11 @@ int main(int argc_in, char const *argv_in[]) {
   int composite = -1;   // 0: plain, 1: shaded, or -1
   bool isosurface = false, iso_below = false;
   float iso_value = 0.0f;
+  int slice = -1;  // renderer::slice_orientation, or -1
+  int slice_mode = CLWH_SLICE_MAX, slice_slab = 1;
+  bool slice_centred = true;
+  float slice_position = 0.0f;
+  static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
     const std::string a = argv_in[i];
@@ -68,9 +76,44 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--isosurface", 0) == 0) {
       std::cout << "Unknown option '" << a << "' (--isosurface=VALUE or --isosurface=VALUE,below)\n";
       return 1;
+    } else if (a.rfind("--slice=", 0) == 0) {
+      std::string rest = a.substr(8);
+      bool ok = true;
+      for (int field = 0; ok && (field == 0 || !rest.empty()); ++field) {
+        const size_t comma = rest.find(',');
+        const std::string v = rest.substr(0, comma);
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+        if (comma != std::string::npos && rest.empty()) ok = false;  // a trailing comma
+        char *end = nullptr;
+        if (field == 0) {
+          slice = v == "axial" ? renderer::SLICE_AXIAL : v == "coronal" ? renderer::SLICE_CORONAL : v == "sagittal" ? renderer::SLICE_SAGITTAL : -1;
+          ok = ok && slice >= 0;
+        } else if (v == "max" || v == "min" || v == "mean") {
+          slice_mode = v == "max" ? CLWH_SLICE_MAX : v == "min" ? CLWH_SLICE_MIN : CLWH_SLICE_MEAN;
+        } else if (v.rfind("slab=", 0) == 0) {
+          const long n = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && n >= 1 && n <= 8192;
+          slice_slab = (int)n;
+        } else {
+          slice_position = std::strtof(v.c_str(), &end);
+          ok = ok && !v.empty() && *end == '\0' && std::isfinite(slice_position);
+          slice_centred = false;
+        }
+      }
+      if (!ok) {
+        std::cout << "Unknown option '" << a << "' " << kSliceUsage << "\n";
+        return 1;
+      }
+    } else if (a.rfind("--slice", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' " << kSliceUsage << "\n";
+      return 1;
     } else {
       args.push_back(argv_in[i]);
     }
+  }
+  if (slice >= 0 && (projection >= 0 || composite >= 0 || isosurface)) {
+    std::cout << "--slice excludes --projection, --composite and --isosurface\n";
+    return 1;
   }
   if (projection >= 0 && composite >= 0) {
     std::cout << "--projection and --composite exclude each other\n";
@@ -83,7 +126,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -115,6 +158,10 @@ int main(int argc_in, char const *argv_in[]) {
   const double scale = rv.get_volume_size()[0] / 512.0;  // the default camera is placed for a 512^3 volume
   state.position = Position3D(-200 * scale, 200 * scale, -200 * scale);
   const unsigned char *frame = nullptr;
+  if (slice >= 0 && slice_centred) {  // the middle of the volume along the plane's normal
+    static const int kNormalAxis[3] = {2, 1, 0};
+    slice_position = (float)(((double)rv.get_volume_size()[kNormalAxis[slice]] - 1.0) / 2.0);
+  }
   // renderer::render_frame seeds every pass from std::rand() and the application never calls srand
   // (app/renderer.cpp:142).  The ROCm runtime draws from rand() while it initialises, so the sequence is put
   // back to the never-seeded state here to make the frames reproducible (1804289383, 846930886, ...).
@@ -123,7 +170,9 @@ int main(int argc_in, char const *argv_in[]) {
   for (int f = 0; f < frames; ++f) {
     bool changed = false;
     state.cam_changed = true;  // progressive refinement: keep sampling the same view
-    if (isosurface)
+    if (slice >= 0)
+      frame = static_cast<const unsigned char *>(r.render_slice(state, slice, slice_position, slice_mode, slice_slab, 0.5f, 0.0f, 4000.0f));
+    else if (isosurface)
       frame = static_cast<const unsigned char *>(r.render_isosurface(state, iso_value, iso_below ? CLWH_ISO_BELOW : 0));
     else if (composite >= 0)
       frame = static_cast<const unsigned char *>(
@@ -148,11 +197,14 @@ int main(int argc_in, char const *argv_in[]) {
       for (int x = 0; x < width; ++x) ppm.write(reinterpret_cast<const char *>(frame + ((size_t)y * SCREEN_WIDTH + x) * 4), 3);
   }
   static const char *const kProjectionNames[] = {"max", "min", "mean"};
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s}\n",
+  static const char *const kSliceNames[] = {"axial", "coronal", "sagittal"};
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s%s}\n",
               frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
               projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "",
               composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "",
-              isosurface ? (", \"isosurface\": " + std::to_string(iso_value) + ", \"below\": " + (iso_below ? "true" : "false")).c_str() : "");
+              isosurface ? (", \"isosurface\": " + std::to_string(iso_value) + ", \"below\": " + (iso_below ? "true" : "false")).c_str() : "",
+              slice >= 0 ? (std::string(", \"slice\": \"") + kSliceNames[slice] + "\", \"position\": " + std::to_string(slice_position) +
+                            ", \"slab\": " + std::to_string(slice_slab) + ", \"mode\": \"" + kProjectionNames[slice_mode] + "\"").c_str() : "");
   for (tf_selection *s : selection) delete s;
   return 0;
 }

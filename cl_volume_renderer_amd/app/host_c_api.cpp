@@ -111,6 +111,14 @@ const void *clvr_host_render_isosurface(clvr_host *h, const float pos[3], const 
   h->state.height = height;
   return h->rend.render_isosurface(h->state, iso, flags, step, refine, ambient, color[0], color[1], color[2]);
 }
+// renderer::render_slice for a region of width x height pixels (no camera): orientation 0 axial, 1 coronal, 2 sagittal; the RGBA8
+// frame (SCREEN_WIDTH x SCREEN_HEIGHT)
+const void *clvr_host_render_slice(clvr_host *h, int width, int height, int orientation, float position, int mode, int slab_samples,
+                                   float step, float center, float window_width, int flags) {
+  h->state.width = width;
+  h->state.height = height;
+  return h->rend.render_slice(h->state, orientation, position, mode, slab_samples, step, center, window_width, flags);
+}
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

@@ -177,6 +177,46 @@ void *renderer::render_isosurface(struct ui_state &state, float iso, int flags, 
   return &frame[0];
 }
 
+void renderer::slice_plane(const size_t dims[3], int orientation, float position, int width, int height, int slab_samples, float step,
+                           float origin[3], float du[3], float dv[3], float normal[3]) {
+  static const int axes[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};  // (axis of du, axis of dv, axis of the normal)
+  const int iu = axes[orientation][0], iv = axes[orientation][1], iw = axes[orientation][2];
+  const double a = (double)dims[iu], b = (double)dims[iv];
+  const double s = std::max(a / (double)width, b / (double)height);
+  double o[3] = {0.0, 0.0, 0.0};
+  o[iu] = a / 2.0 + (0.5 - (double)width / 2.0) * s;
+  o[iv] = b / 2.0 + (0.5 - (double)height / 2.0) * s;
+  o[iw] = (double)position + 0.5 - (double)(slab_samples - 1) * (double)step / 2.0;
+  for (int q = 0; q < 3; ++q) {
+    origin[q] = (float)o[q];
+    du[q] = dv[q] = normal[q] = 0.0f;
+  }
+  du[iu] = dv[iv] = (float)s;
+  normal[iw] = 1.0f;
+}
+
+void *renderer::render_slice(struct ui_state &state, int orientation, float position, int mode, int slab_samples, float step, float center,
+                             float width, int flags) {
+  if (orientation < SLICE_AXIAL || orientation > SLICE_SAGITTAL || state.width < 1 || state.height < 1) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  clwh_slice_desc d{};
+  d.frame = frame.get_device_reference();
+  d.volume = volume->get_reference_volume().get_device_reference();
+  const auto &size = volume->get_volume_size();
+  const size_t dims[3] = {size[0], size[1], size[2]};
+  slice_plane(dims, orientation, position, state.width, state.height, slab_samples, step, d.origin, d.du, d.dv, d.normal);
+  d.width = (uint32_t)state.width;
+  d.height = (uint32_t)state.height;
+  d.mode = mode;
+  d.flags = flags;
+  d.slab_samples = slab_samples;
+  d.step = step;
+  d.window_center = center;
+  d.window_width = width;
+  clw_fail_hard_on_error(clwh_render_slice(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
 // reference :45-124 -- the 2-D (value, |gradient|) histogram texture of the transfer-function editor:
 // bin the volume, quantise the counts on the host so that small counts stay distinguishable, rank the
 // distinct counts, colour each bin by its rank.  (The reference declares render_tf(width, height) and

@@ -51,6 +51,20 @@ class renderer : public frame_emitter {
   void *render_isosurface(struct ui_state &state, float iso, int flags = 0, float step = 0.5f, int refine = 8, float ambient = 0.3f,
                           float red = 1.0f, float green = 1.0f, float blue = 1.0f);
 
+  // not in the reference: a slice of the volume's trilinear field on the axial, coronal or sagittal plane at `position` (voxel centres
+  // along the plane's normal), or the maximum / minimum / mean (mode = CLWH_SLICE_MAX / MIN / MEAN) of a slab of `slab_samples` planes
+  // `step` voxels apart centred on it: multi-planar reformatting.  The plane is slice_plane's for the launched region (state.width x
+  // state.height); `center` / `width` window the value to grey.  flags: CLWH_SLICE_DENSE.  Pulls the frame (a pixel outside the volume
+  // is 0, 0, 0, 0) and returns its host copy.
+  enum slice_orientation { SLICE_AXIAL = 0, SLICE_CORONAL = 1, SLICE_SAGITTAL = 2 };
+  void *render_slice(struct ui_state &state, int orientation, float position, int mode = 0, int slab_samples = 1, float step = 0.5f,
+                     float center = 0.0f, float width = 4000.0f, int flags = 0);
+  // the plane of a volume of `dims` voxels for a region of width x height pixels: normal +z with x right and y up (axial), normal +y
+  // with x and z (coronal), normal +x with y and z (sagittal); one pixel spacing for both axes, the smallest at which the volume's
+  // cross-section fits the region, centred in it; the slab centred on `position`.  Computed in double, rounded once.
+  static void slice_plane(const size_t dims[3], int orientation, float position, int width, int height, int slab_samples, float step,
+                          float origin[3], float du[3], float dv[3], float normal[3]);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }

@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing and isosurfaces).
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing, isosurfaces and slices).
 // No kernel needs this header.
 #pragma once
 
@@ -139,6 +139,7 @@ struct Tuning {
   int32_t sdfbit_grid = 512;   // CLWH_TUNE_SDFBIT_GRID: its persistent grid
   int32_t sdfbit_rec_lds = 0;  // CLWH_TUNE_SDFBIT_REC=lds: the layer records in LDS, three blocks of eight waves per CU (grid x 3 / 2)
   int32_t sdf_front = 0;       // CLWH_TUNE_SDF=front: the byte-front build (one launch per layer) instead of the bit-parallel one
+  int32_t slice_coarse = 1;    // CLWH_TUNE_SLICE_COARSE=0: k_slice's skipping walk asks the bricks' table only, not the cells of 4^3 bricks
 };
 Tuning tuning_from_environment();
 
@@ -214,8 +215,9 @@ struct ProjectionData {
   const void *vol = nullptr;
   uint64_t vol_ver = 0;
   size_t dims[3] = {0, 0, 0};
-  // clwh_render_isosurface only: the {min, max} table of the bricks dilated by one voxel (and of the cells of 4^3 bricks behind it),
-  // built from `data` by the first isosurface call after `data` was (re)built -- valid only while `valid` is and for the same key
+  // clwh_render_isosurface and clwh_render_slice (MAX / MIN without CLWH_SLICE_DENSE) only: the {min, max} table of the bricks dilated
+  // by one voxel (and of the cells of 4^3 bricks behind it), built from `data` by the first such call after `data` was (re)built --
+  // valid only while `valid` is and for the same key
   DeviceBuffer dilated;
   bool dilated_valid = false;  // cleared whenever `data` is rebuilt and by clwh_ctx_invalidate_derived (projection)
   DeviceBuffer lut_prefix;

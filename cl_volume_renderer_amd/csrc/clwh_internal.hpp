@@ -303,4 +303,25 @@ struct IsoArgs {
 hipError_t launch_iso_dilate(const int16_t *bricks, int X, int Y, int Z, int NBX, int NBY, int NBZ, uint32_t *dilated, hipStream_t s);
 hipError_t launch_isosurface(const IsoArgs &a, bool below, bool dense, hipStream_t s);
 
+// ---- oblique slices and thick slabs of the trilinear field (slice_kernels.hip): parallel rays with one origin per pixel over the
+// projections' bricked copy; MAX / MIN may step over bricks (and cells of 4^3 bricks) by the isosurface's dilated {min, max} tables
+struct SliceArgs {
+  const int16_t *bricks;
+  const uint32_t *table;   // the projections' {min, max} table (not read by k_slice)
+  const uint32_t *dilated; // as IsoArgs::dilated; nullptr when the launch cannot skip (MEAN, CLWH_SLICE_DENSE)
+  const uint32_t *coarse;  // as IsoArgs::coarse
+  int32_t X, Y, Z, NBX, NBY, CNX, CNY;
+  int32_t use_coarse;      // 1: ask the cell of 4^3 bricks first (Tuning::slice_coarse)
+  uint32_t *frame;         // RGBA8 packed, row-major, frame_w x frame_h
+  int32_t frame_w, frame_h;
+  int32_t launch_w, launch_h, tiles_x, num_tiles;
+  float origin[3], du[3], dv[3], normal[3];
+  float step;
+  float window_center, window_width;
+  int32_t slab_samples;    // 1 .. 8192: the sample indices' cap
+  float *values;           // optional, row-major launch_w x launch_h
+  float *t_extreme;        // optional, same
+};
+hipError_t launch_slice(const SliceArgs &a, int mode, bool dense, hipStream_t s);
+
 }  // namespace clvr

@@ -1,7 +1,7 @@
-// clwh_projection.hip -- clwh_render_projection, clwh_render_composite and clwh_render_isosurface on the host: intensity projections
-// of the volume, compositing through a colour/opacity table and the isosurface of the trilinear field.  All march the same bricked
-// copy of the volume (ensure_projection_data).  The kernels are in projection_kernels.hip, composite_kernels.hip and
-// isosurface_kernels.hip.
+// clwh_projection.hip -- clwh_render_projection, clwh_render_composite, clwh_render_isosurface and clwh_render_slice on the host:
+// intensity projections of the volume, compositing through a colour/opacity table, the isosurface of the trilinear field and its
+// oblique slices and slabs.  All march the same bricked copy of the volume (ensure_projection_data).  The kernels are in
+// projection_kernels.hip, composite_kernels.hip, isosurface_kernels.hip and slice_kernels.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -177,8 +177,9 @@ extern "C" int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *d
 
 // the {min, max} table of the bricks dilated by one voxel and, behind it, of the cells of 4^3 bricks, built from the bricked copy
 // (which ensure_projection_data has just made current: a rebuild of the copy has cleared dilated_valid) by the first isosurface
-// call of a volume content
-static int ensure_dilated_table(clwh_ctx *ctx, IsoArgs &a) {
+// call of a volume content, or the first slice call that may skip
+template <class Args>
+static int ensure_dilated_table(clwh_ctx *ctx, Args &a) {
   ProjectionData &p = ctx->proj;
   if (!p.dilated_valid) {
     const int NBZ = (a.Z + 7) / 8;
@@ -244,5 +245,58 @@ extern "C" int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc 
   a.t_hit = d->t_hit ? (float *)d->t_hit->dptr : nullptr;
   a.normal = d->normal ? (float4 *)d->normal->dptr : nullptr;
   HIP_TRY(launch_isosurface(a, below, dense, ctx->stream));
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *d) {
+  if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
+  if (!is_image(d->frame, 2, 4, CLWH_ELEM_U8) || !is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;
+  if (d->mode != CLWH_SLICE_MAX && d->mode != CLWH_SLICE_MIN && d->mode != CLWH_SLICE_MEAN) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_SLICE_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->slab_samples < 1 || d->slab_samples > 8192) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  for (int q = 0; q < 3; ++q) {
+    if (!(std::isfinite(d->origin[q]) && std::isfinite(d->du[q]) && std::isfinite(d->dv[q]) && std::isfinite(d->normal[q]))) return CLWH_ERR_INVALID_VALUE;
+    // how far any sample of the region can lie from 0 on this axis: below 2^30 every coordinate is finite and converts to int32
+    const double reach = std::fabs((double)d->origin[q]) + (d->width ? (double)d->width - 1.0 : 0.0) * std::fabs((double)d->du[q]) +
+                         (d->height ? (double)d->height - 1.0 : 0.0) * std::fabs((double)d->dv[q]) +
+                         (double)(d->slab_samples - 1) * (double)d->step * std::fabs((double)d->normal[q]);
+    if (!(reach < 1073741824.0)) return CLWH_ERR_INVALID_VALUE;
+  }
+  if (!dims_fit_int32(d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if (!launch_size_ok(d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > 65535u || d->height > 65535u) return CLWH_ERR_BAD_NDRANGE;
+  if (d->width > d->frame->dims[0] || d->height > d->frame->dims[1]) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if ((d->values && d->values->bytes < out_bytes) || (d->t_extreme && d->t_extreme->bytes < out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  SliceArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a));
+  const bool dense = (d->flags & CLWH_SLICE_DENSE) != 0 || d->mode == CLWH_SLICE_MEAN;  // MEAN reads every kept sample
+  if (!dense) CLWH_TRY(ensure_dilated_table(ctx, a));
+  a.use_coarse = ctx->tune.slice_coarse;
+  a.frame = (uint32_t *)d->frame->dptr;
+  a.frame_w = (int32_t)d->frame->dims[0];
+  a.frame_h = (int32_t)d->frame->dims[1];
+  a.launch_w = (int32_t)d->width;
+  a.launch_h = (int32_t)d->height;
+  a.tiles_x = a.launch_w / 8;
+  a.num_tiles = a.tiles_x * (a.launch_h / 8);
+  for (int q = 0; q < 3; ++q) {
+    a.origin[q] = d->origin[q];
+    a.du[q] = d->du[q];
+    a.dv[q] = d->dv[q];
+    a.normal[q] = d->normal[q];
+  }
+  a.step = d->step;
+  a.window_center = d->window_center;
+  a.window_width = d->window_width;
+  a.slab_samples = d->slab_samples;
+  a.values = d->values ? (float *)d->values->dptr : nullptr;
+  a.t_extreme = d->t_extreme ? (float *)d->t_extreme->dptr : nullptr;
+  HIP_TRY(launch_slice(a, d->mode, dense, ctx->stream));
   return CLWH_OK;
 }

@@ -22,6 +22,8 @@ PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2
 PROJ_DENSE = 1
 COMP_DENSE, COMP_SHADE = 1, 2
 ISO_DENSE, ISO_BELOW = 1, 2
+SLICE_MAX, SLICE_MIN, SLICE_MEAN = 0, 1, 2
+SLICE_DENSE = 1
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -117,6 +119,18 @@ class IsosurfaceDesc(C.Structure):
     ]
 
 
+class SliceDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("volume", C.c_void_p),
+        ("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("normal", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("mode", C.c_int32), ("flags", C.c_int32),
+        ("slab_samples", C.c_int32), ("step", C.c_float),
+        ("window_center", C.c_float), ("window_width", C.c_float),
+        ("values", C.c_void_p), ("t_extreme", C.c_void_p),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -154,6 +168,7 @@ _PROTOTYPES = [
     ("clwh_render_projection", C.c_int, [C.c_void_p, C.POINTER(ProjectionDesc)]),
     ("clwh_render_composite", C.c_int, [C.c_void_p, C.POINTER(CompositeDesc)]),
     ("clwh_render_isosurface", C.c_int, [C.c_void_p, C.POINTER(IsosurfaceDesc)]),
+    ("clwh_render_slice", C.c_int, [C.c_void_p, C.POINTER(SliceDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -451,6 +466,24 @@ class Context:
         d.t_hit = t_hit.h if t_hit is not None else None
         d.normal = normal.h if normal is not None else None
         _check(lib().clwh_render_isosurface(self.h, C.byref(d)), "clwh_render_isosurface")
+
+    def render_slice(self, frame: Mem, volume: Mem, origin, du, dv, normal, width, height, mode=SLICE_MAX, slab_samples=1, step=0.5,
+                     window=(0.0, 1.0), flags=0, values: Mem = None, t_extreme: Mem = None):
+        """a slice of the trilinear field of `volume` (S16) on the plane origin + x * du + y * dv (voxel space) into `frame` (RGBA8),
+        or the maximum / minimum / mean over `slab_samples` planes `step` apart along `normal` (mode: SLICE_MAX / MIN / MEAN;
+        scene.slice_plane makes axial, coronal and sagittal planes).  window = (center, width) maps the value to grey.  flags:
+        SLICE_DENSE.  values / t_extreme: optional float32[height][width] buffers."""
+        d = SliceDesc()
+        d.frame, d.volume = frame.h, volume.h
+        for k in range(3):
+            d.origin[k], d.du[k], d.dv[k], d.normal[k] = float(origin[k]), float(du[k]), float(dv[k]), float(normal[k])
+        d.width, d.height = int(width), int(height)
+        d.mode, d.flags = int(mode), int(flags)
+        d.slab_samples, d.step = int(slab_samples), float(step)
+        d.window_center, d.window_width = float(window[0]), float(window[1])
+        d.values = values.h if values is not None else None
+        d.t_extreme = t_extreme.h if t_extreme is not None else None
+        _check(lib().clwh_render_slice(self.h, C.byref(d)), "clwh_render_slice")
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -213,7 +213,8 @@ int clwh_frame_from_tiles(clwh_ctx *ctx, clwh_mem *tiles_all_ranks, int32_t tile
  *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table that clwh_render_projection and
  *                        clwh_render_composite share, per context (ONE copy: 2 bytes per voxel + 4 per 8^3 brick), and with it the
  *                        prefix count over clwh_render_composite's colour/opacity table (4 bytes per entry) and the dilated
- *                        {min, max} tables of clwh_render_isosurface (4 bytes per brick and per 4^3 bricks): all are dropped */
+ *                        {min, max} tables that clwh_render_isosurface and clwh_render_slice share (4 bytes per brick and per
+ *                        4^3 bricks): all are dropped */
 enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2, CLWH_DERIVED_PROJECTION = 4 };
 int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what);
 /* which copy of the derived scene data the context renders from (after its last clwh_render): a process-wide unique id
@@ -352,7 +353,8 @@ int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *desc);
  * 16 * width * height: CLWH_ERR_SIZE_MISMATCH.
  * Asynchronous and ordered on the context's stream; no host wait.  The derived data (CLWH_DERIVED_PROJECTION) is the projections'
  * bricked copy of the volume, shared with them, plus the dilated {min, max} tables (4 bytes per brick and per cell of 4^3 bricks),
- * built by the first isosurface call of a volume content and keyed like the copy: projections and composites never build them. */
+ * built by the first isosurface call of a volume content -- or by the first clwh_render_slice call that may skip, whichever comes
+ * first -- and keyed like the copy: projections and composites never build them. */
 enum clwh_isosurface_flags {
   CLWH_ISO_DENSE = 1,  /* no brick skipping: same result by contract; for tests and timing */
   CLWH_ISO_BELOW = 2   /* inside iff S <= T */
@@ -373,6 +375,69 @@ typedef struct clwh_isosurface_desc {
   clwh_mem *normal;           /* optional float32[height][width][4] */
 } clwh_isosurface_desc;
 int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc *desc);
+
+/* ---- oblique slices and thick slabs (multi-planar reformatting): the TRILINEAR field of the volume on a plane given in voxel
+ * space, or its maximum / minimum / mean over `slab_samples` planes stacked along `normal` (not in the reference).  No camera: every
+ * pixel owns a ray of its own, and all rays are parallel.
+ * Rays.  For pixel (x, y) of the launched region, in float32 without contraction, per component c:
+ *   o.c = (origin.c + (float)x * du.c) + (float)y * dv.c
+ * Sample k, 0 <= k < slab_samples, sits at t_k = (float)k * step, p_k = o + normal * t_k (per component one float multiply, then one
+ * float add), and is KEPT iff 0 <= p_k.c < dim_c on all three axes (NaN never; -0.0 counts as 0): the sample rule of
+ * clwh_render_projection with a per-pixel origin, t_near = 0 and no t_far.  Float multiply and add are monotone in k, so the kept
+ * samples of a ray -- and those inside any 8^3 brick -- are one contiguous range of k.
+ * Value of a sample: S(p_k), the fixed-point trilinear field of clwh_render_isosurface, word for word: per axis q = p.c - 0.5f,
+ * f = floorf(q), i0 = (int)f, w = min((int)((q - f) * 256.0f), 255); corners i0 and i0 + 1, each clamped to [0, dim_c - 1], with the
+ * weights 256 - w and w; S = sum over the 8 corners of wx * wy * wz * V(corner), an exact integer, the interpolated value times 2^24,
+ * |S| <= 2^39.
+ * Per pixel:
+ *   CLWH_SLICE_MAX   best = the largest kept S, k_ext = the smallest k that attains it.  value = (float)best * 2^-24, where (float)best
+ *                    is ONE rounding to nearest-even of an integer that is exact in binary64 ((float)(double)best) and the scaling
+ *                    by 2^-24 is exact.  t_extreme = (float)k_ext * step.
+ *   CLWH_SLICE_MIN   the same with the smallest kept S
+ *   CLWH_SLICE_MEAN  sum = the int64 sum of the kept S, count their number: value = (float)((double)sum / ((double)count *
+ *                    16777216.0)); t_extreme = NaN.  |sum| <= 8192 * 2^39 = 2^52 is exact in binary64: hence slab_samples <= 8192.
+ * A pixel without a kept sample has value = t_extreme = NaN and frame pixel (0, 0, 0, 0).  Every other pixel is windowed exactly as
+ * the projections are: u = ((value - window_center) / window_width + 0.5f) * 255.0f + 0.5f, grey = (int)fminf(fmaxf(u, 0), 255),
+ * frame pixel (grey, grey, grey, 255).  Pixels of the frame outside the region are not touched.  Optional values and t_extreme
+ * (float32[height][width], row-major over the launched region); every NaN is stored as 0x7FC00000.
+ * With slab_samples = 1 the result is the thin slice: value = (float)S(o) * 2^-24 in every mode, t_extreme = 0 (NaN for MEAN).
+ * Skipping.  CLWH_SLICE_DENSE reads every kept sample.  Without it MAX may step over an 8^3 brick unread once a `best` exists and
+ * dmax * 2^24 <= best, where dmax is the maximum of the brick DILATED BY ONE VOXEL (clamped at the volume's faces; the table of
+ * clwh_render_isosurface); MIN likewise when dmin * 2^24 >= best.  Proof: a sample whose voxel floor(p) = v lies in the brick has i0 in
+ * {v - 1, v} on every axis, so all its clamped corners lie within one voxel of the brick, inside the dilated box; S is a combination of
+ * their values with non-negative integer weights that sum to 2^24, so dmin * 2^24 <= S <= dmax * 2^24.  Every sample of a skipped brick
+ * therefore has S <= best (MAX) or S >= best (MIN); the samples are taken in increasing k, so such a sample comes after the one that
+ * set `best`, and a sample that merely equals `best` changes neither `best` nor k_ext.  The pair of a cell of 4^3 bricks (minimum and
+ * maximum over the cell's bricks) bounds every brick of the cell and may be used in the same way.  Same bytes as the dense walk, by the
+ * contract.  MEAN reads every kept sample: the flag is accepted and changes nothing.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc, a NULL or wrong-kind frame or volume; an unknown
+ * mode or unknown flag bits; slab_samples outside [1, 8192]; a step that is not finite and > 0 (a zero-initialised descriptor is
+ * rejected this way); a window that is not finite with window_width > 0; a component of origin, du, dv or normal that is not finite;
+ * on any axis c, |origin.c| + (width - 1) * |du.c| + (height - 1) * |dv.c| + (slab_samples - 1) * step * |normal.c| >= 2^30, evaluated
+ * in double (this keeps every coordinate finite and every float -> int conversion defined); volume dims beyond the projections' rule.
+ * CLWH_ERR_BAD_NDRANGE: the region rules of the projections (empty, not a multiple of 8, larger than the frame or than 65535).
+ * CLWH_ERR_SIZE_MISMATCH: values or t_extreme smaller than 4 * width * height bytes.
+ * Asynchronous and ordered on the context's stream; no host wait.  The derived data (CLWH_DERIVED_PROJECTION) is the projections'
+ * bricked copy of the volume, shared with them.  The dilated {min, max} tables are built by the first slice call that may skip (MAX or
+ * MIN without CLWH_SLICE_DENSE) or by the first isosurface call of a volume content, whichever comes first, and are keyed like the
+ * copy: a push, clwh_mem_mark_dirty or clwh_ctx_invalidate_derived rebuilds them. */
+enum clwh_slice_mode { CLWH_SLICE_MAX = 0, CLWH_SLICE_MIN = 1, CLWH_SLICE_MEAN = 2 };
+enum clwh_slice_flags { CLWH_SLICE_DENSE = 1 };  /* no brick skipping: same result by contract; for tests and timing */
+typedef struct clwh_slice_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image */
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  float origin[3];            /* voxel-space position of pixel (0, 0), sample 0 */
+  float du[3], dv[3];         /* voxel-space offset per pixel in x and in y */
+  float normal[3];            /* slab direction; need not be unit; (0, 0, 0) allowed */
+  uint32_t width, height;     /* launched region: multiples of 8, <= frame dims, <= 65535 */
+  int32_t mode, flags;
+  int32_t slab_samples;       /* 1 .. 8192; 1 = a thin slice */
+  float step;                 /* > 0, finite */
+  float window_center, window_width;  /* window_width > 0, finite */
+  clwh_mem *values;           /* optional float32[height][width] */
+  clwh_mem *t_extreme;        /* optional float32[height][width] */
+} clwh_slice_desc;
+int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *desc);
 
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
