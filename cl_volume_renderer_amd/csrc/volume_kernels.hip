@@ -401,14 +401,19 @@ __global__ __launch_bounds__(kBfB * kBfB * kBfB / 2) void k_bilateral_filter2(co
 // transfer-function editor.  The reference does one global atomic per voxel; CT data puts most voxels
 // into a handful of bins.  A persistent grid walks the volume (a lane eight voxels at a time, merging runs of equal bins)
 // and every block counts into a hash table in LDS, flushed to memory once at the end.  (The first version merged equal bins
-// across a wave and sent one global atomic per wave and distinct bin: still 94 ms at 512^3 on the few hot bins.)  Bins outside the width x height
-// frame (value == max_value rounds to column `width`; values below min_value go negative -- both write
-// out of bounds in the reference) are dropped.
+// across a wave and sent one global atomic per wave and distinct bin: still 94 ms at 512^3 on the few hot bins.)  The reference indexes
+// frame[x * height + y] unchecked (histogram.cl:31): a point off the frame's top edge (|gradient| == max_gradient rounds to y == height)
+// is counted in bin (x + 1, 0), inside the buffer; only an index outside the buffer (value == max_value rounds to column `width`;
+// values below min_value go negative -- both write out of bounds in the reference) is dropped.  Pinned by tests/test_ref_render.py.
 // 4096 slots (32 KB): four blocks per CU.  8192 slots left two (0.68 ms at 512^3 against 0.54); 2048: 0.55 ms; 1024: 0.81 ms (bins that find
 // no slot go to memory).  Also measured, without gain (profiles/r03_volume_kernels_512.txt): the first probes of a lane's eight updates in
 // flight together; both bin coordinates from exact tables instead of sqrt / divide / round (VALU 69 % -> 35 % busy, same time: the walk's
 // slice takes 9 us here against 2.3 us in k_fetch_stats_columns, and it is not issue, LDS cycles or same-bin atomics that it waits for).
 constexpr int kHistSlotsLog2 = 12, kHistSlots = 1 << kHistSlotsLog2;
+__device__ inline int hist_bin(int px, int py, int width, int height) {
+  const long long i = (long long)px * (long long)height + (long long)py;
+  return (i >= 0 && i < (long long)width * (long long)height) ? (int)i : -1;
+}
 __global__ __launch_bounds__(256) void k_tf_sort_values(const int16_t *__restrict__ vol, int X, int Y, int Z, uint32_t *frame,
                                                         int width, int height, float min_value, float max_value,
                                                         float min_gradient, float max_gradient) {
@@ -455,7 +460,7 @@ __global__ __launch_bounds__(256) void k_tf_sort_values(const int16_t *__restric
       if (!(grad_length > max_gradient) && !((float)ref_value > max_value)) {
         const int px = f2i(roundf((((float)ref_value - min_value) / value_range) * (float)width));
         const int py = f2i(roundf(((grad_length - min_gradient) / gradient_range) * (float)height));
-        if (px >= 0 && px < width && py >= 0 && py < height) bin = px * height + py;
+        bin = hist_bin(px, py, width, height);
       }
       if (bin != run_bin) {  // neighbouring voxels mostly share a bin: one table update per run
         if (run_count) add(run_bin, run_count);
@@ -514,7 +519,7 @@ __global__ __launch_bounds__(256) void k_tf_sort_values_columns(const int16_t *_
         if (!(grad_length > max_gradient) && !((float)ref_value > max_value)) {
           const int px = f2i(roundf((((float)ref_value - min_value) / value_range) * (float)width));
           const int py = f2i(roundf(((grad_length - min_gradient) / gradient_range) * (float)height));
-          if (px >= 0 && px < width && py >= 0 && py < height) bin = px * height + py;
+          bin = hist_bin(px, py, width, height);
         }
         if (bin != run_bin) {  // neighbouring voxels mostly share a bin: one table update per run
           if (run_count) add(run_bin, run_count);

@@ -1,7 +1,13 @@
 /*
  * oracle/orc_render.c -- CPU restatement of the reference `render` kernel and everything it calls.
- * TEST INFRASTRUCTURE ONLY (see orc.h).  PARITY UNPINNED for this file: the reference ships no
- * golden vector for `render`; every function below cites the reference lines it restates.
+ * TEST INFRASTRUCTURE ONLY (see orc.h).  Every function below cites the reference lines it restates.
+ * PINNED since tests/test_ref_render.py: with threads = 1 this file gives, bit for bit, what the reference's own
+ * ray_marching.cl / utility*.cl give when they are compiled for the host from the reference's text and run one work-item
+ * after the other (oracle/ref/Makefile, oracle/ref/ref_cl_shim.cpp; outputs stored in tests/golden/ref_render.npz): hit entry
+ * and contribution per pixel, cache after every pass, raw frame, compute_ao's cache -- control flow, operation order, hash,
+ * seeds, cache addressing and token rule are the reference's.  Still a stated choice, the same here and in that shim: the
+ * OpenCL built-ins of DESIGN.md section 2's list (image reads, dot, normalize, min / max, pow / atan2 / asin), and the serial
+ * pixel order, one legal outcome of the reference's race.
  *
  * Build: gcc -O2 -ffp-contract=off -fno-fast-math -fopenmp (oracle/Makefile).
  */

@@ -1,5 +1,6 @@
 """numpy restatement of the volume pre-processing kernels next to the hot path.
-TEST INFRASTRUCTURE ONLY (see oracle/orc.h).  PARITY UNPINNED: the reference holds no fixture for them.
+TEST INFRASTRUCTURE ONLY (see oracle/orc.h).  Pinned by tests/test_ref_render.py on what the reference's own kernels, compiled
+for the host, gave for ragged volumes (tests/golden/ref_volume_kernels.npz).
 
 fetch_stats  opencl_kernels/reference_volume_figures.cl:10-26 (+ utility_filter.cl:2-35)
 apply_clip   opencl_kernels/reference_volume_clip.cl:4-15
@@ -65,16 +66,22 @@ def _round_half_away(x: np.ndarray) -> np.ndarray:
     return np.where(x >= 0, np.floor(x + np.float32(0.5)), np.ceil(x - np.float32(0.5))).astype(np.float32)
 
 
+def bin_in_buffer(px, py, width, height):
+    """histogram.cl:31 indexes frame[x * height + y] unchecked: a point off the frame's top edge (|gradient| == max_gradient rounds
+    to y == height) is counted in bin (x + 1, 0); only an index outside the buffer (the reference writes out of bounds) is dropped"""
+    i = px.astype(np.int64) * height + py.astype(np.int64)
+    return (i >= 0) & (i < width * height)
+
+
 def tf_sort_values(vol, width, height, min_v, max_v, min_g, max_g) -> np.ndarray:
-    """opencl_kernels/histogram.cl:4-32; bins outside the frame are dropped (the reference writes out of
-    bounds for them).  Returns frame[width*height] indexed x*height + y."""
+    """opencl_kernels/histogram.cl:4-32.  Returns frame[width*height] indexed x*height + y."""
     f32 = np.float32
     g = gradient_length_f32(vol)
     v = vol.astype(np.float32)
     keep = ~(g > f32(max_g)) & ~(v > f32(max_v))
     px = _round_half_away(((v - f32(min_v)) / (f32(max_v) - f32(min_v))) * f32(width)).astype(np.int64)
     py = _round_half_away(((g - f32(min_g)) / (f32(max_g) - f32(min_g))) * f32(height)).astype(np.int64)
-    keep &= (px >= 0) & (px < width) & (py >= 0) & (py < height)
+    keep &= bin_in_buffer(px, py, width, height)
     frame = np.zeros(width * height, dtype=np.uint32)
     np.add.at(frame, (px[keep] * height + py[keep]).ravel(), 1)
     return frame

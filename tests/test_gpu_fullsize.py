@@ -459,7 +459,7 @@ def test_config4_2048_volume_on_one_gpu(gpu_ctx, orc):
         keep = ~(g > f32(st[3])) & ~(vf > f32(st[1]))
         px = orc_volume._round_half_away(((vf - f32(st[0])) / (f32(st[1]) - f32(st[0]))) * f32(W5)).astype(np.int64)
         py = orc_volume._round_half_away(((g - f32(st[2])) / (f32(st[3]) - f32(st[2]))) * f32(H5)).astype(np.int64)
-        keep &= (px >= 0) & (px < W5) & (py >= 0) & (py < H5)
+        keep &= orc_volume.bin_in_buffer(px, py, W5, H5)
         hist = np.bincount((px[keep] * H5 + py[keep]).ravel(), minlength=W5 * H5)
         return int(v.min()), int(v.max()), int(gi.min()), int(gi.max()), hist
 
