@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -10,6 +10,8 @@
 // --slice=ORIENTATION[,POSITION][,slab=N][,max|min|mean]: the frames show the axial, coronal or sagittal plane of the trilinear field
 // at POSITION (voxel centres along the plane's normal; default: the middle of the volume), or the maximum / minimum / mean of a slab
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
+// --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
+// and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -37,6 +39,8 @@ int main(int argc_in, char const *argv_in[]) {
   int slice_mode = CLWH_SLICE_MAX, slice_slab = 1;
   bool slice_centred = true;
   float slice_position = 0.0f;
+  bool mesh = false, mesh_below = false;
+  float mesh_value = 0.0f;
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -76,6 +80,27 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--isosurface", 0) == 0) {
       std::cout << "Unknown option '" << a << "' (--isosurface=VALUE or --isosurface=VALUE,below)\n";
       return 1;
+    } else if (a.rfind("--mesh=", 0) == 0) {
+      std::string v = a.substr(7);
+      const size_t comma = v.find(',');
+      if (comma != std::string::npos) {
+        if (v.substr(comma + 1) != "below") {
+          std::cout << "Unknown option '" << a << "' (--mesh=VALUE or --mesh=VALUE,below)\n";
+          return 1;
+        }
+        mesh_below = true;
+        v = v.substr(0, comma);
+      }
+      char *end = nullptr;
+      mesh_value = std::strtof(v.c_str(), &end);
+      if (v.empty() || *end != '\0' || !std::isfinite(mesh_value)) {
+        std::cout << "Bad mesh value '" << v << "'\n";
+        return 1;
+      }
+      mesh = true;
+    } else if (a.rfind("--mesh", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' (--mesh=VALUE or --mesh=VALUE,below)\n";
+      return 1;
     } else if (a.rfind("--slice=", 0) == 0) {
       std::string rest = a.substr(8);
       bool ok = true;
@@ -111,6 +136,10 @@ int main(int argc_in, char const *argv_in[]) {
       args.push_back(argv_in[i]);
     }
   }
+  if (mesh && (projection >= 0 || composite >= 0 || isosurface || slice >= 0)) {
+    std::cout << "--mesh excludes --projection, --composite, --isosurface and --slice\n";
+    return 1;
+  }
   if (slice >= 0 && (projection >= 0 || composite >= 0 || isosurface)) {
     std::cout << "--slice excludes --projection, --composite and --isosurface\n";
     return 1;
@@ -126,7 +155,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -146,6 +175,20 @@ int main(int argc_in, char const *argv_in[]) {
   image em = iloader.load_file(argv[2]);
   env_map emap(ctx, em);
   emitter->image_set(&rv, &emap);
+
+  if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera
+    ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
+    const auto m0 = std::chrono::steady_clock::now();
+    const mesh_data m = r.extract_mesh(none, mesh_value, mesh_below ? CLWH_MESH_BELOW : 0);
+    const double mesh_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - m0).count();
+    if (argc > 6 && !write_ply(argv[6], m)) {
+      std::cout << "Cannot write '" << argv[6] << "'\n";
+      return 1;
+    }
+    std::printf("{\"mesh\": %s, \"below\": %s, \"vertices\": %llu, \"triangles\": %llu, \"seconds\": %.6f}\n", std::to_string(mesh_value).c_str(),
+                mesh_below ? "true" : "false", (unsigned long long)m.keys.size(), (unsigned long long)(m.triangles.size() / 3), mesh_seconds);
+    return 0;
+  }
 
   std::vector<tf_selection *> selection{new tf_rect_selection(0, 500.f, 1200.f, 0.0f, 4000.f)};
   emitter->next_event_code_set(tf_generate_source(rv.get_volume_stats(), selection));

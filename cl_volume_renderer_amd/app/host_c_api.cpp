@@ -18,6 +18,7 @@ struct clvr_host {
   std::unique_ptr<reference_volume> rv;
   std::unique_ptr<env_map> emap;
   ui_state state;
+  mesh_data mesh;  // of the last clvr_host_extract_mesh
   clvr_host() : rend(ctx), state{"", true, 0, 0, Position3D(0, 0, 0), {0.f, 0.f}, true} {}
 };
 
@@ -119,6 +120,20 @@ const void *clvr_host_render_slice(clvr_host *h, int width, int height, int orie
   h->state.height = height;
   return h->rend.render_slice(h->state, orientation, position, mode, slab_samples, step, center, window_width, flags);
 }
+// renderer::extract_mesh: the counts, and pointers to the host's copy of the arrays (float[n][3], float[n][3], uint64[n], uint32[m][3]),
+// valid until the next call or clvr_host_destroy
+void clvr_host_extract_mesh(clvr_host *h, float iso, int flags, unsigned long long *n_vertices, unsigned long long *n_triangles,
+                            const float **positions, const float **normals, const unsigned long long **keys, const unsigned **triangles) {
+  h->mesh = h->rend.extract_mesh(h->state, iso, flags);
+  *n_vertices = h->mesh.keys.size();
+  *n_triangles = h->mesh.triangles.size() / 3;
+  *positions = h->mesh.positions.data();
+  *normals = h->mesh.normals.data();
+  *keys = reinterpret_cast<const unsigned long long *>(h->mesh.keys.data());
+  *triangles = h->mesh.triangles.data();
+}
+// write_ply of that mesh; 1 on success
+int clvr_host_write_mesh_ply(clvr_host *h, const char *path) { return write_ply(path, h->mesh) ? 1 : 0; }
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <set>
 
@@ -215,6 +216,60 @@ void *renderer::render_slice(struct ui_state &state, int orientation, float posi
   clw_fail_hard_on_error(clwh_render_slice(ctx.get_handle(), &d));
   frame.pull();
   return &frame[0];
+}
+
+mesh_data renderer::extract_mesh(struct ui_state &, float iso, int flags) {
+  mesh_data out;
+  uint64_t nv = 0, nt = 0;
+  clwh_mesh_desc d{};
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.iso = iso;
+  d.flags = flags;
+  d.n_vertices = &nv;
+  d.n_triangles = &nt;
+  clw_fail_hard_on_error(clwh_mesh_isosurface(ctx.get_handle(), &d));  // counts only
+  if (nv == 0) return out;
+  clw_vector<float> positions(ctx, std::vector<float>((size_t)nv * 3)), normals(ctx, std::vector<float>((size_t)nv * 3));
+  clw_vector<uint64_t> keys(ctx, std::vector<uint64_t>((size_t)nv));
+  clw_vector<uint32_t> triangles(ctx, std::vector<uint32_t>((size_t)nt * 3));
+  d.positions = positions.get_device_reference();
+  d.normals = normals.get_device_reference();
+  d.keys = keys.get_device_reference();
+  d.triangles = triangles.get_device_reference();
+  d.vertex_capacity = nv;
+  d.triangle_capacity = nt;
+  clw_fail_hard_on_error(clwh_mesh_isosurface(ctx.get_handle(), &d));
+  positions.pull();
+  normals.pull();
+  keys.pull();
+  triangles.pull();
+  out.positions.assign(&positions[0], &positions[0] + positions.size());
+  out.normals.assign(&normals[0], &normals[0] + normals.size());
+  out.keys.assign(&keys[0], &keys[0] + keys.size());
+  out.triangles.assign(&triangles[0], &triangles[0] + triangles.size());
+  return out;
+}
+
+// (the host is little-endian, like every target of the library: the arrays go out as they lie in memory)
+bool write_ply(const std::string &path, const mesh_data &mesh) {
+  const size_t nv = mesh.positions.size() / 3, nt = mesh.triangles.size() / 3;
+  if (mesh.normals.size() != mesh.positions.size()) return false;
+  std::ofstream f(path, std::ios::binary);
+  f << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv
+    << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nelement face " << nt
+    << "\nproperty list uchar uint vertex_indices\nend_header\n";
+  std::vector<char> body(nv * 24 + nt * 13);
+  for (size_t i = 0; i < nv; ++i) {
+    std::memcpy(&body[i * 24], &mesh.positions[i * 3], 12);
+    std::memcpy(&body[i * 24 + 12], &mesh.normals[i * 3], 12);
+  }
+  for (size_t i = 0; i < nt; ++i) {
+    body[nv * 24 + i * 13] = 3;
+    std::memcpy(&body[nv * 24 + i * 13 + 1], &mesh.triangles[i * 3], 12);
+  }
+  f.write(body.data(), (std::streamsize)body.size());
+  f.flush();
+  return f.good();
 }
 
 // reference :45-124 -- the 2-D (value, |gradient|) histogram texture of the transfer-function editor:

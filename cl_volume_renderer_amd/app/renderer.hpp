@@ -1,6 +1,7 @@
 // renderer.hpp -- the renderer the SDL/ImGui application talks to: same class name, base class and
 // public methods as the reference's app/renderer.hpp:10-29, so `ui::run(&renderer)` is a drop-in.
 #pragma once
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -12,6 +13,16 @@
 
 #include "signed_distance_field.hpp"
 #include "ui.hpp"
+
+// renderer::extract_mesh's result: the isosurface as an indexed triangle mesh in voxel space (clwh_mesh_isosurface)
+struct mesh_data {
+  std::vector<float> positions, normals;  // three per vertex
+  std::vector<uint64_t> keys;             // one per vertex: the grid edge it sits on
+  std::vector<uint32_t> triangles;        // three vertex indices per triangle, counter-clockwise seen from outside
+};
+// binary little-endian PLY (vertex x y z nx ny nz float, face uchar uint list): the bytes of scene.write_ply.  false: the file could
+// not be written
+bool write_ply(const std::string &path, const mesh_data &mesh);
 
 class renderer : public frame_emitter {
  public:
@@ -64,6 +75,11 @@ class renderer : public frame_emitter {
   // cross-section fits the region, centred in it; the slab centred on `position`.  Computed in double, rounded once.
   static void slice_plane(const size_t dims[3], int orientation, float position, int width, int height, int slab_samples, float step,
                           float origin[3], float du[3], float dv[3], float normal[3]);
+
+  // not in the reference: the isosurface of the volume's grid at value `iso` as a triangle mesh (marching tetrahedra on the voxel
+  // centres; flags: CLWH_MESH_DENSE | CLWH_MESH_BELOW): one counting call, buffers of that size, the filling call, the readback.
+  // Unlike the views it waits for the device; no camera takes part (`state` is not read).
+  mesh_data extract_mesh(struct ui_state &state, float iso, int flags = 0);
 
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }

@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing, isosurfaces and slices).
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing, isosurfaces, slices and the isosurface mesh).
 // No kernel needs this header.
 #pragma once
 
@@ -220,6 +220,9 @@ struct ProjectionData {
   // valid only while `valid` is and for the same key
   DeviceBuffer dilated;
   bool dilated_valid = false;  // cleared whenever `data` is rebuilt and by clwh_ctx_invalidate_derived (projection)
+  // clwh_mesh_isosurface only: its scratch (per-brick counts and their scans, the scan's work space, the point table of the bricks with
+  // a vertex).  Every call rewrites what it reads, so nothing here outlives a call: only the allocations are kept
+  DeviceBuffer mesh_counts, mesh_temp, mesh_points;
   DeviceBuffer lut_prefix;
   bool lut_valid = false;  // cleared by clwh_ctx_invalidate_derived (projection)
   const void *lut = nullptr;

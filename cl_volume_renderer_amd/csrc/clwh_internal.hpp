@@ -324,4 +324,31 @@ struct SliceArgs {
 };
 hipError_t launch_slice(const SliceArgs &a, int mode, bool dense, hipStream_t s);
 
+// ---- the isosurface as an indexed triangle mesh (mesh_kernels.hip): marching tetrahedra over the projections' bricked copy, one block
+// per 8^3 brick; without CLWH_MESH_DENSE the isosurface's dilated {min, max} table says which bricks the surface can touch
+struct MeshArgs {
+  const int16_t *bricks;
+  const uint32_t *table;   // the projections' {min, max} table (not read by the mesher)
+  const uint32_t *dilated; // as IsoArgs::dilated; read when `skip` is set
+  const uint32_t *coarse;  // as IsoArgs::coarse (not read by the mesher)
+  int32_t X, Y, Z, NBX, NBY, CNX, CNY;
+  uint64_t n_bricks;       // NBX * NBY * NBZ: the grid of every launch
+  int32_t lo[3], hi[3];    // the box in grid points, lo < hi <= dim - 1 on every axis
+  int64_t threshold;       // T = floor(iso * 2^24)
+  int32_t in_bound;        // V is inside iff V >= in_bound (ceil(T / 2^24)), below: iff V <= in_bound (floor(T / 2^24))
+  int32_t below, skip;
+  // three columns of n_bricks + 1 words each: vertices, triangles, "has a vertex" per brick, the last word 0 -- `counts` as k_mesh_count
+  // writes them, `bases` their exclusive scans (so the last word of a column is its total)
+  uint64_t *counts;
+  const uint64_t *bases;
+  uint32_t *points;        // per brick with a vertex (slot = bases[2][brick]) 512 words: edge mask | rank << 8 per grid point
+  float *positions;        // [n_vertices][3]
+  float *normals;          // optional, same
+  uint64_t *keys;          // optional, [n_vertices]
+  uint32_t *triangles;     // optional, [n_triangles][3]
+};
+hipError_t launch_mesh_count(const MeshArgs &a, hipStream_t s);
+hipError_t launch_mesh_scan(void *temp, size_t &temp_bytes, const uint64_t *counts, uint64_t *bases, size_t n, hipStream_t s);
+hipError_t launch_mesh_fill(const MeshArgs &a, hipStream_t s);  // k_mesh_vertices, then k_mesh_triangles if `triangles` is given
+
 }  // namespace clvr

@@ -24,6 +24,7 @@ COMP_DENSE, COMP_SHADE = 1, 2
 ISO_DENSE, ISO_BELOW = 1, 2
 SLICE_MAX, SLICE_MIN, SLICE_MEAN = 0, 1, 2
 SLICE_DENSE = 1
+MESH_DENSE, MESH_BELOW = 1, 2
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -131,6 +132,17 @@ class SliceDesc(C.Structure):
     ]
 
 
+class MeshDesc(C.Structure):
+    _fields_ = [
+        ("volume", C.c_void_p),
+        ("iso", C.c_float), ("flags", C.c_int32),
+        ("box_lo", C.c_uint32 * 3), ("box_hi", C.c_uint32 * 3),
+        ("positions", C.c_void_p), ("normals", C.c_void_p), ("keys", C.c_void_p), ("triangles", C.c_void_p),
+        ("vertex_capacity", C.c_uint64), ("triangle_capacity", C.c_uint64),
+        ("n_vertices", C.POINTER(C.c_uint64)), ("n_triangles", C.POINTER(C.c_uint64)),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -169,6 +181,7 @@ _PROTOTYPES = [
     ("clwh_render_composite", C.c_int, [C.c_void_p, C.POINTER(CompositeDesc)]),
     ("clwh_render_isosurface", C.c_int, [C.c_void_p, C.POINTER(IsosurfaceDesc)]),
     ("clwh_render_slice", C.c_int, [C.c_void_p, C.POINTER(SliceDesc)]),
+    ("clwh_mesh_isosurface", C.c_int, [C.c_void_p, C.POINTER(MeshDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -484,6 +497,47 @@ class Context:
         d.values = values.h if values is not None else None
         d.t_extreme = t_extreme.h if t_extreme is not None else None
         _check(lib().clwh_render_slice(self.h, C.byref(d)), "clwh_render_slice")
+
+    def mesh_isosurface_raw(self, volume: Mem, iso, flags=0, box=None, positions: Mem = None, normals: Mem = None, keys: Mem = None,
+                            triangles: Mem = None, vertex_capacity=0, triangle_capacity=0):
+        """one clwh_mesh_isosurface call: (status, n_vertices, n_triangles); nothing is raised.  box = ((lo), (hi)) in grid points."""
+        d = MeshDesc()
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        d.volume = volume.h if volume is not None else None
+        d.iso, d.flags = float(iso), int(flags)
+        if box is not None:
+            for k in range(3):
+                d.box_lo[k], d.box_hi[k] = int(box[0][k]), int(box[1][k])
+        d.positions = positions.h if positions is not None else None
+        d.normals = normals.h if normals is not None else None
+        d.keys = keys.h if keys is not None else None
+        d.triangles = triangles.h if triangles is not None else None
+        d.vertex_capacity, d.triangle_capacity = int(vertex_capacity), int(triangle_capacity)
+        d.n_vertices, d.n_triangles = C.pointer(nv), C.pointer(nt)
+        status = lib().clwh_mesh_isosurface(self.h, C.byref(d))
+        return status, int(nv.value), int(nt.value)
+
+    def mesh_isosurface(self, volume: Mem, iso, flags=0, box=None, normals=True, keys=False):
+        """the isosurface of `volume` (S16) at `iso` as an indexed triangle mesh (marching tetrahedra on the voxel centres; positions
+        in voxel space): (positions float32[n][3], normals float32[n][3] | None, triangles uint32[m][3], keys uint64[n] | None) as
+        numpy arrays.  flags: MESH_DENSE | MESH_BELOW; box = ((lo), (hi)) in grid points, None = the whole volume.  One counting
+        call, then the filling call; both wait for the device."""
+        status, nv, nt = self.mesh_isosurface_raw(volume, iso, flags, box)
+        _check(status, "clwh_mesh_isosurface")
+        out_n = np.zeros((nv, 3), np.float32) if normals else None
+        out_k = np.zeros((nv,), np.uint64) if keys else None
+        if nv == 0:
+            return np.zeros((0, 3), np.float32), out_n, np.zeros((0, 3), np.uint32), out_k
+        bufs = [self.buffer(nv * 12, np.float32, (nv, 3)), self.buffer(nv * 12, np.float32, (nv, 3)) if normals else None,
+                self.buffer(nv * 8, np.uint64, (nv,)) if keys else None, self.buffer(max(nt, 1) * 12, np.uint32, (max(nt, 1), 3))]
+        try:
+            status, _, _ = self.mesh_isosurface_raw(volume, iso, flags, box, bufs[0], bufs[1], bufs[2], bufs[3], nv, nt)
+            _check(status, "clwh_mesh_isosurface")
+            return (bufs[0].pull(), bufs[1].pull() if normals else None, bufs[3].pull()[:nt], bufs[2].pull() if keys else None)
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.release()
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

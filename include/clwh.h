@@ -213,8 +213,8 @@ int clwh_frame_from_tiles(clwh_ctx *ctx, clwh_mem *tiles_all_ranks, int32_t tile
  *   CLWH_DERIVED_PROJECTION  the bricked int16 copy of the volume + per-brick {min, max} table that clwh_render_projection and
  *                        clwh_render_composite share, per context (ONE copy: 2 bytes per voxel + 4 per 8^3 brick), and with it the
  *                        prefix count over clwh_render_composite's colour/opacity table (4 bytes per entry) and the dilated
- *                        {min, max} tables that clwh_render_isosurface and clwh_render_slice share (4 bytes per brick and per
- *                        4^3 bricks): all are dropped */
+ *                        {min, max} tables that clwh_render_isosurface, clwh_render_slice and clwh_mesh_isosurface share (4 bytes
+ *                        per brick and per 4^3 bricks): all are dropped */
 enum clwh_derived { CLWH_DERIVED_SCENE = 1, CLWH_DERIVED_CAMERA = 2, CLWH_DERIVED_PROJECTION = 4 };
 int clwh_ctx_invalidate_derived(clwh_ctx *ctx, int what);
 /* which copy of the derived scene data the context renders from (after its last clwh_render): a process-wide unique id
@@ -438,6 +438,81 @@ typedef struct clwh_slice_desc {
   clwh_mem *t_extreme;        /* optional float32[height][width] */
 } clwh_slice_desc;
 int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *desc);
+
+/* ---- the isosurface as an indexed triangle mesh, by marching tetrahedra (not in the reference): the first output that is geometry, not
+ * pixels.  Every decision is an integer comparison, so the result is defined bit for bit.
+ * Grid.  Grid point P = (x, y, z), 0 <= P.c < dim_c, carries A(P) = (int64)V[z][y][x] << 24 and sits at the voxel's centre P + 0.5: the
+ * voxel space of clwh_render_slice and of the trilinear field S, whose value at a voxel centre is exactly A(P).
+ * T = (int64)floor((double)iso * 16777216.0), as for clwh_render_isosurface.  P is INSIDE iff A(P) >= T, with CLWH_MESH_BELOW iff
+ * A(P) <= T.
+ * Box.  The cells meshed are those with origin c, lo_k <= c.k < hi_k; box_lo / box_hi are given in grid points,
+ * 0 <= lo_k <= hi_k <= dim_k - 1.  box_hi all zero means the whole volume, hi_k = dim_k - 1.  An axis with lo_k == hi_k gives the empty
+ * mesh (0 vertices, 0 triangles, CLWH_OK).
+ * Tetrahedra.  The corners of a cell are numbered by the mask m = dx | dy << 1 | dz << 2.  Every cell is cut into the six tetrahedra of
+ * the Kuhn triangulation, one per permutation (a, b, c) of the axis bits {1, 2, 4}, in lexicographic order of (a, b); each has the
+ * corners 0, a, a|b, 7 in this order.  All share the body diagonal, and the cut is the same in every cell, so neighbouring cells agree on
+ * the diagonal of their common face.  Every edge of a tetrahedron runs from a grid point P to Q = P + d with d in {0,1}^3 \ {0}: seven
+ * kinds of edge, dir = d.x | d.y << 1 | d.z << 2 in 1..7.
+ * Vertices.  One per edge (P, dir) such that P and Q both lie in [lo, hi] on every axis (inclusive) and exactly one of P, Q is inside
+ * (hence A(P) != A(Q)):
+ *   key = ((P.z * Y + P.y) * X + P.x) * 8 + dir, a uint64
+ *   w = (|T - A(P)| << 16) / |A(Q) - A(P)|, an int64 floor division, in [0, 65536]; always taken from the lower end P, so every
+ *     tetrahedron and cell that shares the edge gets the same vertex
+ *   position, per axis: F_c = P.c * 65536 + 32768 + (Q.c - P.c) * w as an integer, pos_c = (float)F_c * 2^-16: the conversion is ONE
+ *     rounding to nearest-even, the scaling is exact
+ *   normal: g_c(R) = V(R + e_c) - V(R - e_c) in int32, each neighbour coordinate clamped to [0, dim_c - 1] (the isosurface's central
+ *     differences); G_c = (65536 - w) * g_c(P) + w * g_c(Q), an exact int64, |G_c| < 2^34; g_c = (float)G_c, one rounding;
+ *     l2 = (gx*gx + gy*gy) + gz*gz; if l2 > 0: n_c = (-g_c) / sqrtf(l2), with CLWH_MESH_BELOW n_c = g_c / sqrtf(l2) (float32, without
+ *     contraction, sqrtf and / correctly rounded: the compositor's words), so that the normal points to the outside; otherwise
+ *     n = (0, 0, 0).
+ * Triangles.  Let a tetrahedron's corners be at positions 0..3 in the order above.  0 or 4 of them inside: no triangle.  One inside a,
+ * outside b < c < d: one triangle over the edges (a,b), (a,c), (a,d).  Three inside a < b < c, outside d: one triangle over (a,d),
+ * (b,d), (c,d).  Two inside a < b, outside c < d: the quad (a,c), (a,d), (b,d), (b,c), split along (a,c)-(b,d) into q0 q1 q2 and
+ * q0 q2 q3.  The winding is decided from the grid, never from vertex positions (which may coincide): with each vertex replaced by the
+ * midpoint of its edge, m0, m1, m2, the triangle is emitted in the order for which ((m1 - m0) x (m2 - m0)) . (centroid of the outside
+ * corners - centroid of the inside corners) > 0, otherwise with its last two vertices swapped: counter-clockwise seen from the
+ * outside.  (The sign depends only on the tetrahedron and its 4-bit case.)  A triangle is three uint32 indices into the vertex array.
+ * Triangles with coinciding positions are kept (w = 0 or 65536: a grid value equal to iso).
+ * Order.  The order of vertices and of triangles is unspecified but deterministic: two calls with the same inputs give the same bytes,
+ * and no order depends on the scheduling of the device.  Every vertex is referenced by at least one triangle.  The surface is left open
+ * where it meets the box: no caps.
+ * Buffers.  positions and normals (float32[capacity][3]), keys (uint64[capacity]) and triangles (uint32[capacity][3]) are plain device
+ * buffers (clwh_mem_create, clwh_mem_wrap), all optional; positions and triangles come together, and normals and keys only with them.
+ * The call always stores the true counts in *n_vertices and *n_triangles.  With every buffer NULL and both capacities 0 it only counts.
+ * If a count exceeds its capacity, or 2^32 - 1, the call returns CLWH_ERR_SIZE_MISMATCH with the counts set and writes nothing to the
+ * buffers: the caller allocates and calls again.
+ * SYNCHRONOUS, unlike the views: the call is ordered on the context's stream, but it waits for the device -- once for the counts, once
+ * more after filling -- and returns with the buffers written.  It is not a per-frame call.
+ * Skipping.  Without CLWH_MESH_DENSE a brick of 8^3 grid points is visited only if its pair {dmin, dmax} over the brick DILATED BY ONE
+ * VOXEL (the table of clwh_render_isosurface) allows a crossing: dmin * 2^24 < T <= dmax * 2^24, with CLWH_MESH_BELOW
+ * dmin * 2^24 <= T < dmax * 2^24.  Proof: every edge owned by a grid point of the brick, and every corner of a cell whose origin lies in
+ * the brick, is within one voxel of the brick; a crossing needs one end inside and one end outside, that is a value on either side of
+ * T in the dilated box.  Same bytes as CLWH_MESH_DENSE, order included: the dense walk visits every brick and finds nothing in the others.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc, n_vertices or n_triangles; a NULL or wrong-kind
+ * volume; unknown flag bits; iso not finite or |iso| > 65536; a box that breaks the rule above; a buffer that is an image; triangles
+ * without positions or the reverse; normals or keys without positions; a capacity > 0 whose buffer (positions, triangles) is NULL;
+ * volume dims beyond the projections' rule.  CLWH_ERR_SIZE_MISMATCH: a buffer smaller than its capacity times its element size (12,
+ * 12, 8, 12 bytes), and the capacity rule above.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.
+ * The derived data (CLWH_DERIVED_PROJECTION) is the projections' bricked copy of the volume and, without CLWH_MESH_DENSE, the dilated
+ * {min, max} tables, keyed and invalidated exactly as for clwh_render_isosurface.  The mesher's scratch (48 bytes per brick, and 2 KiB
+ * per brick that has a vertex while a filling call runs) is kept with them and holds nothing between calls. */
+enum clwh_mesh_flags {
+  CLWH_MESH_DENSE = 1,  /* no brick skipping: same result by contract; for tests and timing */
+  CLWH_MESH_BELOW = 2   /* inside iff A <= T */
+};
+typedef struct clwh_mesh_desc {
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  float iso;                  /* finite, |iso| <= 65536 */
+  int32_t flags;
+  uint32_t box_lo[3], box_hi[3];  /* grid points; box_hi all zero = the whole volume */
+  clwh_mem *positions;        /* optional float32[vertex_capacity][3] */
+  clwh_mem *normals;          /* optional float32[vertex_capacity][3] */
+  clwh_mem *keys;             /* optional uint64[vertex_capacity] */
+  clwh_mem *triangles;        /* optional uint32[triangle_capacity][3] */
+  uint64_t vertex_capacity, triangle_capacity;
+  uint64_t *n_vertices, *n_triangles;  /* host; required */
+} clwh_mesh_desc;
+int clwh_mesh_isosurface(clwh_ctx *ctx, const clwh_mesh_desc *desc);
 
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
