@@ -95,21 +95,32 @@ void renderer::render_frame_device(struct ui_state &state, const clw_foreign_mem
   state.path_changed = false;
 }
 
-void *renderer::render_projection(struct ui_state &state, int mode, float center, float width, float step) {
-  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
-  clwh_projection_desc d{};
+// what the view descriptors share: the frame, the volume and the launched region (every view) ...
+template <class Desc>
+static void fill_region(Desc &d, const clw_image<unsigned char, 4> &frame, const reference_volume &volume, const struct ui_state &state) {
   d.frame = frame.get_device_reference();
-  d.volume = volume->get_reference_volume().get_device_reference();
+  d.volume = volume.get_reference_volume().get_device_reference();
+  d.width = (uint32_t)state.width;
+  d.height = (uint32_t)state.height;
+}
+// ... and the camera of `state` with the whole ray as the slab (the camera views)
+template <class Desc>
+static void fill_view(Desc &d, const clw_image<unsigned char, 4> &frame, const reference_volume &volume, const struct ui_state &state) {
+  fill_region(d, frame, volume, state);
+  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
   for (int q = 0; q < 3; ++q) {
     d.cam_pos[q] = (float)state.position.val[q];
     d.cam_dir[q] = (float)vec.val[q];
   }
-  d.width = (uint32_t)state.width;
-  d.height = (uint32_t)state.height;
-  d.mode = mode;
-  d.step = step;
   d.t_near = 0.0f;
   d.t_far = INFINITY;
+}
+
+void *renderer::render_projection(struct ui_state &state, int mode, float center, float width, float step) {
+  clwh_projection_desc d{};
+  fill_view(d, frame, *volume, state);
+  d.mode = mode;
+  d.step = step;
   d.window_center = center;
   d.window_width = width;
   clw_fail_hard_on_error(clwh_render_projection(ctx.get_handle(), &d));
@@ -127,20 +138,10 @@ void *renderer::render_composite(struct ui_state &state, const std::vector<float
     composite_lut = clw_vector<float>(ctx, std::vector<float>(lut), true);
     composite_lut_pushed = true;
   }
-  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
   clwh_composite_desc d{};
-  d.frame = frame.get_device_reference();
-  d.volume = volume->get_reference_volume().get_device_reference();
-  for (int q = 0; q < 3; ++q) {
-    d.cam_pos[q] = (float)state.position.val[q];
-    d.cam_dir[q] = (float)vec.val[q];
-  }
-  d.width = (uint32_t)state.width;
-  d.height = (uint32_t)state.height;
+  fill_view(d, frame, *volume, state);
   d.flags = flags;
   d.step = step;
-  d.t_near = 0.0f;
-  d.t_far = INFINITY;
   d.lut = composite_lut.get_device_reference();
   d.lut_first = lut_first;
   d.lut_len = lut_len;
@@ -153,20 +154,10 @@ void *renderer::render_composite(struct ui_state &state, const std::vector<float
 
 void *renderer::render_isosurface(struct ui_state &state, float iso, int flags, float step, int refine, float ambient, float red,
                                   float green, float blue) {
-  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
   clwh_isosurface_desc d{};
-  d.frame = frame.get_device_reference();
-  d.volume = volume->get_reference_volume().get_device_reference();
-  for (int q = 0; q < 3; ++q) {
-    d.cam_pos[q] = (float)state.position.val[q];
-    d.cam_dir[q] = (float)vec.val[q];
-  }
-  d.width = (uint32_t)state.width;
-  d.height = (uint32_t)state.height;
+  fill_view(d, frame, *volume, state);
   d.flags = flags;
   d.step = step;
-  d.t_near = 0.0f;
-  d.t_far = INFINITY;
   d.iso = iso;
   d.refine = refine;
   d.color[0] = red;
@@ -200,13 +191,10 @@ void *renderer::render_slice(struct ui_state &state, int orientation, float posi
                              float width, int flags) {
   if (orientation < SLICE_AXIAL || orientation > SLICE_SAGITTAL || state.width < 1 || state.height < 1) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
   clwh_slice_desc d{};
-  d.frame = frame.get_device_reference();
-  d.volume = volume->get_reference_volume().get_device_reference();
+  fill_region(d, frame, *volume, state);
   const auto &size = volume->get_volume_size();
   const size_t dims[3] = {size[0], size[1], size[2]};
   slice_plane(dims, orientation, position, state.width, state.height, slab_samples, step, d.origin, d.du, d.dv, d.normal);
-  d.width = (uint32_t)state.width;
-  d.height = (uint32_t)state.height;
   d.mode = mode;
   d.flags = flags;
   d.slab_samples = slab_samples;

@@ -1,6 +1,7 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_projection.hip: projections, compositing, isosurfaces, slices and the isosurface mesh).
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces and slices; clwh_mesh.hip: the
+// isosurface mesh).
 // No kernel needs this header.
 #pragma once
 
@@ -341,6 +342,11 @@ inline void env_into_args(RenderArgs &a, const clwh_mem *env) {
   a.env_w = (int32_t)env->dims[0];
   a.env_h = (int32_t)env->dims[1];
 }
+
+// ---- the derived data the views and the mesher share (clwh_views.hip): the bricked copy of `volume` and its {min, max} table, which
+// also sets v's dims and grids; then, for the callers that may skip by them, the dilated and cell tables
+int ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, ViewVolume &v);
+int ensure_dilated_table(clwh_ctx *ctx, ViewVolume &v);
 
 // ---- a timed region: `launches` (a callable returning hipError_t) between a (begin, end) event pair of timer `which`;
 // with timing off it is `launches` and nothing else -- no event is created or recorded

@@ -229,43 +229,56 @@ hipError_t launch_bilateral_filter(const int16_t *src, int X, int Y, int Z, int1
 hipError_t launch_apply_clip(const int16_t *src, int SX, int SY, int SZ, int16_t *dst, int DX, int DY, int DZ,
                              const uint32_t *start, const uint32_t *len, hipStream_t s);
 
-// ---- intensity projections (projection_kernels.hip): the caller's S16 image in brick order (packed_volume.hpp inner_index,
-// one 4^3 sub-brick = one 128-byte line) plus a {min, max} int16 pair per 8^3 brick, built by k_proj_repack
-struct ProjRepackArgs {
-  const int16_t *volume;  // the caller's image, x fastest
-  int32_t X, Y, Z, NBX, NBY, NBZ;
-  int16_t *bricks;        // NBX * NBY * NBZ * 512 voxels
-  uint32_t *table;        // per brick: (uint16)min | (uint16)max << 16, over the brick's real voxels
-};
-struct ProjArgs {
+// ---- the views of the bricked volume (clwh_views.hip, clwh_mesh.hip): intensity projections, compositing, the isosurface, slices and
+// the isosurface mesh.  Their kernel arguments are composed of three blocks (plain members: memset and pass-by-value stay valid).
+
+// The derived data every view reads.  `bricks`: the caller's S16 image in brick order (packed_volume.hpp inner_index, one 4^3 sub-brick
+// = one 128-byte line), NBX * NBY * NBZ * 512 voxels.  `table`: per 8^3 brick (uint16)min | (uint16)max << 16 over its real voxels.
+// Both are built by k_proj_repack (ensure_projection_data).  `dilated`: the same pair over the voxels within one voxel of the brick
+// (clamped at the volume's faces); `coarse`, stored behind it: the pair per cell of 4^3 bricks (CNX x CNY x ceil(NBZ / 4) cells).
+// Both are built by k_iso_dilate / k_iso_coarse and nullptr until ensure_dilated_table has run.
+struct ViewVolume {
   const int16_t *bricks;
-  const uint32_t *table;
-  int32_t X, Y, Z, NBX, NBY;
+  const uint32_t *table, *dilated, *coarse;
+  int32_t X, Y, Z, NBX, NBY, NBZ, CNX, CNY;
+};
+// where an image view writes: one wave per 8x8 pixel tile of the launched region
+struct ViewFrame {
   uint32_t *frame;        // RGBA8 packed, row-major, frame_w x frame_h
   int32_t frame_w, frame_h;
   int32_t launch_w, launch_h, tiles_x, num_tiles;
+};
+// the camera and the march along its rays
+struct ViewCamera {
   float cam_pos[3], cam_dir[3];
   float step, t_near, t_far;
+  int32_t k_cap;          // every kept sample has k < k_cap (view_march_ok checks the camera distance / step)
+};
+
+// ---- intensity projections (projection_kernels.hip)
+struct ProjRepackArgs {
+  const int16_t *volume;  // the caller's image, x fastest
+  int32_t X, Y, Z, NBX, NBY, NBZ;
+  int16_t *bricks;        // ViewVolume::bricks
+  uint32_t *table;        // ViewVolume::table
+};
+struct ProjArgs {
+  ViewVolume vol;
+  ViewFrame fr;
+  ViewCamera cam;
   float window_center, window_width;
-  int32_t k_cap;          // every kept sample has k < k_cap (clwh_render_projection checks the camera distance / step)
   float *values;          // optional, row-major launch_w x launch_h
   float *t_extreme;       // optional, same
 };
 hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s);
 hipError_t launch_projection(const ProjArgs &a, int mode, bool dense, hipStream_t s);
 
-// ---- compositing through a colour/opacity table (composite_kernels.hip): the projections' bricked copy and {min, max} table plus
-// the table's prefix count of entries with a > 0, built by k_comp_prefix
+// ---- compositing through a colour/opacity table (composite_kernels.hip): beside the volume the table's prefix count of entries with
+// a > 0, built by k_comp_prefix
 struct CompArgs {
-  const int16_t *bricks;
-  const uint32_t *table;
-  int32_t X, Y, Z, NBX, NBY;
-  uint32_t *frame;        // RGBA8 packed, row-major, frame_w x frame_h
-  int32_t frame_w, frame_h;
-  int32_t launch_w, launch_h, tiles_x, num_tiles;
-  float cam_pos[3], cam_dir[3];
-  float step, t_near, t_far;
-  int32_t k_cap;          // as ProjArgs::k_cap
+  ViewVolume vol;
+  ViewFrame fr;
+  ViewCamera cam;
   const float4 *lut;      // lut_len entries (r, g, b, a), 16-byte aligned
   const uint32_t *prefix; // prefix[i] = number of entries j <= i with a > 0
   int32_t lut_first, lut_len;
@@ -277,44 +290,29 @@ struct CompArgs {
 hipError_t launch_comp_prefix(const float4 *lut, int32_t lut_len, uint32_t *prefix, hipStream_t s);
 hipError_t launch_composite(const CompArgs &a, bool shade, bool dense, hipStream_t s);
 
-// ---- isosurface of the trilinear field (isosurface_kernels.hip): the projections' bricked copy plus a {min, max} pair per 8^3 brick
-// over the brick DILATED by one voxel (clamped at the volume's faces), built by k_iso_dilate, and the same pair per cell of 4^3 bricks
+// ---- isosurface of the trilinear field (isosurface_kernels.hip)
 struct IsoArgs {
-  const int16_t *bricks;
-  const uint32_t *table;   // the projections' {min, max} table (not read by k_isosurface)
-  const uint32_t *dilated; // per brick: (uint16)min | (uint16)max << 16 over the voxels within one voxel of the brick
-  int32_t X, Y, Z, NBX, NBY;
-  uint32_t *frame;         // RGBA8 packed, row-major, frame_w x frame_h
-  int32_t frame_w, frame_h;
-  int32_t launch_w, launch_h, tiles_x, num_tiles;
-  float cam_pos[3], cam_dir[3];
-  float step, t_near, t_far;
-  int32_t k_cap;           // as ProjArgs::k_cap
+  ViewVolume vol;
+  ViewFrame fr;
+  ViewCamera cam;
   int64_t threshold;       // T = floor(iso * 2^24)
   int32_t skip_bound;      // a brick is stepped over iff dmax < skip_bound (ceil(T / 2^24)), BELOW: iff dmin > skip_bound (floor(T / 2^24))
   int32_t refine;
   float color[3], ambient;
   float *t_hit;            // optional, row-major launch_w x launch_h
   float4 *normal;          // optional, same
-  const uint32_t *coarse;  // the same pair per cell of 4^3 bricks (CNX x CNY x CNZ cells), stored behind `dilated`
-  int32_t CNX, CNY;
 };
-// `dilated` holds NBX * NBY * NBZ entries followed by ceil(NBX / 4) * ceil(NBY / 4) * ceil(NBZ / 4) cell entries
-hipError_t launch_iso_dilate(const int16_t *bricks, int X, int Y, int Z, int NBX, int NBY, int NBZ, uint32_t *dilated, hipStream_t s);
+// `dilated` receives v.NBX * v.NBY * v.NBZ entries followed by the cells' (ViewVolume::coarse)
+hipError_t launch_iso_dilate(const ViewVolume &v, uint32_t *dilated, hipStream_t s);
 hipError_t launch_isosurface(const IsoArgs &a, bool below, bool dense, hipStream_t s);
 
-// ---- oblique slices and thick slabs of the trilinear field (slice_kernels.hip): parallel rays with one origin per pixel over the
-// projections' bricked copy; MAX / MIN may step over bricks (and cells of 4^3 bricks) by the isosurface's dilated {min, max} tables
+// ---- oblique slices and thick slabs of the trilinear field (slice_kernels.hip): parallel rays with one origin per pixel; MAX / MIN may
+// step over bricks (and cells of 4^3 bricks) by the dilated tables, which stay nullptr when the launch cannot skip (MEAN,
+// CLWH_SLICE_DENSE)
 struct SliceArgs {
-  const int16_t *bricks;
-  const uint32_t *table;   // the projections' {min, max} table (not read by k_slice)
-  const uint32_t *dilated; // as IsoArgs::dilated; nullptr when the launch cannot skip (MEAN, CLWH_SLICE_DENSE)
-  const uint32_t *coarse;  // as IsoArgs::coarse
-  int32_t X, Y, Z, NBX, NBY, CNX, CNY;
+  ViewVolume vol;
+  ViewFrame fr;
   int32_t use_coarse;      // 1: ask the cell of 4^3 bricks first (Tuning::slice_coarse)
-  uint32_t *frame;         // RGBA8 packed, row-major, frame_w x frame_h
-  int32_t frame_w, frame_h;
-  int32_t launch_w, launch_h, tiles_x, num_tiles;
   float origin[3], du[3], dv[3], normal[3];
   float step;
   float window_center, window_width;
@@ -324,14 +322,10 @@ struct SliceArgs {
 };
 hipError_t launch_slice(const SliceArgs &a, int mode, bool dense, hipStream_t s);
 
-// ---- the isosurface as an indexed triangle mesh (mesh_kernels.hip): marching tetrahedra over the projections' bricked copy, one block
-// per 8^3 brick; without CLWH_MESH_DENSE the isosurface's dilated {min, max} table says which bricks the surface can touch
+// ---- the isosurface as an indexed triangle mesh (mesh_kernels.hip): marching tetrahedra, one block per 8^3 brick; without
+// CLWH_MESH_DENSE the dilated table says which bricks the surface can touch
 struct MeshArgs {
-  const int16_t *bricks;
-  const uint32_t *table;   // the projections' {min, max} table (not read by the mesher)
-  const uint32_t *dilated; // as IsoArgs::dilated; read when `skip` is set
-  const uint32_t *coarse;  // as IsoArgs::coarse (not read by the mesher)
-  int32_t X, Y, Z, NBX, NBY, CNX, CNY;
+  ViewVolume vol;          // `dilated` is read when `skip` is set
   uint64_t n_bricks;       // NBX * NBY * NBZ: the grid of every launch
   int32_t lo[3], hi[3];    // the box in grid points, lo < hi <= dim - 1 on every axis
   int64_t threshold;       // T = floor(iso * 2^24)

@@ -1,0 +1,273 @@
+// clwh_views.hip -- the image views of the volume on the host: clwh_render_projection (intensity projections), clwh_render_composite
+// (compositing through a colour/opacity table), clwh_render_isosurface (the isosurface of the trilinear field) and clwh_render_slice
+// (its oblique slices and slabs).  All read the same bricked copy of the volume (ensure_projection_data), as does the mesher
+// (clwh_mesh.hip).  The kernels are in projection_kernels.hip, composite_kernels.hip, isosurface_kernels.hip and slice_kernels.hip.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "clwh_host.hpp"
+
+using namespace clvr;
+
+// the volume in brick order + the per-brick {min, max} table, rebuilt when the key (device pointer, shared content version, dims)
+// changes -- the dims are part of it, so two wraps of one pointer with permuted dims never share a layout
+int clvr::ensure_projection_data(clwh_ctx *ctx, const clwh_mem *volume, ViewVolume &v) {
+  ProjectionData &p = ctx->proj;
+  v.X = (int32_t)volume->dims[0]; v.Y = (int32_t)volume->dims[1]; v.Z = (int32_t)volume->dims[2];
+  v.NBX = (v.X + 7) / 8; v.NBY = (v.Y + 7) / 8; v.NBZ = (v.Z + 7) / 8;
+  v.CNX = (v.NBX + 3) / 4; v.CNY = (v.NBY + 3) / 4;
+  const size_t n_bricks = (size_t)v.NBX * v.NBY * v.NBZ;
+  const size_t off_table = n_bricks * 512u * sizeof(int16_t);
+  const size_t bytes = off_table + n_bricks * sizeof(uint32_t);
+  const bool same = p.valid && p.vol == volume->dptr && p.vol_ver == volume->version() &&
+                    p.dims[0] == volume->dims[0] && p.dims[1] == volume->dims[1] && p.dims[2] == volume->dims[2];
+  if (!same) {
+    p.valid = p.dilated_valid = false;  // (the dilated table is derived from this copy)
+    CLWH_TRY(p.data.reserve(ctx->stream, bytes));
+    ProjRepackArgs r;
+    r.volume = (const int16_t *)volume->dptr;
+    r.X = v.X; r.Y = v.Y; r.Z = v.Z;
+    r.NBX = v.NBX; r.NBY = v.NBY; r.NBZ = v.NBZ;
+    r.bricks = p.data.as<int16_t>();
+    r.table = reinterpret_cast<uint32_t *>(p.data.as<uint8_t>() + off_table);
+    HIP_TRY(launch_proj_repack(r, ctx->stream));
+    p.valid = true;
+    p.vol = volume->dptr;
+    p.vol_ver = volume->version();
+    for (int q = 0; q < 3; ++q) p.dims[q] = volume->dims[q];
+  }
+  v.bricks = p.data.as<int16_t>();
+  v.table = reinterpret_cast<const uint32_t *>(p.data.as<uint8_t>() + off_table);
+  return CLWH_OK;
+}
+
+// the {min, max} table of the bricks dilated by one voxel and, behind it, of the cells of 4^3 bricks, built from the bricked copy
+// (which ensure_projection_data has just made current: a rebuild of the copy has cleared dilated_valid) by the first call of a
+// volume content that may skip by it
+int clvr::ensure_dilated_table(clwh_ctx *ctx, ViewVolume &v) {
+  ProjectionData &p = ctx->proj;
+  const size_t n_bricks = (size_t)v.NBX * v.NBY * v.NBZ, n_cells = (size_t)v.CNX * v.CNY * ((v.NBZ + 3) / 4);
+  if (!p.dilated_valid) {
+    CLWH_TRY(p.dilated.reserve(ctx->stream, (n_bricks + n_cells) * sizeof(uint32_t)));
+    HIP_TRY(launch_iso_dilate(v, p.dilated.as<uint32_t>(), ctx->stream));
+    p.dilated_valid = true;
+  }
+  v.dilated = p.dilated.as<uint32_t>();
+  v.coarse = v.dilated + n_bricks;
+  return CLWH_OK;
+}
+
+// ---- what the entry points check alike, by the status a failure returns: every CLWH_ERR_INVALID_VALUE condition of an entry point is
+// decided before any CLWH_ERR_BAD_NDRANGE condition, and those before any CLWH_ERR_SIZE_MISMATCH
+
+// (value) the frame and the volume are images of the kinds the views read and write
+static bool view_images_ok(const clwh_mem *frame, const clwh_mem *volume) {
+  return is_image(frame, 2, 4, CLWH_ELEM_U8) && is_image(volume, 3, 1, CLWH_ELEM_S16) && dims_fit_int32(volume);
+}
+// (ndrange) the launched region: whole tiles, 16-bit, inside the frame
+static bool view_region_ok(const clwh_mem *frame, uint32_t width, uint32_t height) {
+  return launch_size_ok(width, height) && width <= 65535u && height <= 65535u && width <= frame->dims[0] && height <= frame->dims[1];
+}
+// (size) an optional output holds `bytes`
+static bool holds(const clwh_mem *m, size_t bytes) { return !m || m->bytes >= bytes; }
+
+// distance from the camera to the farthest corner of the volume's box (infinite for an infinite camera)
+static double farthest_corner(const clwh_mem *volume, const float cam_pos[3]) {
+  double far = 0.0;
+  for (int c = 0; c < 8; ++c) {
+    double s2 = 0.0;
+    for (int q = 0; q < 3; ++q) {
+      const double corner = (c >> q) & 1 ? (double)volume->dims[q] : 0.0;
+      s2 += (corner - (double)cam_pos[q]) * (corner - (double)cam_pos[q]);
+    }
+    far = std::max(far, std::sqrt(s2));
+  }
+  return far;
+}
+// (value) the camera and the march.  Every kept sample lies in the volume's box, at most `far` from the camera: k < 2^30 once
+// far / step < 2^29 (|d| = 1 within float rounding), which bounds the kernels' 32-bit sample indices (ViewCamera::k_cap); false for an
+// infinite camera.  std::max in farthest_corner drops a NaN distance, so a NaN camera position passes that test: the compositor and
+// the isosurface refuse it by name (finite_camera), the projections accept it and find no kept sample (include/clwh.h).
+static bool view_march_ok(const clwh_mem *volume, const float cam_pos[3], float step, float t_near, float t_far, bool finite_camera) {
+  if (!(std::isfinite(step) && step > 0.0f)) return false;
+  if (!(t_near <= t_far) || t_near == INFINITY) return false;  // (false for NaN)
+  if (finite_camera && !(std::isfinite(cam_pos[0]) && std::isfinite(cam_pos[1]) && std::isfinite(cam_pos[2]))) return false;
+  return farthest_corner(volume, cam_pos) / (double)step < 536870912.0;
+}
+
+static ViewFrame view_frame(const clwh_mem *frame, uint32_t width, uint32_t height) {
+  ViewFrame f;
+  f.frame = (uint32_t *)frame->dptr;
+  f.frame_w = (int32_t)frame->dims[0];
+  f.frame_h = (int32_t)frame->dims[1];
+  f.launch_w = (int32_t)width;
+  f.launch_h = (int32_t)height;
+  f.tiles_x = f.launch_w / 8;
+  f.num_tiles = f.tiles_x * (f.launch_h / 8);
+  return f;
+}
+static ViewCamera view_camera(const float cam_pos[3], const float cam_dir[3], float step, float t_near, float t_far) {
+  ViewCamera c;
+  for (int q = 0; q < 3; ++q) {
+    c.cam_pos[q] = cam_pos[q];
+    c.cam_dir[q] = cam_dir[q];
+  }
+  c.step = step;
+  c.t_near = t_near;
+  c.t_far = t_far;
+  c.k_cap = 1 << 30;
+  return c;
+}
+template <class T>
+static T *optional_output(const clwh_mem *m) { return m ? (T *)m->dptr : nullptr; }
+
+extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc *d) {
+  if (!ctx || !d || !view_images_ok(d->frame, d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if (d->mode != CLWH_PROJ_MAX && d->mode != CLWH_PROJ_MIN && d->mode != CLWH_PROJ_MEAN) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_PROJ_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/false)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (!holds(d->values, out_bytes) || !holds(d->t_extreme, out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  ProjArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a.vol));
+  a.fr = view_frame(d->frame, d->width, d->height);
+  a.cam = view_camera(d->cam_pos, d->cam_dir, d->step, d->t_near, d->t_far);
+  a.window_center = d->window_center;
+  a.window_width = d->window_width;
+  a.values = optional_output<float>(d->values);
+  a.t_extreme = optional_output<float>(d->t_extreme);
+  HIP_TRY(launch_projection(a, d->mode, (d->flags & CLWH_PROJ_DENSE) != 0, ctx->stream));
+  return CLWH_OK;
+}
+
+// the prefix count of "a > 0" over the table, rebuilt when the key (device pointer, shared content version, length) changes
+static int ensure_lut_prefix(clwh_ctx *ctx, const clwh_mem *lut, int32_t lut_len, CompArgs &a) {
+  ProjectionData &p = ctx->proj;
+  const bool same = p.lut_valid && p.lut == lut->dptr && p.lut_ver == lut->version() && p.lut_len == lut_len;
+  if (!same) {
+    p.lut_valid = false;
+    CLWH_TRY(p.lut_prefix.reserve(ctx->stream, (size_t)lut_len * sizeof(uint32_t)));
+    HIP_TRY(launch_comp_prefix((const float4 *)lut->dptr, lut_len, p.lut_prefix.as<uint32_t>(), ctx->stream));
+    p.lut_valid = true;
+    p.lut = lut->dptr;
+    p.lut_ver = lut->version();
+    p.lut_len = lut_len;
+  }
+  a.prefix = p.lut_prefix.as<uint32_t>();
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *d) {
+  if (!ctx || !d || !view_images_ok(d->frame, d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if (!d->lut || !d->lut->dptr || (reinterpret_cast<uintptr_t>(d->lut->dptr) & 15u) != 0u) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~(CLWH_COMP_DENSE | CLWH_COMP_SHADE)) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->lut_len < 1 || d->lut_len > 65536 || d->lut_first < -65536 || d->lut_first > 65535) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->alpha_stop > 0.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN; +inf never stops early)
+  const bool shade = (d->flags & CLWH_COMP_SHADE) != 0;
+  if (shade && !(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (d->lut->bytes < (size_t)d->lut_len * 16u) return CLWH_ERR_SIZE_MISMATCH;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (!holds(d->rgba, 4u * out_bytes) || !holds(d->t_first, out_bytes) || !holds(d->t_stop, out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  CompArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a.vol));
+  CLWH_TRY(ensure_lut_prefix(ctx, d->lut, d->lut_len, a));
+  a.fr = view_frame(d->frame, d->width, d->height);
+  a.cam = view_camera(d->cam_pos, d->cam_dir, d->step, d->t_near, d->t_far);
+  a.lut = (const float4 *)d->lut->dptr;
+  a.lut_first = d->lut_first;
+  a.lut_len = d->lut_len;
+  a.alpha_stop = d->alpha_stop;
+  a.ambient = d->ambient;
+  a.rgba = optional_output<float4>(d->rgba);
+  a.t_first = optional_output<float>(d->t_first);
+  a.t_stop = optional_output<float>(d->t_stop);
+  HIP_TRY(launch_composite(a, shade, (d->flags & CLWH_COMP_DENSE) != 0, ctx->stream));
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc *d) {
+  if (!ctx || !d || !view_images_ok(d->frame, d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~(CLWH_ISO_DENSE | CLWH_ISO_BELOW)) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->iso) && std::fabs(d->iso) <= 65536.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (d->refine < 0 || d->refine > 24) return CLWH_ERR_INVALID_VALUE;
+  if (!(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
+  if (!(std::isfinite(d->color[0]) && std::isfinite(d->color[1]) && std::isfinite(d->color[2]))) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (!holds(d->t_hit, out_bytes) || !holds(d->normal, 4u * out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  IsoArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a.vol));
+  CLWH_TRY(ensure_dilated_table(ctx, a.vol));
+  const bool dense = (d->flags & CLWH_ISO_DENSE) != 0, below = (d->flags & CLWH_ISO_BELOW) != 0;
+  a.fr = view_frame(d->frame, d->width, d->height);
+  a.cam = view_camera(d->cam_pos, d->cam_dir, d->step, d->t_near, d->t_far);
+  for (int q = 0; q < 3; ++q) a.color[q] = d->color[q];
+  // T = floor(iso * 2^24): the product is exact in binary64 (24 significant bits, |.| <= 2^40)
+  a.threshold = (int64_t)std::floor((double)d->iso * 16777216.0);
+  // dmax * 2^24 < T  <=>  dmax < ceil(T / 2^24);  dmin * 2^24 > T  <=>  dmin > floor(T / 2^24)  (>> of a negative int64 is arithmetic)
+  a.skip_bound = below ? (int32_t)(a.threshold >> 24) : (int32_t)(-((-a.threshold) >> 24));
+  a.refine = d->refine;
+  a.ambient = d->ambient;
+  a.t_hit = optional_output<float>(d->t_hit);
+  a.normal = optional_output<float4>(d->normal);
+  HIP_TRY(launch_isosurface(a, below, dense, ctx->stream));
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *d) {
+  if (!ctx || !d || !view_images_ok(d->frame, d->volume)) return CLWH_ERR_INVALID_VALUE;
+  if (d->mode != CLWH_SLICE_MAX && d->mode != CLWH_SLICE_MIN && d->mode != CLWH_SLICE_MEAN) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_SLICE_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->slab_samples < 1 || d->slab_samples > 8192) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  for (int q = 0; q < 3; ++q) {
+    if (!(std::isfinite(d->origin[q]) && std::isfinite(d->du[q]) && std::isfinite(d->dv[q]) && std::isfinite(d->normal[q]))) return CLWH_ERR_INVALID_VALUE;
+    // how far any sample of the region can lie from 0 on this axis: below 2^30 every coordinate is finite and converts to int32
+    const double reach = std::fabs((double)d->origin[q]) + (d->width ? (double)d->width - 1.0 : 0.0) * std::fabs((double)d->du[q]) +
+                         (d->height ? (double)d->height - 1.0 : 0.0) * std::fabs((double)d->dv[q]) +
+                         (double)(d->slab_samples - 1) * (double)d->step * std::fabs((double)d->normal[q]);
+    if (!(reach < 1073741824.0)) return CLWH_ERR_INVALID_VALUE;
+  }
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (!holds(d->values, out_bytes) || !holds(d->t_extreme, out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  SliceArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a.vol));
+  const bool dense = (d->flags & CLWH_SLICE_DENSE) != 0 || d->mode == CLWH_SLICE_MEAN;  // MEAN reads every kept sample
+  if (!dense) CLWH_TRY(ensure_dilated_table(ctx, a.vol));
+  a.use_coarse = ctx->tune.slice_coarse;
+  a.fr = view_frame(d->frame, d->width, d->height);
+  for (int q = 0; q < 3; ++q) {
+    a.origin[q] = d->origin[q];
+    a.du[q] = d->du[q];
+    a.dv[q] = d->dv[q];
+    a.normal[q] = d->normal[q];
+  }
+  a.step = d->step;
+  a.window_center = d->window_center;
+  a.window_width = d->window_width;
+  a.slab_samples = d->slab_samples;
+  a.values = optional_output<float>(d->values);
+  a.t_extreme = optional_output<float>(d->t_extreme);
+  HIP_TRY(launch_slice(a, d->mode, dense, ctx->stream));
+  return CLWH_OK;
+}

@@ -21,8 +21,7 @@
 // same order because an unvisited brick and a visited one without a crossing both count zero.
 #include <rocprim/device/device_scan.hpp>
 
-#include "packed_volume.hpp"
-#include "clwh_internal.hpp"
+#include "view_device.hpp"
 
 namespace clvr {
 
@@ -48,8 +47,8 @@ __device__ __forceinline__ bool mesh_brick_active(const MeshArgs &a, size_t bric
   // its grid points [8 b, 8 b + 7] meet the box [lo, hi] on every axis
   if (bx * 8 > a.hi[0] || bx * 8 + 7 < a.lo[0] || by * 8 > a.hi[1] || by * 8 + 7 < a.lo[1] || bz * 8 > a.hi[2] || bz * 8 + 7 < a.lo[2]) return false;
   if (a.skip) {  // a crossing needs a value inside and a value outside within one voxel of the brick
-    const uint32_t mm = a.dilated[brick];
-    const int dmin = (int)(int16_t)(mm & 0xFFFFu), dmax = (int)(int16_t)(mm >> 16);
+    const uint32_t mm = a.vol.dilated[brick];
+    const int dmin = table_min(mm), dmax = table_max(mm);
     return a.below ? (dmin <= a.in_bound && dmax > a.in_bound) : (dmin < a.in_bound && dmax >= a.in_bound);
   }
   return true;
@@ -61,7 +60,7 @@ __device__ __forceinline__ void mesh_stage(const MeshArgs &a, int bx, int by, in
   for (unsigned i = threadIdx.x; i < 729u; i += 512u) {
     const int x = bx * 8 + (int)(i % 9u), y = by * 8 + (int)((i / 9u) % 9u), z = bz * 8 + (int)(i / 81u);
     int v = 0;  // past the volume: never an end of an edge of the box (hi <= dim - 1)
-    if (x < a.X && y < a.Y && z < a.Z) v = a.bricks[VolumePacked::record_index(x, y, z, a.NBX, a.NBY)];
+    if (x < a.vol.X && y < a.vol.Y && z < a.vol.Z) v = a.vol.bricks[VolumePacked::record_index(x, y, z, a.vol.NBX, a.vol.NBY)];
     s_val[i] = v;
   }
   __syncthreads();
@@ -136,9 +135,9 @@ __device__ __forceinline__ uint32_t mesh_block_scan(uint32_t v, uint32_t *s_wave
 }
 
 __device__ __forceinline__ void mesh_brick_coords(const MeshArgs &a, size_t brick, int &bx, int &by, int &bz) {
-  bx = (int)(brick % (size_t)a.NBX);
-  by = (int)((brick / (size_t)a.NBX) % (size_t)a.NBY);
-  bz = (int)(brick / ((size_t)a.NBX * (size_t)a.NBY));
+  bx = (int)(brick % (size_t)a.vol.NBX);
+  by = (int)((brick / (size_t)a.vol.NBX) % (size_t)a.vol.NBY);
+  bz = (int)(brick / ((size_t)a.vol.NBX * (size_t)a.vol.NBY));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -161,14 +160,6 @@ __global__ __launch_bounds__(512) void k_mesh_count(const MeshArgs a) {
     a.counts[2u * n1 + brick] = (total & 0xFFFFu) ? 1u : 0u;
     if (brick == 0u) a.counts[a.n_bricks] = a.counts[n1 + a.n_bricks] = a.counts[2u * n1 + a.n_bricks] = 0u;  // the scans' last element: the totals
   }
-}
-
-// g_c(R): the clamped central differences of the isosurface's normal
-__device__ __forceinline__ void mesh_gradient(const MeshArgs &a, int x, int y, int z, int &gx, int &gy, int &gz) {
-  const int xm = max(x - 1, 0), xp = min(x + 1, a.X - 1), ym = max(y - 1, 0), yp = min(y + 1, a.Y - 1), zm = max(z - 1, 0), zp = min(z + 1, a.Z - 1);
-  gx = (int)a.bricks[VolumePacked::record_index(xp, y, z, a.NBX, a.NBY)] - (int)a.bricks[VolumePacked::record_index(xm, y, z, a.NBX, a.NBY)];
-  gy = (int)a.bricks[VolumePacked::record_index(x, yp, z, a.NBX, a.NBY)] - (int)a.bricks[VolumePacked::record_index(x, ym, z, a.NBX, a.NBY)];
-  gz = (int)a.bricks[VolumePacked::record_index(x, y, zp, a.NBX, a.NBY)] - (int)a.bricks[VolumePacked::record_index(x, y, zm, a.NBX, a.NBY)];
 }
 
 __global__ __launch_bounds__(512) void k_mesh_vertices(const MeshArgs a) {
@@ -200,14 +191,14 @@ __global__ __launch_bounds__(512) void k_mesh_vertices(const MeshArgs a) {
     a.positions[3u * o + 0u] = (float)(double)Fx * 1.52587890625e-05f;
     a.positions[3u * o + 1u] = (float)(double)Fy * 1.52587890625e-05f;
     a.positions[3u * o + 2u] = (float)(double)Fz * 1.52587890625e-05f;
-    if (a.keys) a.keys[o] = (((uint64_t)p.z * (uint64_t)a.Y + (uint64_t)p.y) * (uint64_t)a.X + (uint64_t)p.x) * 8u + (uint64_t)dir;
+    if (a.keys) a.keys[o] = (((uint64_t)p.z * (uint64_t)a.vol.Y + (uint64_t)p.y) * (uint64_t)a.vol.X + (uint64_t)p.x) * 8u + (uint64_t)dir;
     if (a.normals) {
       int px, py, pz, qx, qy, qz;
-      mesh_gradient(a, p.x, p.y, p.z, px, py, pz);
-      mesh_gradient(a, p.x + dx, p.y + dy, p.z + dz, qx, qy, qz);
+      central_difference(a.vol, p.x, p.y, p.z, px, py, pz);  // g_c(R): the isosurface's
+      central_difference(a.vol, p.x + dx, p.y + dy, p.z + dz, qx, qy, qz);
       const long long Gx = (65536 - w) * px + w * qx, Gy = (65536 - w) * py + w * qy, Gz = (65536 - w) * pz + w * qz;
       const float gx = (float)(double)Gx, gy = (float)(double)Gy, gz = (float)(double)Gz;
-      const float l2 = (gx * gx + gy * gy) + gz * gz;
+      const float l2 = length2(gx, gy, gz);
       float nx = 0.0f, ny = 0.0f, nz = 0.0f;
       if (l2 > 0.0f) {
         const float len = sqrtf(l2);
@@ -244,7 +235,7 @@ __global__ __launch_bounds__(512) void k_mesh_triangles(const MeshArgs a) {
       for (uint32_t v = 0; v < 3u; ++v, word >>= 4) {
         const uint32_t lo = (corners >> (3u * (word & 3u))) & 7u, dir = ((corners >> (3u * ((word >> 2) & 3u))) & 7u) ^ lo;  // the edge's lower end P' = P + lo owns it
         const int x = p.x + (int)(lo & 1u), y = p.y + (int)((lo >> 1) & 1u), z = p.z + (int)(lo >> 2);
-        const size_t owner = ((size_t)(z >> 3) * (size_t)a.NBY + (size_t)(y >> 3)) * (size_t)a.NBX + (size_t)(x >> 3);
+        const size_t owner = brick_index(a.vol, x >> 3, y >> 3, z >> 3);
         const uint32_t rec = a.points[(size_t)a.bases[2u * n1 + owner] * 512u + (size_t)(((z & 7) * 8 + (y & 7)) * 8 + (x & 7))];
         a.triangles[3u * o + v] = (uint32_t)(a.bases[owner] + (uint64_t)(rec >> 8) + (uint64_t)__popc(rec & ((1u << (dir - 1u)) - 1u)));
       }

@@ -1,15 +1,15 @@
 // projection_kernels.hip -- maximum / minimum / mean intensity projections of the caller's S16 image (clwh_render_projection).
 //
-// The exact sample set of a ray and the brick walk over it are in projection_device.hpp (shared with composite_kernels.hip).
+// The pixel mapping, the exact sample set of a ray and the brick walk over it are in view_device.hpp, shared by all the views.
 //
 //   k_proj_repack            the caller's image -> brick order (packed_volume.hpp inner_index: one 4^3 sub-brick of int16 = one 128-byte
 //                            line) + a {min, max} pair per 8^3 brick over its real voxels
-//   k_projection<MODE, SKIP> one wave per 8x8 pixel tile, tiles in XCD-contiguous order (as k_primary); each lane walks its ray's kept
-//                            range brick by brick.  SKIP (MAX / MIN without CLWH_PROJ_DENSE): a brick whose table entry cannot beat the
+//   k_projection<MODE, SKIP> one wave per 8x8 pixel tile (view_pixel); each lane walks its ray's kept range brick by brick
+//                            (walk_bricks).  SKIP (MAX / MIN without CLWH_PROJ_DENSE): a brick whose table entry cannot beat the
 //                            running extreme -- max <= best for MAX, min >= best for MIN -- is stepped over without reading it.  A tie
 //                            cannot move t_extreme (the first sample that attains the extreme wins and the walk runs front to back), so
 //                            the result is bit-identical to the dense walk.
-#include "projection_device.hpp"
+#include "view_device.hpp"
 
 namespace clvr {
 
@@ -74,8 +74,7 @@ __global__ __launch_bounds__(256) void k_proj_repack(const ProjRepackArgs a) {
         lo = s_lo[tid][s] < lo ? s_lo[tid][s] : lo;
         hi = s_hi[tid][s] < hi ? s_hi[tid][s] : hi;
       }
-      const int vmin = (int)lo - 32768, vmax = 32767 - (int)hi;
-      a.table[brick_row + (size_t)bx] = (uint32_t)(uint16_t)vmin | ((uint32_t)(uint16_t)vmax << 16);
+      a.table[brick_row + (size_t)bx] = pack_min_max((int)lo - 32768, 32767 - (int)hi);
     }
   }
 }
@@ -84,15 +83,9 @@ enum : int { PROJ_MAX = CLWH_PROJ_MAX, PROJ_MIN = CLWH_PROJ_MIN, PROJ_MEAN = CLW
 
 template <int MODE, bool SKIP>
 __global__ __launch_bounds__(64) void k_projection(const ProjArgs a) {
-  const uint32_t slot = xcd_contiguous_slot(blockIdx.x, (uint32_t)a.num_tiles);
-  const uint32_t tx = slot % (uint32_t)a.tiles_x, ty = slot / (uint32_t)a.tiles_x;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
-
-  const f3 cam_o = f3{a.cam_pos[0], a.cam_pos[1], a.cam_pos[2]};
-  const f3 cam_d = f3{a.cam_dir[0], a.cam_dir[1], a.cam_dir[2]};
-  const Ray ray = generate_ray(cam_o, cam_d, (int)x, (int)y, a.frame_w, a.frame_h);
-  const ProjRay r{ray.origin, ray.direction, a.step, a.t_near, a.t_far, (float)a.X, (float)a.Y, (float)a.Z};
+  uint32_t x, y;
+  view_pixel(a.fr, x, y);
+  const ProjRay r = camera_ray(a.cam, a.vol, a.fr, x, y);
 
   constexpr int kNone = MODE == PROJ_MAX ? -32769 : 32768;  // beyond int16: no sample yet
   int best = kNone;
@@ -100,35 +93,34 @@ __global__ __launch_bounds__(64) void k_projection(const ProjArgs a) {
   long long sum = 0;
   int count = 0;
   int k, kb;
-  if (proj_kept_range(r, a.k_cap, k, kb)) {
-    while (k <= kb) {  // one brick per iteration, front to back
-      float t;
-      const f3 p = proj_sample(r, k, t);  // kept: 0 <= p < dim, so the conversions are floors
-      const unsigned bx = (unsigned)(int)p.x >> 3, by = (unsigned)(int)p.y >> 3, bz = (unsigned)(int)p.z >> 3;
-      const size_t brick = ((size_t)bz * (size_t)a.NBY + (size_t)by) * (size_t)a.NBX + (size_t)bx;
-      const int k_end = proj_brick_exit(r, k, kb, bx, by, bz, a.k_cap);
-      bool skip = false;
-      if constexpr (SKIP) {
-        const uint32_t mm = a.table[brick];
-        skip = MODE == PROJ_MAX ? (int)(int16_t)(mm >> 16) <= best : (int)(int16_t)(mm & 0xFFFFu) >= best;
-      }
-      if (!skip) {
-        const int16_t *__restrict__ b = a.bricks + (brick << 9);
-        for (int j = k; j < k_end; ++j) {
-          float tj;
-          const f3 q = proj_sample(r, j, tj);
-          const int v = b[VolumePacked::inner_index((unsigned)(int)q.x, (unsigned)(int)q.y, (unsigned)(int)q.z)];
-          if constexpr (MODE == PROJ_MEAN) {
-            sum += v;
-            count += 1;
-          } else if (MODE == PROJ_MAX ? v > best : v < best) {  // strict: the first sample attaining the extreme keeps its t
-            best = v;
-            best_t = tj;
+  if (proj_kept_range(r, a.cam.k_cap, k, kb)) {
+    walk_bricks(
+        r, a.vol, k, kb, a.cam.k_cap, NeverSkip{},
+        [&](size_t brick) {
+          if constexpr (SKIP) {
+            const uint32_t mm = a.vol.table[brick];
+            return MODE == PROJ_MAX ? table_max(mm) <= best : table_min(mm) >= best;
+          } else {
+            return false;
           }
-        }
-      }
-      k = k_end;
-    }
+        },
+        [&](size_t brick, int k0, int k_end) {
+          const int16_t *__restrict__ b = a.vol.bricks + (brick << 9);
+          for (int j = k0; j < k_end; ++j) {
+            float tj;
+            const f3 q = proj_sample(r, j, tj);
+            const int v = b[VolumePacked::inner_index((unsigned)(int)q.x, (unsigned)(int)q.y, (unsigned)(int)q.z)];
+            if constexpr (MODE == PROJ_MEAN) {
+              sum += v;
+              count += 1;
+            } else {
+              const bool better = MODE == PROJ_MAX ? v > best : v < best;  // strict: the first sample attaining the extreme keeps its t
+              best_t = better ? tj : best_t;
+              best = better ? v : best;
+            }
+          }
+          return false;
+        });
   }
   float value;
   if constexpr (MODE == PROJ_MEAN) {
@@ -137,16 +129,9 @@ __global__ __launch_bounds__(64) void k_projection(const ProjArgs a) {
   } else {
     value = best != kNone ? (float)best : __builtin_nanf("");
   }
-  uint32_t px = 0u;  // no kept sample: (0, 0, 0, 0)
-  if (value == value) {
-    const float u = ((value - a.window_center) / a.window_width + 0.5f) * 255.0f + 0.5f;
-    const uint32_t grey = (uint32_t)(int)fminf(fmaxf(u, 0.0f), 255.0f);
-    px = grey * 0x010101u | 0xFF000000u;
-  }
-  a.frame[(size_t)y * (size_t)a.frame_w + x] = px;
-  const size_t o = (size_t)y * (size_t)a.launch_w + x;
-  if (a.values) a.values[o] = value;
-  if (a.t_extreme) a.t_extreme[o] = best_t;
+  const size_t o = store_frame(a.fr, x, y, window_grey(value, a.window_center, a.window_width));
+  store_optional(a.values, o, value);
+  store_optional(a.t_extreme, o, best_t);
 }
 
 hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s) {
@@ -156,7 +141,7 @@ hipError_t launch_proj_repack(const ProjRepackArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_projection(const ProjArgs &a, int mode, bool dense, hipStream_t s) {
-  const dim3 grid((unsigned)a.num_tiles), block(64);
+  const dim3 grid((unsigned)a.fr.num_tiles), block(64);
   if (mode == PROJ_MEAN)
     hipLaunchKernelGGL((k_projection<PROJ_MEAN, false>), grid, block, 0, s, a);
   else if (mode == PROJ_MAX && dense)

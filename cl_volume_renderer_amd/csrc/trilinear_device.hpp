@@ -7,33 +7,11 @@
 // 128-byte line -- unless an axis sits at offset 3 of its sub-brick (58 % of the cells do); the eight indices are formed from per-axis
 // terms without a branch (iso_corners).  The x and y stages of the blend fit int32 (|.| <= 2^31 is reached only by -32768 everywhere);
 // the z stage is one 64-bit multiply-add.
-//
-// Beside it the walk's exit search for a cell of 4^3 bricks (iso_cell_exit): the kernels that bound S per brick by the dilated
-// {min, max} tables of k_iso_dilate / k_iso_coarse ask the cell's pair first.
 #pragma once
 
-#include "projection_device.hpp"
+#include "view_device.hpp"
 
 namespace clvr {
-
-// what the field reads: the bricked copy (k_proj_repack) and its grid
-struct FieldVolume {
-  const int16_t *bricks;
-  int X, Y, Z, NBX, NBY;
-};
-
-// proj_brick_exit for the box of a coarse cell (32^3 voxels)
-__device__ __forceinline__ int iso_cell_exit(const ProjRay &r, int k, int kb, unsigned cx, unsigned cy, unsigned cz, int k_cap) {
-  float tb = INFINITY;
-  if (r.d.x != 0.0f) tb = fminf(tb, ((float)((cx + (r.d.x > 0.0f ? 1u : 0u)) * 32u) - r.o.x) / r.d.x);
-  if (r.d.y != 0.0f) tb = fminf(tb, ((float)((cy + (r.d.y > 0.0f ? 1u : 0u)) * 32u) - r.o.y) / r.d.y);
-  if (r.d.z != 0.0f) tb = fminf(tb, ((float)((cz + (r.d.z > 0.0f ? 1u : 0u)) * 32u) - r.o.z) / r.d.z);
-  return first_false(k, kb, index_guess(floorf(tb / r.h) + 1.0f, k_cap), [&](int j) {
-    float tj;
-    const f3 q = proj_sample(r, j, tj);
-    return ((unsigned)(int)q.x >> 5) == cx && ((unsigned)(int)q.y >> 5) == cy && ((unsigned)(int)q.z >> 5) == cz;
-  });
-}
 
 // ------------------------------------------------------------------------------------------------
 // the field
@@ -57,7 +35,7 @@ struct IsoCorners {
   int v000, v100, v010, v110, v001, v101, v011, v111;
 };
 // the 8 corner values of a cell
-__device__ __forceinline__ IsoCorners iso_corners(const FieldVolume &a, const IsoCell &c) {
+__device__ __forceinline__ IsoCorners iso_corners(const ViewVolume &a, const IsoCell &c) {
   const int16_t *__restrict__ vb = a.bricks;
   IsoCorners v;
   // The brick index is separable (packed_volume.hpp): brick number = bx + by + bz, in-brick offset = ix | iy | iz, with per-axis terms.
@@ -88,7 +66,7 @@ __device__ __forceinline__ long long iso_blend(const IsoCorners &v, const IsoCel
   return (long long)b0 * (long long)(256 - c.wz) + (long long)b1 * (long long)c.wz;
 }
 // S(p) for a position inside the volume
-__device__ __forceinline__ long long iso_field(const FieldVolume &a, const f3 p) {
+__device__ __forceinline__ long long iso_field(const ViewVolume &a, const f3 p) {
   const IsoCell c = iso_cell(p);
   return iso_blend(iso_corners(a, c), c);
 }

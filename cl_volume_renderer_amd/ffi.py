@@ -241,6 +241,20 @@ def accum_len(w, h, world=1) -> int:
     return int(lib().clwh_accum_len(w, h, world))
 
 
+def _handle(mem):
+    """the handle of an optional Mem"""
+    return mem.h if mem is not None else None
+
+
+def _fill_view(d, frame, volume, cam_pos, cam_dir, width, height):
+    """what the camera views' descriptors share"""
+    d.frame, d.volume = frame.h, volume.h
+    for k in range(3):
+        d.cam_pos[k] = float(cam_pos[k])
+        d.cam_dir[k] = float(cam_dir[k])
+    d.width, d.height = int(width), int(height)
+
+
 class Mem:
     def __init__(self, ctx, handle, nbytes, dtype=None, shape=None):
         self.ctx, self.h, self.nbytes, self.dtype, self.shape = ctx, C.c_void_p(handle), nbytes, dtype, shape
@@ -426,16 +440,12 @@ class Context:
         """maximum / minimum / mean intensity projection of `volume` (S16) into `frame` (RGBA8) with clwh_render's camera rays;
         window = (center, width) maps the projected value to grey.  values / t_extreme: optional float32[height][width] buffers."""
         d = ProjectionDesc()
-        d.frame, d.volume = frame.h, volume.h
-        for k in range(3):
-            d.cam_pos[k] = float(cam_pos[k])
-            d.cam_dir[k] = float(cam_dir[k])
-        d.width, d.height = int(width), int(height)
+        _fill_view(d, frame, volume, cam_pos, cam_dir, width, height)
         d.mode, d.flags = int(mode), PROJ_DENSE if dense else 0
         d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
         d.window_center, d.window_width = float(window[0]), float(window[1])
-        d.values = values.h if values is not None else None
-        d.t_extreme = t_extreme.h if t_extreme is not None else None
+        d.values = _handle(values)
+        d.t_extreme = _handle(t_extreme)
         _check(lib().clwh_render_projection(self.h, C.byref(d)), "clwh_render_projection")
 
     def render_composite(self, frame: Mem, volume: Mem, cam_pos, cam_dir, width, height, lut: Mem, lut_first, lut_len=None, step=0.5,
@@ -445,20 +455,16 @@ class Context:
         value lut_first) into `frame` (RGBA8, premultiplied) with clwh_render's camera rays.  flags: COMP_DENSE | COMP_SHADE.
         rgba / t_first / t_stop: optional float32 buffers over the launched region.  lut_len defaults to the whole buffer."""
         d = CompositeDesc()
-        d.frame, d.volume = frame.h, volume.h
-        for k in range(3):
-            d.cam_pos[k] = float(cam_pos[k])
-            d.cam_dir[k] = float(cam_dir[k])
-        d.width, d.height = int(width), int(height)
+        _fill_view(d, frame, volume, cam_pos, cam_dir, width, height)
         d.flags = int(flags)
         d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
-        d.lut = lut.h if lut is not None else None
+        d.lut = _handle(lut)
         d.lut_first = int(lut_first)
         d.lut_len = int(lut_len if lut_len is not None else (lut.nbytes // 16 if lut is not None else 0))
         d.alpha_stop, d.ambient = float(alpha_stop), float(ambient)
-        d.rgba = rgba.h if rgba is not None else None
-        d.t_first = t_first.h if t_first is not None else None
-        d.t_stop = t_stop.h if t_stop is not None else None
+        d.rgba = _handle(rgba)
+        d.t_first = _handle(t_first)
+        d.t_stop = _handle(t_stop)
         _check(lib().clwh_render_composite(self.h, C.byref(d)), "clwh_render_composite")
 
     def render_isosurface(self, frame: Mem, volume: Mem, cam_pos, cam_dir, width, height, iso, step=0.5, refine=8, flags=0,
@@ -467,17 +473,14 @@ class Context:
         headlight, with clwh_render's camera rays.  flags: ISO_DENSE | ISO_BELOW.  t_hit (float32[height][width]) / normal
         (float32[height][width][4] = n, value at the hit): optional buffers over the launched region."""
         d = IsosurfaceDesc()
-        d.frame, d.volume = frame.h, volume.h
+        _fill_view(d, frame, volume, cam_pos, cam_dir, width, height)
         for k in range(3):
-            d.cam_pos[k] = float(cam_pos[k])
-            d.cam_dir[k] = float(cam_dir[k])
             d.color[k] = float(color[k])
-        d.width, d.height = int(width), int(height)
         d.flags = int(flags)
         d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
         d.iso, d.refine, d.ambient = float(iso), int(refine), float(ambient)
-        d.t_hit = t_hit.h if t_hit is not None else None
-        d.normal = normal.h if normal is not None else None
+        d.t_hit = _handle(t_hit)
+        d.normal = _handle(normal)
         _check(lib().clwh_render_isosurface(self.h, C.byref(d)), "clwh_render_isosurface")
 
     def render_slice(self, frame: Mem, volume: Mem, origin, du, dv, normal, width, height, mode=SLICE_MAX, slab_samples=1, step=0.5,
@@ -494,8 +497,8 @@ class Context:
         d.mode, d.flags = int(mode), int(flags)
         d.slab_samples, d.step = int(slab_samples), float(step)
         d.window_center, d.window_width = float(window[0]), float(window[1])
-        d.values = values.h if values is not None else None
-        d.t_extreme = t_extreme.h if t_extreme is not None else None
+        d.values = _handle(values)
+        d.t_extreme = _handle(t_extreme)
         _check(lib().clwh_render_slice(self.h, C.byref(d)), "clwh_render_slice")
 
     def mesh_isosurface_raw(self, volume: Mem, iso, flags=0, box=None, positions: Mem = None, normals: Mem = None, keys: Mem = None,
@@ -503,15 +506,15 @@ class Context:
         """one clwh_mesh_isosurface call: (status, n_vertices, n_triangles); nothing is raised.  box = ((lo), (hi)) in grid points."""
         d = MeshDesc()
         nv, nt = C.c_uint64(0), C.c_uint64(0)
-        d.volume = volume.h if volume is not None else None
+        d.volume = _handle(volume)
         d.iso, d.flags = float(iso), int(flags)
         if box is not None:
             for k in range(3):
                 d.box_lo[k], d.box_hi[k] = int(box[0][k]), int(box[1][k])
-        d.positions = positions.h if positions is not None else None
-        d.normals = normals.h if normals is not None else None
-        d.keys = keys.h if keys is not None else None
-        d.triangles = triangles.h if triangles is not None else None
+        d.positions = _handle(positions)
+        d.normals = _handle(normals)
+        d.keys = _handle(keys)
+        d.triangles = _handle(triangles)
         d.vertex_capacity, d.triangle_capacity = int(vertex_capacity), int(triangle_capacity)
         d.n_vertices, d.n_triangles = C.pointer(nv), C.pointer(nt)
         status = lib().clwh_mesh_isosurface(self.h, C.byref(d))

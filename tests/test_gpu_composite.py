@@ -13,51 +13,12 @@ import pytest
 from cl_volume_renderer_amd import ffi, scene
 from tests import composite_ref as cr
 from tests import projection_ref as pr
+from tests.view_helpers import ROOT, F, toward, image_of, pose as _pose, host_lib, Comp, Proj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 INVALID_VALUE, BAD_NDRANGE, SIZE_MISMATCH = 1, 8, 9
 LUT_FIRST = -1024
-
-
-class Comp:
-    """a frame + the optional outputs on one context"""
-
-    def __init__(self, ctx, frame_wh, region_wh):
-        self.ctx, self.frame_wh, self.region_wh = ctx, frame_wh, region_wh
-        fw, fh = frame_wh
-        w, h = region_wh
-        self.frame = ctx.image([fw, fh], 4, np.uint8, (fh, fw, 4))
-        self.rgba = ctx.buffer(w * h * 16, np.float32, (h, w, 4))
-        self.t_first = ctx.buffer(w * h * 4, np.float32, (h, w))
-        self.t_stop = ctx.buffer(w * h * 4, np.float32, (h, w))
-
-    def run(self, volume, pos, d, lut, lut_first, **kw):
-        fw, fh = self.frame_wh
-        self.frame.push(np.full((fh, fw, 4), 7, np.uint8))  # pixels outside the region keep this
-        self.ctx.render_composite(self.frame, volume, pos, d, self.region_wh[0], self.region_wh[1], lut, lut_first, rgba=self.rgba,
-                                  t_first=self.t_first, t_stop=self.t_stop, **kw)
-        frame = self.frame.pull()
-        w, h = self.region_wh
-        assert np.all(frame[h:] == 7) and np.all(frame[:, w:] == 7)
-        return frame[:h, :w], self.rgba.pull(), self.t_first.pull(), self.t_stop.pull()
-
-    def release(self):
-        for m in (self.frame, self.rgba, self.t_first, self.t_stop):
-            m.release()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _check(got, want, what=""):
-    assert np.array_equal(got[0], want[0]), "frame differs %s: %d pixels" % (what, int((got[0] != want[0]).any(axis=-1).sum()))
-    for name, g, w in zip(("rgba", "t_first", "t_stop"), got[1:4], want[1:4]):
-        bad = _bits(g) != _bits(w)
-        assert not bad.any(), "%s differs %s: %d values, first at %s" % (name, what, int(bad.sum()), tuple(np.argwhere(bad)[0]))
 
 
 class Tally:
@@ -82,25 +43,17 @@ class Tally:
         assert self.terminated > 0 and self.partial > 0 and self.transparent_with_samples > 0, vars(self)
 
 
-def _image_of(ctx, vol):
-    Z, Y, X = vol.shape
-    if X > 1:
-        return ctx.image_from(vol), None
-    owner = ctx.buffer_from(vol)  # (clwh_image_create refuses a width of 1, as clw_image does; a wrap takes any dims)
-    return ctx.image_wrap(owner.device_ptr, (X, Y, Z), 1, np.int16), owner
-
-
 def _compare(ctx, vol, pos, d, frame_wh, region_wh, table, lut_first=LUT_FIRST, tally=None, flag_sets=(0, cr.SHADE), step=0.5,
              alpha_stop=0.95, ambient=0.3, t_near=0.0, t_far=np.inf):
     """reference == skipping walk == dense walk, for every set of flags"""
-    volume, owner = _image_of(ctx, vol)
+    volume, owner = image_of(ctx, vol)
     lut = ctx.buffer_from(np.ascontiguousarray(table, F))
     c = Comp(ctx, frame_wh, region_wh)
     kw = dict(step=step, alpha_stop=alpha_stop, ambient=ambient, t_near=t_near, t_far=t_far)
     for flags in flag_sets:
         want = cr.composite(vol, pos, d, frame_wh, region_wh, table, lut_first, flags=flags, **kw)
-        _check(c.run(volume, pos, d, lut, lut_first, flags=flags, **kw), want, "skipping, flags %d" % flags)
-        _check(c.run(volume, pos, d, lut, lut_first, flags=flags | cr.DENSE, **kw), want, "dense, flags %d" % flags)
+        Comp.check(c.run(volume, pos, d, lut, lut_first, flags=flags, **kw), want, "skipping, flags %d" % flags)
+        Comp.check(c.run(volume, pos, d, lut, lut_first, flags=flags | cr.DENSE, **kw), want, "dense, flags %d" % flags)
         if tally is not None:
             tally.add(want, alpha_stop)
     c.release()
@@ -108,24 +61,6 @@ def _compare(ctx, vol, pos, d, frame_wh, region_wh, table, lut_first=LUT_FIRST, 
     volume.release()
     if owner is not None:
         owner.release()
-
-
-def _toward(pos, target):
-    v = np.asarray(target, np.float64) - np.asarray(pos, np.float64)
-    return (v / np.linalg.norm(v)).astype(F)
-
-
-def _pose(name, dims):
-    X, Y, Z = dims
-    n = max(dims)
-    centre = np.array([(X - 1) / 2, (Y - 1) / 2, (Z - 1) / 2], F)
-    if name == "default":  # (aimed at the centre when the default direction would miss a flat or tiny volume)
-        pos, d = scene.default_camera(n)
-        return pos, (d if X == Y == Z and n >= 8 else _toward(pos, centre))
-    if name == "close":  # scene.close_camera about the centre of a box that need not be a cube
-        d = scene.camera_direction(0.9, 6.183)
-        return (centre - d * F(0.6 * n)).astype(F), d
-    return np.array([X * 0.45, Y * 0.55, Z * 0.5], F), scene.camera_direction(2.1, 0.4)
 
 
 @pytest.mark.parametrize("pose", ["default", "close", "inside"])
@@ -159,7 +94,7 @@ def test_axis_parallel_and_grazing_rays(gpu_ctx):
         "face_y0": (np.array([20.0, 0.0, -6.0], F), np.array([0, 0, 1], F)),          # central row runs in the face y = 0
         "edge_x0y0": (np.array([0.0, 0.0, -6.0], F), np.array([0, 0, 1], F)),        # central ray runs along an edge
         "face_xdim": (np.array([40.0, 12.0, -6.0], F), np.array([0, 0, 1], F)),      # x == X is outside
-        "diagonal": (np.array([-8.0, -8.0, -8.0], F), _toward((-8, -8, -8), (40, 24, 32))),
+        "diagonal": (np.array([-8.0, -8.0, -8.0], F), toward((-8, -8, -8), (40, 24, 32))),
         "straight_up": (np.array([20.0, -5.0, 16.0], F), np.array([0, 1, 0], F)),    # degenerate basis: NaN rays, nothing kept
     }
     tally = Tally()
@@ -251,7 +186,7 @@ def test_adversarial_volumes_skipping_equals_dense(gpu_ctx, name):
     vol, table = _adversarial_volumes()[name]
     Z, Y, X = vol.shape
     poses = [scene.default_camera(X), scene.close_camera(X),
-             (np.array([-10.0, -3.0, -10.0], F), _toward((-10, -3, -10), (X, 0, Z))),          # rays graze the far corner
+             (np.array([-10.0, -3.0, -10.0], F), toward((-10, -3, -10), (X, 0, Z))),          # rays graze the far corner
              (np.array([X + 5.0, Y * 0.5, Z * 0.5], F), np.array([-1, 0, 0], F)),
              (np.array([X * 0.5, Y * 0.5, Z * 0.5], F), scene.camera_direction(4.0, 0.3))]
     tally = Tally()
@@ -278,7 +213,7 @@ def test_derived_data_follows_tables_volumes_and_invalidation(gpu_ctx):
     def both(vol, table, what, through=None):
         for flags in (0, cr.SHADE):
             want = cr.composite(vol, pos, d, wh, wh, table, LUT_FIRST, flags=flags)
-            _check(c.run(through or volume, pos, d, lut, LUT_FIRST, flags=flags), want, what)
+            Comp.check(c.run(through or volume, pos, d, lut, LUT_FIRST, flags=flags), want, what)
             tally.add(want, 0.95)
 
     both(a, hard, "first")
@@ -294,7 +229,7 @@ def test_derived_data_follows_tables_volumes_and_invalidation(gpu_ctx):
     both(b, shell, "after invalidate")
     short = ctx.wrap(lut.device_ptr, 16 * 1500, np.float32)  # same pointer and content, shorter table: lut_len is part of the key
     want = cr.composite(b, pos, d, wh, wh, shell[:1500], LUT_FIRST)
-    _check(c.run(volume, pos, d, short, LUT_FIRST), want, "shorter table")
+    Comp.check(c.run(volume, pos, d, short, LUT_FIRST), want, "shorter table")
     lut.push(hard)
     both(b, hard, "after the last push")
     ctx.finish()
@@ -305,8 +240,6 @@ def test_derived_data_follows_tables_volumes_and_invalidation(gpu_ctx):
 
 
 def test_projections_and_composites_share_the_bricked_copy(gpu_ctx):
-    from tests.test_gpu_projection import Proj
-    from tests.test_gpu_projection import _check as check_projection
 
     ctx = gpu_ctx
     a = scene.phantom(48)
@@ -326,11 +259,11 @@ def test_projections_and_composites_share_the_bricked_copy(gpu_ctx):
         order = ("c", "p", "c") if round_ % 2 == 0 else ("p", "c", "p")  # whichever comes first builds the copy the other reads
         for what in order:
             if what == "c":
-                _check(c.run(volume, pos, d, lut, LUT_FIRST), want_c, "composite, round %d" % round_)
+                Comp.check(c.run(volume, pos, d, lut, LUT_FIRST), want_c, "composite, round %d" % round_)
                 tally.add(want_c, 0.95)
             else:
                 for mode in (pr.MAX, pr.MEAN):
-                    check_projection(p.run(volume, pos, d, mode, window=(0.0, 1000.0)), want_p[mode], "projection, round %d" % round_)
+                    Proj.check(p.run(volume, pos, d, mode, window=(0.0, 1000.0)), want_p[mode], "projection, round %d" % round_)
     ctx.finish()
     c.release()
     p.release()
@@ -369,7 +302,7 @@ def test_no_interference_with_the_path_tracer(gpu_ctx, orc):
         results.append((s.frame.pull(), s.cache.pull()))
         if composite:
             want = cr.composite(vol, pos, d, (128, 128), (128, 128), table, LUT_FIRST, flags=cr.SHADE)
-            _check(got, want)
+            Comp.check(got, want)
             tally.add(want, 0.95)
             c.release()
             lut.release()
@@ -446,8 +379,8 @@ def test_full_size_512(gpu_ctx, flags):
     rows = np.arange(0, H, 16)
     want = cr.composite(vol, pos, d, (1920, 1080), (W, H), table, LUT_FIRST, flags=flags, rows=rows)
     got = c.run(volume, pos, d, lut, LUT_FIRST, flags=flags)
-    _check(tuple(g[rows] for g in got), want, "skipping")
-    _check(c.run(volume, pos, d, lut, LUT_FIRST, flags=flags | cr.DENSE), got, "dense")
+    Comp.check(tuple(g[rows] for g in got), want, "skipping")
+    Comp.check(c.run(volume, pos, d, lut, LUT_FIRST, flags=flags | cr.DENSE), got, "dense")
     tally = Tally()
     tally.add(want, 0.95)
     tally.assert_all_three()
@@ -458,15 +391,8 @@ def test_full_size_512(gpu_ctx, flags):
 
 
 def _host_lib():
-    L = C.CDLL(os.path.join(ROOT, "cl_volume_renderer_amd", "libclvr_host.so"))
-    L.clvr_host_create.restype = C.c_void_p
-    L.clvr_host_destroy.argtypes = [C.c_void_p]
-    L.clvr_host_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
-    L.clvr_host_flush.argtypes = [C.c_void_p, C.c_char_p]
-    L.clvr_host_render_composite.restype = C.c_void_p
-    L.clvr_host_render_composite.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p,
-                                             C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float]
-    return L
+    return host_lib(clvr_host_render_composite=(C.c_void_p, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p,
+                                                             C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float]))
 
 
 def test_host_mirror_composite_equals_the_ffi_frame(gpu_ctx):

@@ -13,50 +13,12 @@ import pytest
 
 from cl_volume_renderer_amd import ffi, scene
 from tests import isosurface_ref as ir
+from tests.view_helpers import ROOT, F, toward, image_of, pose as _pose, plant_blocks, quiet_phantom, host_lib, Iso, Comp, Proj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 INVALID_VALUE, BAD_NDRANGE, SIZE_MISMATCH = 1, 8, 9
 FRAME, REGION = (64, 48), (56, 40)
-
-
-class Iso:
-    """a frame + the optional outputs on one context"""
-
-    def __init__(self, ctx, frame_wh, region_wh):
-        self.ctx, self.frame_wh, self.region_wh = ctx, frame_wh, region_wh
-        fw, fh = frame_wh
-        w, h = region_wh
-        self.frame = ctx.image([fw, fh], 4, np.uint8, (fh, fw, 4))
-        self.t_hit = ctx.buffer(w * h * 4, np.float32, (h, w))
-        self.normal = ctx.buffer(w * h * 16, np.float32, (h, w, 4))
-
-    def run(self, volume, pos, d, iso, **kw):
-        fw, fh = self.frame_wh
-        self.frame.push(np.full((fh, fw, 4), 7, np.uint8))  # pixels outside the region keep this
-        self.ctx.render_isosurface(self.frame, volume, pos, d, self.region_wh[0], self.region_wh[1], iso, t_hit=self.t_hit,
-                                   normal=self.normal, **kw)
-        frame = self.frame.pull()
-        w, h = self.region_wh
-        assert np.all(frame[h:] == 7) and np.all(frame[:, w:] == 7)
-        return frame[:h, :w], self.t_hit.pull(), self.normal.pull()
-
-    def release(self):
-        for m in (self.frame, self.t_hit, self.normal):
-            m.release()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _check(got, want, what=""):
-    assert np.array_equal(got[0], want[0]), "frame differs %s: %d pixels" % (what, int((got[0] != want[0]).any(axis=-1).sum()))
-    for name, g, w in zip(("t_hit", "normal"), got[1:3], want[1:3]):
-        bad = _bits(g) != _bits(w)
-        assert not bad.any(), "%s differs %s: %d values, first at %s" % (name, what, int(bad.sum()), tuple(np.argwhere(bad)[0]))
 
 
 class Tally:
@@ -79,14 +41,6 @@ class Tally:
         assert all(getattr(self, k) > 0 for k in self.KINDS) and self.comparisons > 0, vars(self)
 
 
-def _image_of(ctx, vol):
-    Z, Y, X = vol.shape
-    if X > 1:
-        return ctx.image_from(vol), None
-    owner = ctx.buffer_from(vol)  # (clwh_image_create refuses a width of 1, as clw_image does; a wrap takes any dims)
-    return ctx.image_wrap(owner.device_ptr, (X, Y, Z), 1, np.int16), owner
-
-
 def _case(vol, pos, d, iso, frame_wh=FRAME, region_wh=REGION, **kw):
     return dict(vol=vol, pos=pos, d=d, iso=iso, frame_wh=frame_wh, region_wh=region_wh, kw=kw)
 
@@ -103,7 +57,7 @@ def _run_family(ctx, cases):
     for c in cases:
         vol = c["vol"]
         if id(vol) not in images:
-            images[id(vol)] = _image_of(ctx, vol)
+            images[id(vol)] = image_of(ctx, vol)
         key = (c["frame_wh"], c["region_wh"])
         if key not in outputs:
             outputs[key] = Iso(ctx, *key)
@@ -112,8 +66,8 @@ def _run_family(ctx, cases):
         kw = dict(c["kw"])
         flags = kw.pop("flags", 0)
         what = "dims %s iso %r %r" % (vol.shape[::-1], c["iso"], c["kw"])
-        _check(out.run(volume, c["pos"], c["d"], c["iso"], flags=flags, **kw), want, "skipping, " + what)
-        _check(out.run(volume, c["pos"], c["d"], c["iso"], flags=flags | ir.DENSE, **kw), want, "dense, " + what)
+        Iso.check(out.run(volume, c["pos"], c["d"], c["iso"], flags=flags, **kw), want, "skipping, " + what)
+        Iso.check(out.run(volume, c["pos"], c["d"], c["iso"], flags=flags | ir.DENSE, **kw), want, "dense, " + what)
         tally.add(want)
     for out in outputs.values():
         out.release()
@@ -122,25 +76,6 @@ def _run_family(ctx, cases):
         if owner is not None:
             owner.release()
     return tally
-
-
-def _toward(pos, target):
-    v = np.asarray(target, np.float64) - np.asarray(pos, np.float64)
-    return (v / np.linalg.norm(v)).astype(F)
-
-
-def _pose(name, dims):
-    """the poses of tests/test_gpu_composite.py"""
-    X, Y, Z = dims
-    n = max(dims)
-    centre = np.array([(X - 1) / 2, (Y - 1) / 2, (Z - 1) / 2], F)
-    if name == "default":  # (aimed at the centre when the default direction would miss a flat or tiny volume)
-        pos, d = scene.default_camera(n)
-        return pos, (d if X == Y == Z and n >= 8 else _toward(pos, centre))
-    if name == "close":  # scene.close_camera about the centre of a box that need not be a cube
-        d = scene.camera_direction(0.9, 6.183)
-        return (centre - d * F(0.6 * n)).astype(F), d
-    return np.array([X * 0.45, Y * 0.55, Z * 0.5], F), scene.camera_direction(2.1, 0.4)
 
 
 PHANTOM_DIMS = [(64, 64, 64), (70, 33, 45), (130, 20, 9), (5, 4, 3), (1, 1, 1)]
@@ -166,24 +101,14 @@ def test_phantoms_from_several_poses(gpu_ctx, pose):
     _run_family(gpu_ctx, phantom_cases(pose)).assert_all()
 
 
-def _plant_blocks(vol):
-    """constant blocks on three faces of a random volume: a hit inside one has a zero gradient"""
-    Z, Y, X = vol.shape
-    vol[:6, :6, :6] = 32767
-    vol[Z - 6:, Y - 6:, X - 6:] = -32768
-    vol[Z // 2 - 3:Z // 2 + 3, :6, X - 6:] = 32767
-    vol[:6, Y - 6:, :6] = -32768
-    return vol
-
-
 def random_cases():
     rng = np.random.default_rng(2024)
     cases = []
     for dims in [(24, 24, 24), (17, 9, 33)]:
         X, Y, Z = dims
-        vol = _plant_blocks(rng.integers(0, 1 << 16, size=(Z, Y, X), dtype=np.uint16).view(np.int16))
-        poses = [(np.array([-7.0, -5.0, -9.0], F), _toward((-7.0, -5.0, -9.0), (X * 0.3, Y * 0.3, Z * 0.3))),
-                 (np.array([X + 6.0, Y + 4.0, Z + 8.0], F), _toward((X + 6.0, Y + 4.0, Z + 8.0), (X * 0.7, Y * 0.7, Z * 0.7))),
+        vol = plant_blocks(rng.integers(0, 1 << 16, size=(Z, Y, X), dtype=np.uint16).view(np.int16))
+        poses = [(np.array([-7.0, -5.0, -9.0], F), toward((-7.0, -5.0, -9.0), (X * 0.3, Y * 0.3, Z * 0.3))),
+                 (np.array([X + 6.0, Y + 4.0, Z + 8.0], F), toward((X + 6.0, Y + 4.0, Z + 8.0), (X * 0.7, Y * 0.7, Z * 0.7))),
                  _pose("inside", dims)]
         isos = [float(v) for v in rng.uniform(-30000, 30000, 3).astype(F)] + [32767.0, -32768.0, 25000.25, -25000.75]
         for i, (pos, d) in enumerate(poses):
@@ -198,15 +123,9 @@ def test_random_bit_volumes(gpu_ctx):
     _run_family(gpu_ctx, random_cases()).assert_all()
 
 
-def _quiet_phantom(n):
-    """the phantom without its noise: constant regions, so that hits inside them have a zero gradient"""
-    v = scene.phantom(n)
-    return np.where(v < -500, -1000, np.where(v < 500, 40, 900)).astype(np.int16)
-
-
 def slab_and_step_cases():
     n = 48
-    noisy, quiet = scene.phantom(n), _quiet_phantom(n)
+    noisy, quiet = scene.phantom(n), quiet_phantom(n)
     pos, d = scene.default_camera(n)
     centre = float(np.linalg.norm(np.array([(n - 1) / 2] * 3) - pos))
     cases = []
@@ -228,7 +147,7 @@ def test_steps_and_slabs_that_cut_the_surface(gpu_ctx):
 
 def axis_cases():
     X, Y, Z = 40, 24, 32
-    vol = _quiet_phantom(40)[:Z, :Y, :X].copy()
+    vol = quiet_phantom(40)[:Z, :Y, :X].copy()
     poses = {
         "axis": (np.array([20.0, 12.0, -6.0], F), np.array([0, 0, 1], F)),
         "face_y0": (np.array([20.0, 0.0, -6.0], F), np.array([0, 0, 1], F)),          # central row runs in the face y = 0
@@ -252,10 +171,6 @@ def test_axis_parallel_and_grazing_rays(gpu_ctx):
 def test_derived_data_follows_the_volume_and_invalidation(gpu_ctx):
     from tests import composite_ref as cr
     from tests import projection_ref as pr
-    from tests.test_gpu_composite import Comp
-    from tests.test_gpu_composite import _check as check_composite
-    from tests.test_gpu_projection import Proj
-    from tests.test_gpu_projection import _check as check_projection
 
     ctx = gpu_ctx
     X, Y, Z = 24, 16, 40
@@ -275,13 +190,13 @@ def test_derived_data_follows_the_volume_and_invalidation(gpu_ctx):
     def others(vol, what):
         """a projection and a composite: unchanged bytes whether or not an isosurface call came before"""
         want_p = pr.project(vol, pos, d, wh, wh, modes=(pr.MAX,), window_cw=(0.0, 1000.0))
-        check_projection(proj.run(volume, pos, d, pr.MAX, window=(0.0, 1000.0)), want_p[pr.MAX], "projection " + what)
-        check_composite(comp.run(volume, pos, d, lut, -1024), cr.composite(vol, pos, d, wh, wh, table, -1024), "composite " + what)
+        Proj.check(proj.run(volume, pos, d, pr.MAX, window=(0.0, 1000.0)), want_p[pr.MAX], "projection " + what)
+        Comp.check(comp.run(volume, pos, d, lut, -1024), cr.composite(vol, pos, d, wh, wh, table, -1024), "composite " + what)
 
     def iso(vol, what, through=None):
         for flags in (0, ir.BELOW):
             want = ir.isosurface(vol, pos, d, wh, wh, 300.0, flags=flags)
-            _check(out.run(through or volume, pos, d, 300.0, flags=flags), want, what)
+            Iso.check(out.run(through or volume, pos, d, 300.0, flags=flags), want, what)
             tally.add(want)
 
     others(a, "before any isosurface")  # builds the bricked copy; the dilated table does not exist yet
@@ -406,8 +321,8 @@ def test_full_size_512(gpu_ctx):
     for iso, flags, refine, t_near in ((300.0, 0, 8, 0.0), (20.0, ir.BELOW, 24, depth - 0.33 * n)):
         want = ir.isosurface(vol, pos, d, (1920, 1080), (W, H), iso, flags=flags, refine=refine, t_near=t_near, rows=rows)
         got = out.run(volume, pos, d, iso, flags=flags, refine=refine, t_near=t_near)
-        _check(tuple(g[rows] for g in got), want[:3], "skipping")
-        _check(out.run(volume, pos, d, iso, flags=flags | ir.DENSE, refine=refine, t_near=t_near), got, "dense")
+        Iso.check(tuple(g[rows] for g in got), want[:3], "skipping")
+        Iso.check(out.run(volume, pos, d, iso, flags=flags | ir.DENSE, refine=refine, t_near=t_near), got, "dense")
         tally.add(want)
     assert tally.refined > 1000 and tally.first > 1000 and tally.straddle > 0 and tally.miss_with_samples > 0, vars(tally)
     out.release()
@@ -415,15 +330,8 @@ def test_full_size_512(gpu_ctx):
 
 
 def _host_lib():
-    L = C.CDLL(os.path.join(ROOT, "cl_volume_renderer_amd", "libclvr_host.so"))
-    L.clvr_host_create.restype = C.c_void_p
-    L.clvr_host_destroy.argtypes = [C.c_void_p]
-    L.clvr_host_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
-    L.clvr_host_flush.argtypes = [C.c_void_p, C.c_char_p]
-    L.clvr_host_render_isosurface.restype = C.c_void_p
-    L.clvr_host_render_isosurface.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_int,
-                                              C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]
-    return L
+    return host_lib(clvr_host_render_isosurface=(C.c_void_p, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float,
+                                                              C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]))
 
 
 def test_host_mirror_isosurface_equals_the_reference():

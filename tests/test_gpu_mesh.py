@@ -12,10 +12,10 @@ import pytest
 from cl_volume_renderer_amd import ffi, scene
 from tests import isosurface_ref as ir
 from tests import mesh_ref as mr
+from tests.view_helpers import ROOT, host_lib
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID_VALUE, OUT_OF_MEMORY, SIZE_MISMATCH = 1, 3, 9
 DENSE, BELOW = ffi.MESH_DENSE, ffi.MESH_BELOW
 
@@ -355,16 +355,10 @@ def test_argument_errors(gpu_ctx):
 
 
 def _host_lib():
-    L = C.CDLL(os.path.join(ROOT, "cl_volume_renderer_amd", "libclvr_host.so"))
-    L.clvr_host_create.restype = C.c_void_p
-    L.clvr_host_destroy.argtypes = [C.c_void_p]
-    L.clvr_host_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
-    L.clvr_host_extract_mesh.restype = None
-    L.clvr_host_extract_mesh.argtypes = [C.c_void_p, C.c_float, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
-                                         C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
-                                         C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(C.POINTER(C.c_uint))]
-    L.clvr_host_write_mesh_ply.argtypes = [C.c_void_p, C.c_char_p]
-    return L
+    return host_lib(clvr_host_extract_mesh=(None, [C.c_void_p, C.c_float, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                                   C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
+                                                   C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(C.POINTER(C.c_uint))]),
+                    clvr_host_write_mesh_ply=(C.c_int, [C.c_void_p, C.c_char_p]))
 
 
 def test_host_mirror_extracts_the_same_mesh(tmp_path):

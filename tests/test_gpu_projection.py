@@ -10,67 +10,23 @@ import pytest
 
 from cl_volume_renderer_amd import ffi, scene
 from tests import projection_ref as pr
+from tests.view_helpers import ROOT, F, bits, toward, image_of, pose as _pose, host_lib, Proj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 MODES = (pr.MAX, pr.MIN, pr.MEAN)
 
 
-class Proj:
-    """a frame + the optional outputs on one context"""
-
-    def __init__(self, ctx, frame_wh, region_wh):
-        self.ctx, self.frame_wh, self.region_wh = ctx, frame_wh, region_wh
-        fw, fh = frame_wh
-        w, h = region_wh
-        self.frame = ctx.image([fw, fh], 4, np.uint8, (fh, fw, 4))
-        self.values = ctx.buffer(w * h * 4, np.float32, (h, w))
-        self.t = ctx.buffer(w * h * 4, np.float32, (h, w))
-
-    def run(self, volume, pos, d, mode, dense=False, **kw):
-        fw, fh = self.frame_wh
-        self.frame.push(np.full((fh, fw, 4), 7, np.uint8))  # pixels outside the region keep this
-        self.ctx.render_projection(self.frame, volume, pos, d, self.region_wh[0], self.region_wh[1], mode=mode, values=self.values,
-                                   t_extreme=self.t, dense=dense, **kw)
-        frame = self.frame.pull()
-        w, h = self.region_wh
-        assert np.all(frame[h:] == 7) and np.all(frame[:, w:] == 7)
-        return frame[:h, :w], self.values.pull(), self.t.pull()
-
-    def release(self):
-        for m in (self.frame, self.values, self.t):
-            m.release()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _check(got, want, what=""):
-    gf, gv, gt = got
-    wf, wv, wt = want
-    assert np.array_equal(gf, wf), "frame differs %s: %d pixels" % (what, int((gf != wf).any(axis=-1).sum()))
-    assert np.array_equal(_bits(gv), _bits(wv)), "values differ %s: %d pixels" % (what, int((_bits(gv) != _bits(wv)).sum()))
-    assert np.array_equal(_bits(gt), _bits(wt)), "t_extreme differs %s: %d pixels" % (what, int((_bits(gt) != _bits(wt)).sum()))
-
-
 def _compare_all(ctx, vol, pos, d, frame_wh, region_wh, step=0.5, window=(0.0, 1000.0), t_near=0.0, t_far=np.inf, skip_vs_dense=True):
-    Z, Y, X = vol.shape
-    if X > 1:
-        volume, owner = ctx.image_from(vol), None
-    else:  # (clwh_image_create refuses a width of 1, as clw_image does; a wrap takes any dims)
-        owner = ctx.buffer_from(vol)
-        volume = ctx.image_wrap(owner.device_ptr, (X, Y, Z), 1, np.int16)
+    volume, owner = image_of(ctx, vol)
     p = Proj(ctx, frame_wh, region_wh)
     want = pr.project(vol, pos, d, frame_wh, region_wh, modes=MODES, step=step, window_cw=window, t_near=t_near, t_far=t_far)
     kept = 0
     for mode in MODES:
         got = p.run(volume, pos, d, mode, step=step, window=window, t_near=t_near, t_far=t_far)
-        _check(got, want[mode], "mode %d" % mode)
+        Proj.check(got, want[mode], "mode %d" % mode)
         if mode != pr.MEAN and skip_vs_dense:
-            _check(p.run(volume, pos, d, mode, dense=True, step=step, window=window, t_near=t_near, t_far=t_far), want[mode],
+            Proj.check(p.run(volume, pos, d, mode, dense=True, step=step, window=window, t_near=t_near, t_far=t_far), want[mode],
                    "dense mode %d" % mode)
         kept = int((~np.isnan(want[mode][1])).sum())
     p.release()
@@ -80,26 +36,11 @@ def _compare_all(ctx, vol, pos, d, frame_wh, region_wh, step=0.5, window=(0.0, 1
     return kept
 
 
-def _toward(pos, target):
-    v = np.asarray(target, np.float64) - np.asarray(pos, np.float64)
-    return (v / np.linalg.norm(v)).astype(F)
-
-
 @pytest.mark.parametrize("dims", [(64, 64, 64), (70, 33, 45), (130, 20, 9), (5, 4, 3), (1, 1, 1)])
 @pytest.mark.parametrize("pose", ["default", "close", "inside"])
 def test_phantoms_from_several_poses(gpu_ctx, dims, pose):
-    X, Y, Z = dims
-    n = max(dims)
-    vol = scene.phantom(n, dims=dims)
-    centre = np.array([(X - 1) / 2, (Y - 1) / 2, (Z - 1) / 2], F)
-    if pose == "default":  # (aimed at the centre when the default direction would miss a flat or tiny volume)
-        pos, d = scene.default_camera(n)
-        d = d if X == Y == Z and n >= 8 else _toward(pos, centre)
-    elif pose == "close":  # scene.close_camera about the centre of a box that need not be a cube
-        d = scene.camera_direction(0.9, 6.183)
-        pos = (centre - d * F(0.6 * n)).astype(F)
-    else:
-        pos, d = np.array([X * 0.45, Y * 0.55, Z * 0.5], F), scene.camera_direction(2.1, 0.4)
+    vol = scene.phantom(max(dims), dims=dims)
+    pos, d = _pose(pose, dims)
     kept = _compare_all(gpu_ctx, vol, pos, d, (104, 72), (96, 64), window=(200.0, 1500.0))
     assert kept > 0
 
@@ -129,7 +70,7 @@ def test_axis_parallel_and_grazing_rays(gpu_ctx, case):
         "face_y0": (np.array([20.0, 0.0, -6.0], F), np.array([0, 0, 1], F)),          # central row runs in the face y = 0
         "edge_x0y0": (np.array([0.0, 0.0, -6.0], F), np.array([0, 0, 1], F)),        # central ray runs along an edge
         "face_xdim": (np.array([40.0, 12.0, -6.0], F), np.array([0, 0, 1], F)),      # x == X is outside
-        "diagonal": (np.array([-8.0, -8.0, -8.0], F), _toward((-8, -8, -8), (40, 24, 32))),
+        "diagonal": (np.array([-8.0, -8.0, -8.0], F), toward((-8, -8, -8), (40, 24, 32))),
         "straight_up": (np.array([20.0, -5.0, 16.0], F), np.array([0, 1, 0], F)),    # degenerate basis: NaN rays, nothing kept
     }[case]
     kept = _compare_all(gpu_ctx, vol, pos, d, (64, 48), (64, 48))
@@ -156,7 +97,7 @@ def test_adversarial_volumes_skipping_equals_dense(gpu_ctx, name):
     vol = _adversarial_volumes()[name]
     Z, Y, X = vol.shape
     poses = [scene.default_camera(X), scene.close_camera(X),
-             (np.array([-10.0, -3.0, -10.0], F), _toward((-10, -3, -10), (X, 0, Z))),          # rays graze the far corner
+             (np.array([-10.0, -3.0, -10.0], F), toward((-10, -3, -10), (X, 0, Z))),          # rays graze the far corner
              (np.array([X + 5.0, Y * 0.5, Z * 0.5], F), np.array([-1, 0, 0], F)),
              (np.array([X * 0.5, Y * 0.5, Z * 0.5], F), scene.camera_direction(4.0, 0.3))]
     for pos, d in poses:
@@ -172,21 +113,21 @@ def test_cache_follows_pushes_wraps_and_invalidation(gpu_ctx):
     volume = ctx.image_from(a)
     p = Proj(ctx, (64, 48), (64, 48))
     first = p.run(volume, pos, d, pr.MAX)
-    _check(first, pr.project(a, pos, d, (64, 48), (64, 48))[pr.MAX])
+    Proj.check(first, pr.project(a, pos, d, (64, 48), (64, 48))[pr.MAX])
     volume.push(b)  # a changed volume: rebuilt at the next projection
-    _check(p.run(volume, pos, d, pr.MAX), pr.project(b, pos, d, (64, 48), (64, 48))[pr.MAX], "after push")
+    Proj.check(p.run(volume, pos, d, pr.MAX), pr.project(b, pos, d, (64, 48), (64, 48))[pr.MAX], "after push")
     ctx.invalidate_derived(scene=False, camera=False, projection=True)
-    _check(p.run(volume, pos, d, pr.MAX), pr.project(b, pos, d, (64, 48), (64, 48))[pr.MAX], "after invalidate")
+    Proj.check(p.run(volume, pos, d, pr.MAX), pr.project(b, pos, d, (64, 48), (64, 48))[pr.MAX], "after invalidate")
     # two wraps of one pointer with permuted dims: same content version, different layouts
     w1 = ctx.image_wrap(volume.device_ptr, (X, Y, Z), 1, np.int16)
     w2 = ctx.image_wrap(volume.device_ptr, (Z, Y, X), 1, np.int16)
     as2 = b.reshape(X, Y, Z)  # the same bytes read as a Z x Y x X image (x fastest)
     for _ in range(2):
-        _check(p.run(w1, pos, d, pr.MIN), pr.project(b, pos, d, (64, 48), (64, 48), modes=(pr.MIN,))[pr.MIN], "wrap 1")
-        _check(p.run(w2, pos, d, pr.MIN), pr.project(as2, pos, d, (64, 48), (64, 48), modes=(pr.MIN,))[pr.MIN], "wrap 2")
+        Proj.check(p.run(w1, pos, d, pr.MIN), pr.project(b, pos, d, (64, 48), (64, 48), modes=(pr.MIN,))[pr.MIN], "wrap 1")
+        Proj.check(p.run(w2, pos, d, pr.MIN), pr.project(as2, pos, d, (64, 48), (64, 48), modes=(pr.MIN,))[pr.MIN], "wrap 2")
     # a rewrite through one wrap is seen through the other object of the same pointer
     w1.push(a)
-    _check(p.run(volume, pos, d, pr.MEAN), pr.project(a, pos, d, (64, 48), (64, 48), modes=(pr.MEAN,))[pr.MEAN], "after wrap push")
+    Proj.check(p.run(volume, pos, d, pr.MEAN), pr.project(a, pos, d, (64, 48), (64, 48), modes=(pr.MEAN,))[pr.MEAN], "after wrap push")
     ctx.finish()
     for m in (w1, w2, volume):
         m.release()
@@ -223,6 +164,36 @@ def test_argument_errors(gpu_ctx):
         m.release()
 
 
+def test_nan_camera_position_is_accepted_and_keeps_no_sample(gpu_ctx):
+    """the one difference between the views' camera checks (include/clwh.h): the projection does not refuse a NaN camera position --
+    every pixel has no kept sample -- while the compositor and the isosurface return CLWH_ERR_INVALID_VALUE for the same camera"""
+    ctx = gpu_ctx
+    volume = ctx.image_from(scene.phantom(16))
+    frame = ctx.image([16, 16], 4, np.uint8, (16, 16, 4))
+    values, t_extreme = ctx.buffer(16 * 16 * 4, np.float32, (16, 16)), ctx.buffer(16 * 16 * 4, np.float32, (16, 16))
+    lut = ctx.buffer_from(np.ones((16, 4), np.float32))
+    frame.push(np.full((16, 16, 4), 255, np.uint8))
+    pos, d = np.array([np.nan, 0.0, 0.0], F), scene.default_camera(16)[1]
+
+    def status(render, **kw):
+        try:
+            render(frame, volume, pos, d, 16, 16, **kw)
+            return 0
+        except ffi.ClwhError as e:
+            return e.status
+
+    assert status(ctx.render_projection, mode=pr.MAX, values=values, t_extreme=t_extreme) == 0
+    assert not frame.pull().any()
+    assert (bits(values.pull()) == 0x7FC00000).all() and (bits(t_extreme.pull()) == 0x7FC00000).all()
+    assert status(ctx.render_composite, lut=lut, lut_first=0) == 1
+    assert status(ctx.render_isosurface, iso=300.0) == 1
+    pos = scene.default_camera(16)[0]  # the same calls with a finite position: the camera was what they refused
+    assert status(ctx.render_composite, lut=lut, lut_first=0) == 0
+    assert status(ctx.render_isosurface, iso=300.0) == 0
+    for m in (volume, frame, values, t_extreme, lut):
+        m.release()
+
+
 def test_no_interference_with_the_path_tracer(gpu_ctx, orc):
     """projections interleaved with multi-seed render passes on one context: the path tracer's frame and voxel cache equal those of a
     context that never projected"""
@@ -249,7 +220,7 @@ def test_no_interference_with_the_path_tracer(gpu_ctx, orc):
         ctx.finish()
         results.append((s.frame.pull(), s.cache.pull()))
         if project:
-            _check(got, pr.project(vol, pos, d, (128, 128), (128, 128), window_cw=(0.0, 1000.0))[pr.MAX])
+            Proj.check(got, pr.project(vol, pos, d, (128, 128), (128, 128), window_cw=(0.0, 1000.0))[pr.MAX])
             p.release()
         s.release()
     other.destroy()
@@ -269,24 +240,17 @@ def test_full_size_512(gpu_ctx):
     want = pr.project(vol, pos, d, (1920, 1080), (W, H), modes=MODES, window_cw=window, rows=rows)
     for mode in MODES:
         f, v, t = p.run(volume, pos, d, mode, window=window)
-        _check((f[rows], v[rows], t[rows]), want[mode], "mode %d" % mode)
+        Proj.check((f[rows], v[rows], t[rows]), want[mode], "mode %d" % mode)
         if mode != pr.MEAN:
-            _check(p.run(volume, pos, d, mode, dense=True, window=window), (f, v, t), "dense mode %d" % mode)
+            Proj.check(p.run(volume, pos, d, mode, dense=True, window=window), (f, v, t), "dense mode %d" % mode)
     assert (~np.isnan(want[pr.MAX][1])).sum() > 10000
     p.release()
     volume.release()
 
 
 def _host_lib():
-    L = C.CDLL(os.path.join(ROOT, "cl_volume_renderer_amd", "libclvr_host.so"))
-    L.clvr_host_create.restype = C.c_void_p
-    L.clvr_host_destroy.argtypes = [C.c_void_p]
-    L.clvr_host_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
-    L.clvr_host_flush.argtypes = [C.c_void_p, C.c_char_p]
-    L.clvr_host_render_projection.restype = C.c_void_p
-    L.clvr_host_render_projection.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
-                                              C.c_float, C.c_float, C.c_float]
-    return L
+    return host_lib(clvr_host_render_projection=(C.c_void_p, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                                              C.c_float, C.c_float, C.c_float]))
 
 
 def test_host_mirror_projection_equals_the_ffi_frame(gpu_ctx):

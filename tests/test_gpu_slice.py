@@ -13,53 +13,13 @@ import pytest
 
 from cl_volume_renderer_amd import ffi, scene
 from tests import slice_ref as sr
-from tests.test_gpu_isosurface import _image_of, _plant_blocks, _quiet_phantom
+from tests.view_helpers import ROOT, F, bits, image_of, pose as _pose, plant_blocks, quiet_phantom, host_lib, Slice, Iso, Proj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 INVALID_VALUE, BAD_NDRANGE, SIZE_MISMATCH = 1, 8, 9
 FRAME, REGION = (64, 48), (56, 40)
 MODES = (sr.MAX, sr.MIN, sr.MEAN)
-
-
-class Slice:
-    """a frame + the optional outputs on one context"""
-
-    def __init__(self, ctx, frame_wh, region_wh):
-        self.ctx, self.frame_wh, self.region_wh = ctx, frame_wh, region_wh
-        fw, fh = frame_wh
-        w, h = region_wh
-        self.frame = ctx.image([fw, fh], 4, np.uint8, (fh, fw, 4))
-        self.values = ctx.buffer(w * h * 4, np.float32, (h, w))
-        self.t = ctx.buffer(w * h * 4, np.float32, (h, w))
-
-    def run(self, volume, case, mode, flags=0):
-        fw, fh = self.frame_wh
-        self.frame.push(np.full((fh, fw, 4), 7, np.uint8))  # pixels outside the region keep this
-        c = case
-        self.ctx.render_slice(self.frame, volume, c["origin"], c["du"], c["dv"], c["normal"], self.region_wh[0], self.region_wh[1], mode=mode,
-                              slab_samples=c["n"], step=c["step"], window=c["window"], flags=flags, values=self.values, t_extreme=self.t)
-        frame = self.frame.pull()
-        w, h = self.region_wh
-        assert np.all(frame[h:] == 7) and np.all(frame[:, w:] == 7)
-        return frame[:h, :w], self.values.pull(), self.t.pull()
-
-    def release(self):
-        for m in (self.frame, self.values, self.t):
-            m.release()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _check(got, want, what=""):
-    assert np.array_equal(got[0], want[0]), "frame differs %s: %d pixels" % (what, int((got[0] != want[0]).any(axis=-1).sum()))
-    for name, g, w in zip(("values", "t_extreme"), got[1:3], want[1:3]):
-        bad = _bits(g) != _bits(w)
-        assert not bad.any(), "%s differs %s: %d values, first at %s" % (name, what, int(bad.sum()), tuple(np.argwhere(bad)[0]))
 
 
 class Tally:
@@ -112,7 +72,7 @@ def _run_family(ctx, cases):
     for c in cases:
         vol = c["vol"]
         if id(vol) not in images:
-            images[id(vol)] = _image_of(ctx, vol)
+            images[id(vol)] = image_of(ctx, vol)
         key = (c["frame_wh"], c["region_wh"])
         if key not in outputs:
             outputs[key] = Slice(ctx, *key)
@@ -120,8 +80,8 @@ def _run_family(ctx, cases):
         want, stats = reference_of(c)
         what = "dims %s n %d step %r origin %s normal %s" % (vol.shape[::-1], c["n"], c["step"], c["origin"], c["normal"])
         for mode in MODES:
-            _check(out.run(volume, c, mode), want[mode], "skipping, mode %d, %s" % (mode, what))
-            _check(out.run(volume, c, mode, flags=sr.DENSE), want[mode], "dense, mode %d, %s" % (mode, what))
+            Slice.check(out.run(volume, c, mode), want[mode], "skipping, mode %d, %s" % (mode, what))
+            Slice.check(out.run(volume, c, mode, flags=sr.DENSE), want[mode], "dense, mode %d, %s" % (mode, what))
         tally.add(stats)
     for out in outputs.values():
         out.release()
@@ -158,7 +118,7 @@ def phantom_cases():
         vol = scene.phantom(max(dims), dims=dims)
         for n, step in SLABS:
             cases.append(_case(vol, *oblique(dims, n=n, step=step), n=n, step=step))
-    quiet = _quiet_phantom(48)  # constant regions: whole bricks are stepped over as soon as the slab has entered the air
+    quiet = quiet_phantom(48)  # constant regions: whole bricks are stepped over as soon as the slab has entered the air
     for n in (64, 200):
         cases.append(_case(quiet, *oblique((48, 48, 48), n=n, step=0.5), n=n, step=0.5))
     return cases
@@ -174,7 +134,7 @@ def random_cases():
     cases = []
     for dims in [(24, 24, 24), (17, 9, 33)]:
         X, Y, Z = dims
-        vol = _plant_blocks(rng.integers(0, 1 << 16, size=(Z, Y, X), dtype=np.uint16).view(np.int16))
+        vol = plant_blocks(rng.integers(0, 1 << 16, size=(Z, Y, X), dtype=np.uint16).view(np.int16))
         diag = np.array([X, Y, Z], np.float64) / 56  # du along the volume's diagonal: pixel x runs from corner to corner
         side = np.cross(diag, [0.0, 0.0, 1.0])
         side *= 0.4 / np.linalg.norm(side)
@@ -204,7 +164,7 @@ def _axial_identity_cases(vol):
 @functools.lru_cache(maxsize=None)
 def axis_cases():
     X, Y, Z = 40, 24, 32
-    vol = _quiet_phantom(40)[:Z, :Y, :X].copy()
+    vol = quiet_phantom(40)[:Z, :Y, :X].copy()
     cases = []
     for normal, n in (((0, 0, 1), 9), ((0, 0, -1), 9), ((0, 0, 1), 60)):  # the plane lies in the face z = 0; -z leaves at once
         cases.append(_case(vol, (0.25, 0.25, 0.0), (0.75, 0, 0), (0, 0.65, 0), normal, n=n))
@@ -226,7 +186,7 @@ def check_axis_expectations(cases):
     assert want[1][1]["cut"].sum() > 0 and not want[1][1]["full"].any()          # normal -z from the face z = 0: sample 0 alone
     assert want[6][1]["none"].all() and want[8][1]["none"].all()                   # x = X is outside
     assert want[7][1]["cut"].sum() > 0                                            # ... and entered at sample 1
-    assert np.all(_bits(want[7][0][sr.MAX][2][want[7][1]["cut"]]) >= _bits(F(0.5)))  # t_extreme counts from sample 0
+    assert np.all(bits(want[7][0][sr.MAX][2][want[7][1]["cut"]]) >= bits(F(0.5)))  # t_extreme counts from sample 0
     for c, w, v in ((cases[9], want[9], 32767), (cases[10], want[10], -32768)):
         for mode in MODES:
             assert np.all(w[0][mode][1] == F(v)) and w[1]["full"].all()
@@ -246,7 +206,7 @@ def test_axis_aligned_and_grazing_planes(gpu_ctx):
 
 @functools.lru_cache(maxsize=None)
 def window_cases():
-    vol = _quiet_phantom(40)
+    vol = quiet_phantom(40)
     cases = []
     for window in ((1.0e6, 10.0), (-1.0e6, 10.0), (40.0, 0.001), (40.0, 1.0e-30), (0.0, 3.0e38)):
         for n, step in ((1, 0.5), (16, 0.5)):
@@ -279,7 +239,7 @@ def test_windowing_at_its_ends(gpu_ctx):
 
 def derived_data_volumes():
     X, Y, Z = 24, 16, 40
-    a = _quiet_phantom(40)[:Z, :Y, :X].copy()
+    a = quiet_phantom(40)[:Z, :Y, :X].copy()
     b = np.where(a < -500, 900, -1000).astype(np.int16)  # air and ball swap: a stale dilated table skips the bricks that now hold the extreme
     return a, b
 
@@ -292,10 +252,6 @@ def derived_data_case(vol):
 def test_derived_data_follows_the_volume_and_invalidation():
     from tests import isosurface_ref as ir
     from tests import projection_ref as pr
-    from tests.test_gpu_isosurface import Iso, _pose
-    from tests.test_gpu_isosurface import _check as check_isosurface
-    from tests.test_gpu_projection import Proj
-    from tests.test_gpu_projection import _check as check_projection
 
     a, b = derived_data_volumes()
     ctx = ffi.Context(0)  # a fresh context: nothing derived yet, no isosurface call before the first slice
@@ -308,7 +264,7 @@ def test_derived_data_follows_the_volume_and_invalidation():
             c = derived_data_case(vol)
             want, stats = reference_of(c)
             for mode in modes:
-                _check(out.run(volume, c, mode), want[mode], "%s, mode %d" % (what, mode))
+                Slice.check(out.run(volume, c, mode), want[mode], "%s, mode %d" % (what, mode))
             tally.add(stats)
 
         slices(a, "first call of the context", modes=(sr.MAX,))
@@ -320,9 +276,9 @@ def test_derived_data_follows_the_volume_and_invalidation():
         iso, proj = Iso(ctx, FRAME, FRAME), Proj(ctx, FRAME, FRAME)
         pos, d = _pose("default", b.shape[::-1])
         for flags in (0, ir.BELOW):
-            check_isosurface(iso.run(volume, pos, d, 300.0, flags=flags), ir.isosurface(b, pos, d, FRAME, FRAME, 300.0, flags=flags), "isosurface")
+            Iso.check(iso.run(volume, pos, d, 300.0, flags=flags), ir.isosurface(b, pos, d, FRAME, FRAME, 300.0, flags=flags), "isosurface")
         want_p = pr.project(b, pos, d, FRAME, FRAME, modes=(pr.MAX,), window_cw=(0.0, 1000.0))
-        check_projection(proj.run(volume, pos, d, pr.MAX, window=(0.0, 1000.0)), want_p[pr.MAX], "projection")
+        Proj.check(proj.run(volume, pos, d, pr.MAX, window=(0.0, 1000.0)), want_p[pr.MAX], "projection")
         slices(b, "after an isosurface and a projection")
         ctx.finish()
         for o in (out, iso, proj):
@@ -408,14 +364,8 @@ def test_argument_errors(gpu_ctx):
 
 
 def _host_lib():
-    L = C.CDLL(os.path.join(ROOT, "cl_volume_renderer_amd", "libclvr_host.so"))
-    L.clvr_host_create.restype = C.c_void_p
-    L.clvr_host_destroy.argtypes = [C.c_void_p]
-    L.clvr_host_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
-    L.clvr_host_flush.argtypes = [C.c_void_p, C.c_char_p]
-    L.clvr_host_render_slice.restype = C.c_void_p
-    L.clvr_host_render_slice.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
-    return L
+    return host_lib(clvr_host_render_slice=(C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                         C.c_float, C.c_int]))
 
 
 def test_host_mirror_slice_equals_the_binding(gpu_ctx):
