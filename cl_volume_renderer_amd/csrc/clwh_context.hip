@@ -169,6 +169,7 @@ Tuning clvr::tuning_from_environment() {
   if (const char *e = std::getenv("CLWH_TUNE_SDFBIT_GRID")) t.sdfbit_grid = std::max(1, std::atoi(e));
   if (const char *e = std::getenv("CLWH_TUNE_SDFBIT_REC")) t.sdfbit_rec_lds = std::strcmp(e, "lds") == 0 ? 1 : 0;
   if (const char *e = std::getenv("CLWH_TUNE_CERT")) t.cert_min_step = clamped(e, 0, 127);
+  if (const char *e = std::getenv("CLWH_TUNE_CERT_HINT")) t.cert_hint = std::atoi(e) != 0;
   return t;
 }
 

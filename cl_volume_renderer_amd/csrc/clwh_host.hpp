@@ -107,6 +107,7 @@ struct PackedScene {
   TfDev tf{};
   std::string tf_identity;   // opaque (hiprtc) transfer functions: the source text -- two sources may share a palette
   int32_t macro_shift = 0;
+  int32_t dims[3] = {0, 0, 0};  // of the volume (the macro table's place in `data` follows from them)
   uint64_t generation = 0;   // process-wide unique id of this content (part of the primary-hit key)
   Event ready;               // recorded on the building stream after the last build kernel; adopters make their stream wait for it
   bool stale = false;        // clwh_ctx_invalidate_derived: nobody adopts it any more
@@ -133,6 +134,7 @@ struct Tuning {
   int32_t literal_gradient = 0;
   int32_t unit_block_log2 = 4;
   int32_t unit_group = 1, unit_affinity = 0, unit_queues = 8;
+  int32_t cert_hint = 1;       // CLWH_TUNE_CERT_HINT=0: a refused march asks again at its next long step, whatever the refusing entry says
   int32_t cert_min_step = -1;  // CLWH_TUNE_CERT: 0 = exit certificates off; -1 = by volume size (12 at 512^3, 24 at 1024^3, 48 at 2048^3:
                                // the best of the sweeps in profiles/r02_sweep_k_bounce_lds_state.txt)
   uint32_t bounce_max_blocks = 2048;  // CLWH_TUNE_BLOCKS

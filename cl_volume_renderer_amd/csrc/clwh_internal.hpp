@@ -52,11 +52,13 @@ struct RenderArgs {
   const int16_t *volume_lin;  // the caller's images (x fastest): literal taps of the rare paths
   const int8_t *sdf_lin;
   // exit certificates (render_kernels.hip, certify_exit): eight bytes per macro cell of 16^3 voxels; byte o: the smallest SDF value in
-  // the box a march from this cell in direction octant o crosses until it leaves the volume, 0 = the box is not free
+  // the box a march from this cell in direction octant o crosses until it leaves the volume (1..127), or, when the box is not free,
+  // 0x80 | the number of cells along the octant's diagonal until it is (k_macro_hints)
   const uint8_t *macro;
   int32_t MNX, MNY, MNZ, macro_shift;  // cells per axis, log2 of the cell's edge in voxels
   int32_t cert_min_step;   // a march asks for a certificate once its next step is at least this long; 0 = certificates off
   int32_t cert_min_lanes;  // ... and the wave looks them up once this many lanes wait for one (launch_bounce sets it)
+  int32_t cert_hint;       // 1: a refused march stays off the table for the distance the refusing entry names (k_macro_hints)
   int32_t NBX, NBY;
   const uint32_t *env;     // RGBA8 packed, row-major
   int32_t env_w, env_h;

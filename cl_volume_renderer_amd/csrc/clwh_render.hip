@@ -119,6 +119,7 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
     entry->tf = tf;
     entry->tf_identity = tf_identity;
     entry->macro_shift = L.mshift;
+    entry->dims[0] = L.X; entry->dims[1] = L.Y; entry->dims[2] = L.Z;
     entry->generation = ++g_packed_generation;
     entry->stale = false;
     bool listed = false;
@@ -229,6 +230,7 @@ static int describe_launch(const clwh_ctx *ctx, const clwh_render_desc *d, Rende
   a.unit_block_log2 = t.unit_block_log2;
   a.unit_affinity = t.unit_affinity;
   a.unit_queues = t.unit_queues;
+  a.cert_hint = t.cert_hint;
   return CLWH_OK;
 }
 
@@ -255,7 +257,7 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   bool zero_may_hit = a.tf.border_class != 0;
   for (int q = 0; q < a.tf.n && a.tf.uses_gradient && !a.tf.opaque; ++q)
     if (a.tf.rules[q].v_lo <= 0 && 0 <= a.tf.rules[q].v_hi) zero_may_hit = true;
-  const int cert_auto = std::min(12 << (a.macro_shift - 4), 48);  // re-swept in round 3 with the stronger certificates: 8 / 12 / 16 -> 3.69 / 3.59 / 3.6-3.9 ms
+  const int cert_auto = a.macro_shift < 4 ? 12 >> (4 - a.macro_shift) : std::min(12 << (a.macro_shift - 4), 48);  // re-swept in round 3 with the stronger certificates: 8 / 12 / 16 -> 3.69 / 3.59 / 3.6-3.9 ms
   a.cert_min_step = zero_may_hit ? 0 : (ctx->tune.cert_min_step >= 0 ? ctx->tune.cert_min_step : cert_auto);
   return CLWH_OK;
 }
@@ -543,6 +545,26 @@ int clwh_ctx_scene_info(clwh_ctx *ctx, uint64_t *scene_id, uint64_t *bytes, int3
   if (scene_id) *scene_id = ctx->scene ? ctx->scene->generation : 0;
   if (bytes) *bytes = ctx->scene ? ctx->scene->data.bytes : 0;
   if (holders) *holders = ctx->scene ? (int32_t)ctx->scene.use_count() : 0;
+  return CLWH_OK;
+}
+
+int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
+  PackedLayout L;
+  {
+    std::lock_guard<std::mutex> lock(g_scenes_mutex);
+    clwh_mem shape{};
+    for (int q = 0; q < 3; ++q) shape.dims[q] = (size_t)ctx->scene->dims[q];
+    L = packed_layout(&shape, ctx->scene->macro_shift);
+  }
+  info_out[0] = L.MNX; info_out[1] = L.MNY; info_out[2] = L.MNZ; info_out[3] = L.mshift;
+  const size_t bytes = L.bytes - L.off_macro;
+  if (!host_out) return CLWH_OK;  // the size alone
+  if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + L.off_macro, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return CLWH_OK;
 }
 

@@ -275,6 +275,37 @@ __global__ __launch_bounds__(256) void k_macro_bounds(uint2 *__restrict__ macro,
   }
   macro[c] = r;
 }
+// Step 4: a refusing entry says how long to stay away.  For a cell c whose box towards octant o is not free, g = the number of cells
+// one must advance along the octant's diagonal until the box is free or the volume ends.  The box of any cell at Chebyshev offset
+// <= m from c in the octant's direction contains the box of c + m diagonal, so no cell with every offset below g has a free box: a
+// march refused at c cannot get a certificate before one of its coordinates has advanced g - 1 whole cells (k_bounce stays off the
+// table that long).  The entry becomes kCertRefused | min(g, 127); certify_exit reads every such value as "not free", so the hint can
+// only change WHEN a look-up is made.  (In place: an entry is free before and after, or refusing before -- 0 -- and after -- bit 7
+// set --, so a thread that reads a neighbour's entry sees the same answer either way.)
+constexpr uint32_t kCertRefused = 0x80u;  // box minima are SDF values, at most 127
+__global__ __launch_bounds__(256) void k_macro_hints(uint2 *__restrict__ macro, int MNX, int MNY, int MNZ) {
+  const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (c >= MNX * MNY * MNZ) return;
+  const int cx = c % MNX, cy = (c / MNX) % MNY, cz = c / (MNX * MNY);
+  const uint8_t *bytes = reinterpret_cast<const uint8_t *>(macro);
+  const uint2 v = macro[c];
+  uint2 r = v;
+  for (int o = 0; o < 8; ++o) {
+    const uint32_t m = ((o < 4 ? v.x : v.y) >> ((o & 3) * 8)) & 0xFFu;
+    if (m != 0u && !(m & kCertRefused)) continue;  // free
+    const int sx = (o & 1) ? -1 : 1, sy = (o & 2) ? -1 : 1, sz = (o & 4) ? -1 : 1;
+    uint32_t g = 1u;
+    for (; g < 127u; ++g) {
+      const int x = cx + sx * (int)g, y = cy + sy * (int)g, z = cz + sz * (int)g;
+      if ((unsigned)x >= (unsigned)MNX || (unsigned)y >= (unsigned)MNY || (unsigned)z >= (unsigned)MNZ) break;
+      const uint32_t n = bytes[((((size_t)z * (size_t)MNY + (size_t)y) * (size_t)MNX + (size_t)x) << 3) | (size_t)o];
+      if (n != 0u && !(n & kCertRefused)) break;
+    }
+    const uint32_t e = kCertRefused | g;
+    if (o < 4) r.x = (r.x & ~(0xFFu << (o * 8))) | (e << (o * 8)); else r.y = (r.y & ~(0xFFu << ((o - 4) * 8))) | (e << ((o - 4) * 8));
+  }
+  macro[c] = r;
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_primary: ray_marching.cl:152-186 up to (and including) the first march_to_next_event of
@@ -485,12 +516,17 @@ constexpr int kFixupDwords = 32;  // one record = 128 B: header[4] bv_before[3] 
 // with another weight, ray_marching.cl:52-73).  tools/exit_certificate.py measured the idea on the oracle first: every
 // exiting ray gets its certificate at some point, 5 of the 30 step fetches per item disappear (all far field), and not
 // one certificate in millions was wrong.
-__device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
+// `away`: after a refusal, the path length the march has to cover before a look-up can succeed ((g - 1) cells, k_macro_hints); 0 when
+// the table does not say (the box is free but the budget too small, or one of the rare directions)
+__device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget, int &away) {
   // the position has a voxel or sits on the far face: 0 <= p <= dim (or -0.0)
   const unsigned cx = min((unsigned)(int)p.x >> a.macro_shift, (unsigned)a.MNX - 1u), cy = min((unsigned)(int)p.y >> a.macro_shift, (unsigned)a.MNY - 1u),
                  cz = min((unsigned)(int)p.z >> a.macro_shift, (unsigned)a.MNZ - 1u);
   const unsigned octant = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-  const int box_min = a.macro[(((cz * (unsigned)a.MNY + cy) * (unsigned)a.MNX + cx) << 3) | octant];  // (at most 2^22 entries)
+  const int entry = a.macro[(((cz * (unsigned)a.MNY + cy) * (unsigned)a.MNX + cx) << 3) | octant];  // (at most 2^22 entries)
+  const bool refused = (entry & (int)kCertRefused) != 0;
+  const int box_min = refused ? 0 : entry;
+  away = refused ? ((entry & 0x7F) - 1) << a.macro_shift : 0;
   // One kind of position is outside the reasoning below: a coordinate that landed exactly ON the far face (== dimension: not exited,
   // utility_ray.cl:112-117) reads the border SDF 0 and advances 0.5 |d| per step; with a direction component too small to move that
   // coordinate (0.5 x 2^-10 is above half an ulp of every dimension below 2^13) the reference can crawl along the face and even run
@@ -506,6 +542,10 @@ __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, in
   const float fx = d.x < 0.0f ? p.x : (float)a.X - p.x, fy = d.y < 0.0f ? p.y : (float)a.Y - p.y, fz = d.z < 0.0f ? p.z : (float)a.Z - p.z;
   const bool leaves = T * fabsf(d.x) >= fx || T * fabsf(d.y) >= fy || T * fabsf(d.z) >= fz;
   return box_min != 0 && budget > 5 && leaves && dmin >= 0.0009765625f && dsum == dsum;
+}
+__device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
+  int away;
+  return certify_exit(a, p, d, budget, away);
 }
 
 #ifndef CLVR_BOUNCE_WAVES_PER_SIMD
@@ -565,7 +605,13 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // scheduling state
   int st = ST_IDLE;        // ST_IDLE / ST_MARCH / ST_CERT / ST_EVENT + event
   int sd = 0;              // SDF value for the next step of a MARCH lane
-  int steps_left = 0;
+  // steps this march may still take (0..70) in bits 24-30; below them kCertReady - (the path length the march still has to cover
+  // before its next certificate look-up can succeed, see certify_exit): one add per step moves both, `no steps left` is one
+  // unsigned compare, and the march may ask again once bit 23 is set.  (The distance is at most 126 cells, a march covers at most
+  // 70 x 127 voxels: neither field reaches its neighbour.)
+  uint32_t march = 0u;
+  constexpr uint32_t kOneStep = 1u << 24, kCertReady = 1u << 23;
+  const bool cert_hint = a.cert_hint != 0;
   const int cert_min_lanes = a.cert_min_lanes;
   // a lane asks for an exit certificate when its next step is at least this long (wave-uniform)
   const int cert_at = a.cert_min_step != 0 ? a.cert_min_step : kCertNever;
@@ -696,7 +742,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         if (st == ST_MARCH) {
           // sd is an integer in 0..127: fmaxf is cl_max here
           ray.origin = ray.origin + ray.direction * fmaxf((float)sd, 0.5f);
-          --steps_left;
+          march += (uint32_t)sd - kOneStep;
           if (!USE_GRAD) {
             // Has the new position a voxel?  +0 <= coordinate < dimension is ONE unsigned compare of the float's bits per axis
             // (negative values, -0.0 and NaN all have larger patterns than any dimension).  Whatever fails it -- nearly always
@@ -735,8 +781,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
 #endif
               sd = (int)(q & 0x7Fu);
               if (q & 0x80u) st = ST_EVENT + EV_HIT_COLOR_PENDING;
-              else if (steps_left == 0) st = ST_EVENT + EV_NONE;
-              else if (sd >= cert_at) st = ST_CERT;  // far from every surface: can the rest of this march be proven to exit?
+              else if (march < kOneStep) st = ST_EVENT + EV_NONE;
+              else if (sd >= cert_at && (march & kCertReady)) st = ST_CERT;  // far from every surface: can the rest of this march be proven to exit?
             } else {
               st = ST_EVENT + EV_CHECK;
             }
@@ -748,11 +794,11 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             const bool is_hit = classify_step<USE_GRAD, SMALL, true>(vol, a.tf, ray.origin, color, next_sd, &pending);
             if (is_hit) {
               st = ST_EVENT + (pending ? EV_HIT_COLOR_PENDING : EV_HIT);
-            } else if (steps_left == 0) {
+            } else if (march < kOneStep) {
               st = ST_EVENT + EV_NONE;
             } else {
               sd = next_sd;
-              if (sd >= cert_at) st = ST_CERT;
+              if (sd >= cert_at && (march & kCertReady)) st = ST_CERT;
             }
           }
         }
@@ -766,11 +812,14 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           const int marching_before = __popcll(__ballot(st == ST_MARCH));
 #endif
           if (st == ST_CERT) {
-            if (certify_exit(a, ray.origin, ray.direction, steps_left)) {
+            int away;
+            if (certify_exit(a, ray.origin, ray.direction, (int)(march >> 24), away)) {
               st = ST_EVENT + EV_EXIT;  // the march WOULD end in Exit_volume; only its direction matters from here on
             } else {
               // it tries again at its next step that is long enough (trying less often -- only once the step has doubled, or grown by
-              // half -- left more lines to fetch than the look-ups cost: 4.03 / 3.92 / 3.91 ms)
+              // half -- left more lines to fetch than the look-ups cost: 4.03 / 3.92 / 3.91 ms), but not before it has covered the
+              // distance the refusing entry names (CLWH_TUNE_CERT_HINT=0: at once, as before the table had hints)
+              march = (march & ~(kOneStep - 1u)) | (kCertReady - (uint32_t)(cert_hint ? away : 0));
               st = ST_MARCH;
             }
           }
@@ -813,9 +862,9 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             ev = pending ? EV_HIT_COLOR_PENDING : EV_HIT;
             break;
           }
-          if (steps_left == 0) { ev = EV_NONE; break; }
+          if (march < kOneStep) { ev = EV_NONE; break; }
           ray.origin = ray.origin + ray.direction * fmaxf((float)next_sd, 0.5f);
-          --steps_left;
+          march -= kOneStep;
         }
       }
       bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
@@ -935,7 +984,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
       if (st >= ST_EVENT) {
         // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
         sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
-        steps_left = 70;
+        march = 70u * kOneStep + kCertReady;
         st = ST_MARCH;
       }
     }
@@ -1520,6 +1569,7 @@ hipError_t launch_macro_table(const uint32_t *brick_min, int NBX, int NBY, int N
   for (int axis = 0; axis < 3; ++axis)
     hipLaunchKernelGGL(k_macro_octants, dim3(((unsigned)lines[axis] + 63u) / 64u), dim3(64), 0, s, macro, MNX, MNY, MNZ, axis);
   hipLaunchKernelGGL(k_macro_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, macro, MNX, MNY, MNZ);
+  hipLaunchKernelGGL(k_macro_hints, dim3((n + 255u) / 256u), dim3(256), 0, s, macro, MNX, MNY, MNZ);
   return hipGetLastError();
 }
 

@@ -190,6 +190,7 @@ _PROTOTYPES = [
     ("clwh_tf_parse", C.c_int, [C.c_char_p, C.POINTER(Tf)]),
     ("clwh_debug_float_conversions", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("clwh_debug_wave_min", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("clwh_debug_macro_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_strerror", C.c_char_p, [C.c_int]),
     ("clwh_last_hip_error", C.c_int, []),
     ("clwh_version", C.c_char_p, []),
@@ -547,6 +548,15 @@ class Context:
         sid, nb, holders = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
         _check(lib().clwh_ctx_scene_info(self.h, C.byref(sid), C.byref(nb), C.byref(holders)), "clwh_ctx_scene_info")
         return int(sid.value), int(nb.value), int(holders.value)
+
+    def macro_table(self):
+        """the exit-certificate table of the scene data this context rendered from last: (uint8 [cz][cy][cx][octant], log2 of the
+        cell's edge); entries 1..127: the box is free, this is its smallest step value; 0x80 | g: not free, stay away g - 1 cells"""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_macro_table(self.h, None, C.c_uint64(0), info), "clwh_debug_macro_table")
+        out = np.empty((info[2], info[1], info[0], 8), np.uint8)
+        _check(lib().clwh_debug_macro_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_macro_table")
+        return out, int(info[3])
 
     def image_wrap(self, device_ptr: int, dims, channels, dtype, shape=None) -> Mem:
         """adopt device memory somebody else allocated (a graphics-interop mapping, a torch tensor) as an image"""

@@ -583,6 +583,12 @@ int clwh_debug_float_conversions(clwh_ctx *ctx, clwh_mem *floats_in, uint64_t n,
 /* self-test of the wave-wide minimum k_repack takes over a sub-brick's 64 voxels for the exit-certificate table (cross-lane DPP
  * operations): n (a multiple of 64) values, one wave per 64; u32_out[0, n/64) = that minimum, [n/64, 2n/64) = the same by a shuffle loop */
 int clwh_debug_wave_min(clwh_ctx *ctx, clwh_mem *u32_in, uint64_t n, clwh_mem *u32_out);
+/* the exit-certificate table of the derived scene data the context rendered from last: info_out = {cells along x, y, z,
+ * log2 of a cell's edge in voxels}; host_out (may be null: the shape alone) receives 8 bytes per cell, x fastest, byte o = the entry
+ * of direction octant o = [d.x < 0] | [d.y < 0] << 1 | [d.z < 0] << 2: 1..127 = the box towards the octant's corner is free and this is
+ * its smallest step value; 0x80 | g = it is not, and g (saturating at 127) cells along the octant's diagonal is the nearest cell
+ * whose box is free or that lies outside the volume.  CLWH_ERR_BAD_ARGS: the context holds no scene data */
+int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
 const char *clwh_strerror(int status);
 int clwh_last_hip_error(void);
 const char *clwh_version(void);
