@@ -392,7 +392,7 @@ static int plan_voxel_grants(clwh_ctx *ctx, RenderArgs &a) {
 
 #ifdef CLVR_BOUNCE_STATS  // experiment builds only (CLVR_EXTRA_HIPCC_FLAGS=-DCLVR_BOUNCE_STATS): scheduling statistics of the launch
 static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
-  uint32_t h[22];
+  uint32_t h[23];
   HIP_TRY(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   std::fprintf(stderr, "[bounce stats] items=%llu step_iters=%u avg_march_lanes=%.2f event_phases=%u avg_event_lanes=%.2f "
@@ -401,6 +401,8 @@ static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
                h[10] ? (double)h[11] / h[10] : 0.0, h[12], h[12] ? (double)h[13] / h[12] : 0.0, h[14], h[15], h[16], h[17], h[18],
                h[18] ? (double)h[19] / h[18] : 0.0, h[20]);
   if (h[21]) std::fprintf(stderr, "[bounce stats] two rays per lane: %u swap points\n", h[21]);
+  // k_bounce: idle lanes while the wave steps ([21] belongs to k_bounce2)
+  std::fprintf(stderr, "[bounce stats] per step iteration: avg_idle_lanes=%.2f (lane sum %u)\n", h[8] ? (double)h[22] / h[8] : 0.0, h[22]);
   return CLWH_OK;
 }
 #endif

@@ -388,11 +388,12 @@ __global__ __launch_bounds__(64) void k_primary(const RenderArgs a) {
 // k_bounce: ray_marching.cl:39-77 for every (hit, seed) item.
 //
 // Lane state machine.  MARCH lanes take march steps; a lane that reaches an event (Hit / Exit /
-// 70 steps, or a freshly fetched item) parks in EVENT until the wave runs its event phase; IDLE
-// lanes have no item.
+// 70 steps) parks in EVENT until the wave runs its event phase; IDLE lanes have no item.  The event
+// phase has two halves with the refill between them, so a lane whose sample ends takes its next
+// item and starts it in the same phase (k_bounce2 still parks fresh items through a step run).
 // One register holds both: ST_IDLE, ST_MARCH, ST_CERT (parked for an exit-certificate attempt), or ST_EVENT + the pending event.
 enum : int { ST_IDLE = 0, ST_MARCH = 1, ST_CERT = 2, ST_EVENT = 8 };
-enum : int { EV_START = 3,              // a freshly fetched item: start distribution ray 1
+enum : int { EV_START = 3,              // start distribution ray `o` from the primary hit (a freshly fetched item: o = 1)
              EV_HIT_COLOR_PENDING = 4,  // a Hit whose rule colour is still to be fetched (classify_step DEFER_COLOR)
              EV_CHECK = 5 };            // the new position has no voxel: left the volume, or one of the rare in-between cases?
 constexpr int kCertNever = 255;         // no step is this long
@@ -620,116 +621,18 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   uint32_t st_step_iters = 0, st_step_lanes = 0, st_event_phases = 0, st_event_lanes = 0, st_refills = 0, st_refill_lanes = 0;
   uint32_t st_ev_kind[4] = {0, 0, 0, 0};
   uint32_t st_cert_phases = 0, st_cert_lanes = 0, st_cert_granted = 0;
+  uint32_t st_step_idle = 0;  // idle lanes, summed over the step iterations
 #endif
 
+  // One pass of the loop: step run, closing half of the event phase, refill, opening half.  (First pass: no lane marches and no
+  // lane has an event, so only the refill and the opening half do anything.)
   for (;;) {
-    // ---- refill: idle lanes pull consecutive items of the unit queues ---------------------------------
-    // An item is (hit, seed); 64 consecutive items of a queue are one unit = (chunk of 64 consecutive hits,
-    // seed).  Units are dealt to eight queues by chunk number; a wave serves the queue of the XCD it runs on
-    // first (so the seeds of one chunk -- thousands of rays leaving the same few voxels -- meet in ONE L2)
-    // and steals from the other queues when its own is dry.  As soon as `refill_min_lanes` lanes are idle
-    // they take the next items in queue order (one atomic per refill), so a wave does not drain down to its
-    // slowest sample before it gets new work.  Placement only affects speed.
-    const unsigned long long idle_mask = __ballot(st == ST_IDLE);
-    const uint32_t n_idle = (uint32_t)__popcll(idle_mask);
-    if (!exhausted && n_idle >= (uint32_t)a.refill_min_lanes) {
-      const uint32_t NQ = (uint32_t)a.unit_queues, S = (uint32_t)a.n_seeds, G = (uint32_t)a.unit_group;
-      const uint32_t KB = (uint32_t)a.unit_block_log2, n_blocks = (n_chunks + (1u << KB) - 1u) >> KB;
-      uint32_t base = 0u, count = 0u, q_sel = 0u;
-      if (lane == 0u) {
-        for (uint32_t tries = 0; tries < NQ && count == 0u; ++tries) {
-          const uint32_t q = (home_queue + tries) % NQ;
-          // blocks of 2^unit_block_log2 consecutive chunks are dealt round-robin to the queues (a block past the
-          // last chunk is padding: its items name hits that do not exist and are skipped)
-          const uint32_t blocks_q = (n_blocks + NQ - 1u - q) / NQ;
-          const uint32_t chunks_q = blocks_q << KB;
-          if (chunks_q == 0u || ((queue_dry >> q) & 1u)) continue;
-          const uint32_t total = chunks_q * S * 64u;
-          // every head sits on its own 128-byte line: same-address atomics serialise at one L2 channel
-          const uint32_t p = atomicAdd(&a.counters[32u * (q + 1u)], n_idle);
-          if (p + n_idle >= total) queue_dry |= 1u << q;  // remembered: never asked again
-          if (p < total) {
-            base = p;
-            count = min(n_idle, total - p);
-            q_sel = q;
-          }
-        }
-      }
-      base = __shfl(base, 0);
-      count = __shfl(count, 0);
-      q_sel = __shfl(q_sel, 0);
-#ifdef CLVR_BOUNCE_STATS
-      st_refills += 1; st_refill_lanes += count;
-#endif
-      if (count == 0u) {
-        exhausted = true;  // every queue is dry
-      } else if (st == ST_IDLE) {
-        const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull));
-        if (rank < count) {
-          const uint32_t item = base + rank, p = item >> 6;
-          // queue order: groups of `unit_group` chunks, inside a group seed-major -- the seeds of a chunk are
-          // `unit_group` units apart (their accumulation atomics do not collide) yet close enough to find
-          // each other's voxels still in L2
-          // (units per queue stay below 2^24: launch_bounce checks)
-          const uint32_t chunks_q = ((n_blocks + NQ - 1u - q_sel) / NQ) << KB;  // wave-uniform: scalar
-          uint32_t r, c_in;
-          const uint32_t g = udivmod24(p, G * S, r);
-          const uint32_t in_group = min(G, chunks_q - g * G);  // the last group may be short
-          const uint32_t s = udivmod24(r, in_group, c_in), ch = g * G + c_in;
-          const uint32_t chunk = ((q_sel + NQ * (ch >> KB)) << KB) + (ch & ((1u << KB) - 1u));
-          const uint32_t h = chunk * 64u + (item & 63u);
-          if (h < n_hits) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(&a.hits[h]);
-            const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-            const f3 hit_origin = f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
-            const f3 hit_direction = f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
-            const f3 start = hit_origin + hit_direction;  // ray_bounce_fake_reflectance's origin (utility_ray.cl:100-103)
-            color = q2.y;
-            const int64_t entry = (int64_t)(((uint64_t)q2.w << 32) | (uint64_t)q2.z);
-            bool granted = true;
-            if (MODE == CLWH_ACCUM_VOXEL_CACHE)
-              granted = a.grants ? s < a.grants[h] : (entry >= 0 && cache_take_token(a.cache, entry, 256u));
-            if (granted) {
-              COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
-              COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
-              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = q2.w;
-              COLD(C_PIXEL) = q3.x;
-              COLD(C_HIT) = h;
-              COLD(C_SEED) = (uint32_t)a.seeds[s];
-              COLD(C_FIX) = (uint32_t)(-1 + 2) << 2;
-              COLD(C_BV_R) = 0u; COLD(C_BV_G) = 0u; COLD(C_BV_B) = 0u;
-              r_energy = div255[color & 255u];
-              g_energy = div255[(color >> 8) & 255u];
-              b_energy = div255[(color >> 16) & 255u];
-              o = 1;
-              st = ST_EVENT + EV_START;
-            } else if (a.contrib_out) {
-              uint32_t *q = a.contrib_out + ((size_t)(q3.x >> 16) * (size_t)a.launch_w + (q3.x & 0xFFFFu)) * 4;
-              q[0] = 0u; q[1] = 0u; q[2] = 0u; q[3] = 0u;
-            }
-          }
-        }
-      }
-    }
-    if (__ballot(st != ST_IDLE) == 0ull) {
-#ifdef CLVR_BOUNCE_STATS
-      if (exhausted && lane == 0u) {
-        atomicAdd(&a.counters[8], st_step_iters); atomicAdd(&a.counters[9], st_step_lanes);
-        atomicAdd(&a.counters[10], st_event_phases); atomicAdd(&a.counters[11], st_event_lanes);
-        atomicAdd(&a.counters[12], st_refills); atomicAdd(&a.counters[13], st_refill_lanes);
-        for (int k = 0; k < 4; ++k) atomicAdd(&a.counters[14 + k], st_ev_kind[k]);
-        atomicAdd(&a.counters[18], st_cert_phases); atomicAdd(&a.counters[19], st_cert_lanes); atomicAdd(&a.counters[20], st_cert_granted);
-      }
-#endif
-      if (exhausted) break;  // nothing in flight and nothing left to fetch
-      continue;              // every fetched sample was refused its token (or was padding): fetch again
-    }
-
     // ---- step phase: MARCH lanes step until fewer than kStepPhaseMinLanes are still marching -----
     if (__ballot(st == ST_MARCH) != 0ull) {
       do {
 #ifdef CLVR_BOUNCE_STATS
         st_step_iters += 1; st_step_lanes += (uint32_t)__popcll(__ballot(st == ST_MARCH));
+        st_step_idle += (uint32_t)__popcll(__ballot(st == ST_IDLE));
 #endif
 #ifdef CLVR_EXP_STEP_PAD  // experiment: N extra dependent FMAs per step iteration
         {
@@ -830,7 +733,10 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
       } while (__popcll(__ballot(st == ST_MARCH)) >= a.step_min_lanes);
     }
 
-    // ---- event phase: every parked lane handles its event; the bounce is one shared block ---------
+    // ---- event phase, closing half: every parked lane handles its event, up to the end of its sample -----
+    // What the lane does next is left in `st` for the opening half: ST_EVENT + EV_START (start distribution ray `o` from the
+    // primary hit), + EV_HIT / EV_HIT_COLOR_PENDING (bounce from this hit; with i > 10 its bounced ray is not marched and ray
+    // `o` starts instead), + EV_NONE (march on); ST_IDLE when the sample has ended.  No vector crosses the refill between the halves.
 #ifdef CLVR_EXP_EVENT_PAD  // experiment: how sensitive is the launch to VALU work in the event phase?  N extra dependent FMAs per phase
     {
       float pad = ray.origin.x;
@@ -840,8 +746,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
     }
 #endif
 #ifdef CLVR_BOUNCE_STATS
-    st_event_phases += 1; st_event_lanes += (uint32_t)__popcll(__ballot(st >= ST_EVENT));
-    st_ev_kind[0] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_START));
+    const uint32_t st_closing = (uint32_t)__popcll(__ballot(st >= ST_EVENT));
+    st_event_lanes += st_closing;
     st_ev_kind[1] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_EXIT || st == ST_EVENT + EV_CHECK));
     st_ev_kind[2] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_HIT || st == ST_EVENT + EV_HIT_COLOR_PENDING));
     st_ev_kind[3] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_NONE));
@@ -867,10 +773,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           march -= kOneStep;
         }
       }
-      bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
-      bool bounce = false, from_hit = false;
-      f3 bn{0, 0, 0}, bstart{0, 0, 0};  // the bounce's normal and its origin + direction
-      int bseed = 0;                    // its seed, less the sample's
+      bool ended = false;  // distribution ray `o` has ended: the next one starts from the primary hit, or the sample is complete
 
       if (ev == EV_EXIT) {
         // ray_marching.cl:54-62: left the volume -> environment light ends this distribution ray
@@ -914,16 +817,167 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           COLD(C_FIX) = ((uint32_t)(fix + 2) << 2) | (uint32_t)npend;
         }
         o += 1;
-        start_path = true;
+        ev = EV_START;
+        ended = true;
       } else if (ev == EV_HIT || ev == EV_HIT_COLOR_PENDING) {
+        // ray_marching.cl:63-72: secondary hit; the bounce itself is the opening half's.  i > 10: third march of this
+        // distribution ray, see there
+        i += 1;
+        if (i > 10) {
+          o += 1;
+          ended = true;
+        }
+      } else if (ev == EV_NONE) {
+        // 70 steps without an event: the next march continues from where this one stopped
+        i += 1;
+        if (i > 10) {
+          o += 1;
+          ev = EV_START;
+          ended = true;
+        }
+      }
+
+      if (ended && o > 2) {
+        const int fix = (int)(COLD(C_FIX) >> 2) - 2;
+        if (fix == -1)
+          finish_item<MODE>(a, (int64_t)(((uint64_t)COLD(C_ENTRY_HI) << 32) | (uint64_t)COLD(C_ENTRY_LO)), COLD(C_HIT), COLD(C_PIXEL) & 0xFFFFu,
+                            COLD(C_PIXEL) >> 16, COLD(C_BV_R), COLD(C_BV_G), COLD(C_BV_B));
+        else if (fix >= 0) a.fixups[(size_t)fix * kFixupDwords + 7] = COLD(C_FIX) & 3u;  // k_env_fixup finishes it
+        st = ST_IDLE;
+      } else {
+        st = ST_EVENT + ev;
+      }
+    }
+
+    // ---- refill, between the two halves of the event phase: idle lanes pull consecutive items of the unit queues ----
+    // (ballots and shuffles: all 64 lanes pass here.)  A lane whose sample has just ended in the closing half takes its next
+    // item now and starts it in the opening half of the same pass; it never sits out a step run without a ray.
+    // An item is (hit, seed); 64 consecutive items of a queue are one unit = (chunk of 64 consecutive hits,
+    // seed).  Units are dealt to eight queues by chunk number; a wave serves the queue of the XCD it runs on
+    // first (so the seeds of one chunk -- thousands of rays leaving the same few voxels -- meet in ONE L2)
+    // and steals from the other queues when its own is dry.  As soon as `refill_min_lanes` lanes are idle
+    // they take the next items in queue order (one atomic per refill), so a wave does not drain down to its
+    // slowest sample before it gets new work.  Placement only affects speed.
+    const unsigned long long idle_mask = __ballot(st == ST_IDLE);
+    const uint32_t n_idle = (uint32_t)__popcll(idle_mask);
+    if (!exhausted && n_idle >= (uint32_t)a.refill_min_lanes) {
+      const uint32_t NQ = (uint32_t)a.unit_queues, S = (uint32_t)a.n_seeds, G = (uint32_t)a.unit_group;
+      const uint32_t KB = (uint32_t)a.unit_block_log2, n_blocks = (n_chunks + (1u << KB) - 1u) >> KB;
+      uint32_t base = 0u, count = 0u, q_sel = 0u;
+      if (lane == 0u) {
+        for (uint32_t tries = 0; tries < NQ && count == 0u; ++tries) {
+          const uint32_t q = (home_queue + tries) % NQ;
+          // blocks of 2^unit_block_log2 consecutive chunks are dealt round-robin to the queues (a block past the
+          // last chunk is padding: its items name hits that do not exist and are skipped)
+          const uint32_t blocks_q = (n_blocks + NQ - 1u - q) / NQ;
+          const uint32_t chunks_q = blocks_q << KB;
+          if (chunks_q == 0u || ((queue_dry >> q) & 1u)) continue;
+          const uint32_t total = chunks_q * S * 64u;
+          // every head sits on its own 128-byte line: same-address atomics serialise at one L2 channel
+          const uint32_t p = atomicAdd(&a.counters[32u * (q + 1u)], n_idle);
+          if (p + n_idle >= total) queue_dry |= 1u << q;  // remembered: never asked again
+          if (p < total) {
+            base = p;
+            count = min(n_idle, total - p);
+            q_sel = q;
+          }
+        }
+      }
+      base = __shfl(base, 0);
+      count = __shfl(count, 0);
+      q_sel = __shfl(q_sel, 0);
+#ifdef CLVR_BOUNCE_STATS
+      st_refills += 1; st_refill_lanes += count;
+#endif
+      if (count == 0u) {
+        exhausted = true;  // every queue is dry
+      } else if (st == ST_IDLE) {
+        const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull));
+        if (rank < count) {
+          const uint32_t item = base + rank, p = item >> 6;
+          // queue order: groups of `unit_group` chunks, inside a group seed-major -- the seeds of a chunk are
+          // `unit_group` units apart (their accumulation atomics do not collide) yet close enough to find
+          // each other's voxels still in L2
+          // (units per queue stay below 2^24: launch_bounce checks)
+          const uint32_t chunks_q = ((n_blocks + NQ - 1u - q_sel) / NQ) << KB;  // wave-uniform: scalar
+          uint32_t r, c_in;
+          const uint32_t g = udivmod24(p, G * S, r);
+          const uint32_t in_group = min(G, chunks_q - g * G);  // the last group may be short
+          const uint32_t s = udivmod24(r, in_group, c_in), ch = g * G + c_in;
+          const uint32_t chunk = ((q_sel + NQ * (ch >> KB)) << KB) + (ch & ((1u << KB) - 1u));
+          const uint32_t h = chunk * 64u + (item & 63u);
+          if (h < n_hits) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(&a.hits[h]);
+            const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+            const f3 hit_origin = f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
+            const f3 hit_direction = f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
+            const f3 start = hit_origin + hit_direction;  // ray_bounce_fake_reflectance's origin (utility_ray.cl:100-103)
+            color = q2.y;
+            const int64_t entry = (int64_t)(((uint64_t)q2.w << 32) | (uint64_t)q2.z);
+            bool granted = true;
+            if (MODE == CLWH_ACCUM_VOXEL_CACHE)
+              granted = a.grants ? s < a.grants[h] : (entry >= 0 && cache_take_token(a.cache, entry, 256u));
+            if (granted) {
+              COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
+              COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
+              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = q2.w;
+              COLD(C_PIXEL) = q3.x;
+              COLD(C_HIT) = h;
+              COLD(C_SEED) = (uint32_t)a.seeds[s];
+              COLD(C_FIX) = (uint32_t)(-1 + 2) << 2;
+              COLD(C_BV_R) = 0u; COLD(C_BV_G) = 0u; COLD(C_BV_B) = 0u;
+              r_energy = div255[color & 255u];
+              g_energy = div255[(color >> 8) & 255u];
+              b_energy = div255[(color >> 16) & 255u];
+              o = 1;
+              st = ST_EVENT + EV_START;  // ready to bounce from its primary hit
+            } else if (a.contrib_out) {
+              uint32_t *q = a.contrib_out + ((size_t)(q3.x >> 16) * (size_t)a.launch_w + (q3.x & 0xFFFFu)) * 4;
+              q[0] = 0u; q[1] = 0u; q[2] = 0u; q[3] = 0u;
+            }
+          }
+        }
+      }
+    }
+#ifdef CLVR_BOUNCE_STATS
+    {
+      // a fresh item's start counts as an event of this phase, as it did when it was served from its parked state
+      const uint32_t n_fresh = (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_START && o == 1));
+      st_ev_kind[0] += n_fresh; st_event_lanes += n_fresh;
+      if (st_closing + n_fresh != 0u) st_event_phases += 1;  // one phase, two halves
+    }
+#endif
+    if (__ballot(st != ST_IDLE) == 0ull) {
+#ifdef CLVR_BOUNCE_STATS
+      if (exhausted && lane == 0u) {
+        atomicAdd(&a.counters[8], st_step_iters); atomicAdd(&a.counters[9], st_step_lanes);
+        atomicAdd(&a.counters[10], st_event_phases); atomicAdd(&a.counters[11], st_event_lanes);
+        atomicAdd(&a.counters[12], st_refills); atomicAdd(&a.counters[13], st_refill_lanes);
+        for (int k = 0; k < 4; ++k) atomicAdd(&a.counters[14 + k], st_ev_kind[k]);
+        atomicAdd(&a.counters[18], st_cert_phases); atomicAdd(&a.counters[19], st_cert_lanes); atomicAdd(&a.counters[20], st_cert_granted);
+        atomicAdd(&a.counters[22], st_step_idle);  // ([21] is k_bounce2's)
+      }
+#endif
+      if (exhausted) break;  // nothing in flight and nothing left to fetch
+      continue;              // every fetched sample was refused its token (or was padding): fetch again (no lane marches, no lane has an event)
+    }
+
+    // ---- event phase, opening half: the bounce is one shared block, then the march's first SDF read ---------
+    if (st >= ST_EVENT) {
+      const int ev = st - ST_EVENT;
+      bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
+      bool bounce = false, from_hit = false;
+      f3 bn{0, 0, 0}, bstart{0, 0, 0};  // the bounce's normal and its origin + direction
+      int bseed = 0;                    // its seed, less the sample's
+
+      if (ev == EV_HIT || ev == EV_HIT_COLOR_PENDING) {
         // ray_marching.cl:63-72: secondary hit -> bounce around the local normal, attenuate; the rule colour (still
         // pending when the Hit came through the step byte) and the gradient arrive in one 8-byte load
         bn = -normalize3(hit_gradient_and_color<SMALL>(vol, a.tf, ray.origin, ev == EV_HIT_COLOR_PENDING, color));
         bstart = ray.origin + ray.direction;
-        bseed = o + i;
+        bseed = o + i - 1;  // (the closing half has counted this march already)
         bounce = true;
         from_hit = true;
-        i += 1;
         if (i > 10) {
           // third march of this distribution ray: the reference still multiplies the energies (they
           // carry into the next distribution ray) but its bounced ray is never marched
@@ -931,34 +985,17 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           g_energy *= div255[(color >> 8) & 255u];
           b_energy *= div255[(color >> 16) & 255u];
           bounce = false;
-          o += 1;
-          start_path = true;
-        }
-      } else if (ev == EV_NONE) {
-        // 70 steps without an event: the next march continues from where this one stopped
-        i += 1;
-        if (i > 10) {
-          o += 1;
           start_path = true;
         }
       }
 
       if (start_path) {
-        if (o > 2) {
-          const int fix = (int)(COLD(C_FIX) >> 2) - 2;
-          if (fix == -1)
-            finish_item<MODE>(a, (int64_t)(((uint64_t)COLD(C_ENTRY_HI) << 32) | (uint64_t)COLD(C_ENTRY_LO)), COLD(C_HIT), COLD(C_PIXEL) & 0xFFFFu,
-                              COLD(C_PIXEL) >> 16, COLD(C_BV_R), COLD(C_BV_G), COLD(C_BV_B));
-          else if (fix >= 0) a.fixups[(size_t)fix * kFixupDwords + 7] = COLD(C_FIX) & 3u;  // k_env_fixup finishes it
-          st = ST_IDLE;
-        } else {
-          // ray_marching.cl:48: bounce from the primary hit around the primary normal
-          bn = f3{__uint_as_float(COLD(C_NORMAL_X)), __uint_as_float(COLD(C_NORMAL_Y)), __uint_as_float(COLD(C_NORMAL_Z))};
-          bstart = f3{__uint_as_float(COLD(C_START_X)), __uint_as_float(COLD(C_START_Y)), __uint_as_float(COLD(C_START_Z))};
-          bseed = o;
-          bounce = true;
-          from_hit = false;
-        }
+        // ray_marching.cl:48: bounce from the primary hit around the primary normal
+        bn = f3{__uint_as_float(COLD(C_NORMAL_X)), __uint_as_float(COLD(C_NORMAL_Y)), __uint_as_float(COLD(C_NORMAL_Z))};
+        bstart = f3{__uint_as_float(COLD(C_START_X)), __uint_as_float(COLD(C_START_Y)), __uint_as_float(COLD(C_START_Z))};
+        bseed = o;
+        bounce = true;
+        from_hit = false;
       }
 
       if (bounce) {
@@ -981,12 +1018,10 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         ray = nr;
       }
 
-      if (st >= ST_EVENT) {
-        // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
-        sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
-        march = 70u * kOneStep + kCertReady;
-        st = ST_MARCH;
-      }
+      // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
+      sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
+      march = 70u * kOneStep + kCertReady;
+      st = ST_MARCH;
     }
   }
 #undef COLD
