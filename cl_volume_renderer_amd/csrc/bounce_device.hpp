@@ -1,0 +1,206 @@
+// bounce_device.hpp -- what the kernels of the `render` pass share around k_bounce / k_bounce2: small wave helpers, the lane states, the
+// end of a sample (finish_item, k_env_fixup's too), the fix-up record, the exit certificate's look-up, scheduling statistics.
+#pragma once
+#include "render_device.hpp"
+
+namespace clvr {
+
+__device__ __forceinline__ VolumePacked make_volume(const RenderArgs &a) {
+  return VolumePacked{a.grec, a.stepb, a.volume_lin, a.sdf_lin, a.X, a.Y, a.Z, a.NBX, a.NBY};
+}
+
+// n / d and n % d for n, d < 2^24 through the float reciprocal (a 32-bit integer division is ~35 VALU instructions)
+__device__ __forceinline__ uint32_t udivmod24(uint32_t n, uint32_t d, uint32_t &rem) {
+  // n < 2^24 and d < 2^24 convert exactly; the estimate's relative error is below 2^-22, so for the quotients met
+  // here (below 2^20, or d a power of two) it is off by at most one either way
+  uint32_t q = (uint32_t)((float)n * __builtin_amdgcn_rcpf((float)d));
+  uint32_t qd;
+  asm("v_mul_u32_u24 %0, %1, %2" : "=v"(qd) : "v"(q), "v"(d));
+  int32_t r = (int32_t)(n - qd);
+  if (r < 0) { q -= 1u; r += (int32_t)d; }
+  if (r >= (int32_t)d) { q += 1u; r -= (int32_t)d; }
+  rem = (uint32_t)r;
+  return q;
+}
+
+// number of set bits of `mask` below this lane
+__device__ __forceinline__ unsigned prefix_count(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+__device__ __forceinline__ unsigned lane_id() { return prefix_count(~0ull); }
+
+// The state of a ray in k_bounce / k_bounce2, one register: ST_IDLE (no item), ST_MARCH, ST_CERT (parked for an exit-certificate attempt),
+// or ST_EVENT + the pending event.
+enum : int { ST_IDLE = 0, ST_MARCH = 1, ST_CERT = 2, ST_EVENT = 8 };
+enum : int { EV_START = 3,              // start distribution ray `o` from the primary hit (a freshly fetched item: o = 1)
+             EV_HIT_COLOR_PENDING = 4,  // a Hit whose rule colour is still to be fetched (classify_step DEFER_COLOR)
+             EV_CHECK = 5 };            // the new position has no voxel: left the volume, or one of the rare in-between cases?
+constexpr int kCertNever = 255;         // no step is this long
+
+// Image-space accumulation of one launch: a sample adds r | g<<16 | b<<32 | 1<<48 to its HIT's 64-bit
+// delta with ONE atomic (a launch has at most 64 seeds and a contribution is at most 255, so no field can
+// carry); k_commit then folds the deltas into the caller's float4 buffer with plain read-modify-writes.
+// Four float atomics per sample were a quarter of the kernel's L2-missing requests.
+template <int MODE>
+__device__ __forceinline__ void finish_item(const RenderArgs &a, int64_t entry, uint32_t hit, uint32_t gx, uint32_t gy,
+                                            uint32_t bv_r, uint32_t bv_g, uint32_t bv_b) {
+  // ray_marching.cl:75-76: halve (dist_count = 2), then add
+  const uint32_t cr = (bv_r / 2u) & 0xFFFFu, cg = (bv_g / 2u) & 0xFFFFu, cb = (bv_b / 2u) & 0xFFFFu;
+  if (MODE == CLWH_ACCUM_VOXEL_CACHE && a.grants == nullptr) {
+    cache_add(a.cache, entry, cr, cg, cb, 0u);
+  } else {
+    const unsigned long long packed = (unsigned long long)cr | ((unsigned long long)cg << 16) |
+                                      ((unsigned long long)cb << 32) | (1ull << 48);
+    atomicAdd(a.delta + hit, packed);
+  }
+  if (a.contrib_out) {
+    uint32_t *q = a.contrib_out + ((size_t)gy * (size_t)a.launch_w + gx) * 4;
+    q[0] = cr; q[1] = cg; q[2] = cb; q[3] = 1u;
+  }
+}
+
+// Environment lookups use the certified fast path (env_fast.hpp).  A lookup that cannot be certified
+// (about one in a thousand) does not stall the lane: the sample's pending term {atten*energy, factor,
+// direction} goes into a fix-up record, the lane walks the rest of the sample as usual, and the tiny
+// k_env_fixup launch that follows evaluates the exact binary64 lookup and finishes the arithmetic in
+// the reference's order.  Every sample is accumulated exactly once, by one of the two kernels.
+constexpr int kFixupDwords = 32;  // one record = 128 B: header[4] bv_before[3] n_pending[1] 2 x {P[3] factor dir[3]}
+
+// Exit certificates.  A march that ends in Exit_volume contributes through its DIRECTION only (ray_marching.cl:54-62
+// samples the environment with current_ray.direction): where it leaves the volume is never used.  So when it can be
+// PROVEN that a march will leave the volume without a Hit within the steps it has left, its remaining steps -- far-field
+// fetches, one 128-byte line each, for a position nobody needs -- are skipped and the Exit event is raised at once; the
+// result is bit-identical.  The proof is one table lookup: the ray's coordinates are monotone, so the rest of its path
+// lies in the box between its macro cell (16^3 voxels) and the volume corner its direction octant heads for, and the
+// table (k_macro_table .. k_macro_bounds) holds, per cell and octant, the smallest SDF value of that box if it is
+// free: no voxel that could be an event (a Hit needs one) and SDF values of at least kCertMinStep.  The ray's distance to the face it
+// leaves through, divided by that minimum, bounds the steps the march still takes; the bound must fit the march's budget (a march that ran out of steps would continue as the NEXT march,
+// with another weight, ray_marching.cl:52-73).  tools/exit_certificate.py measured the idea on the oracle first: every
+// exiting ray gets its certificate at some point, 5 of the 30 step fetches per item disappear (all far field), and not
+// one certificate in millions was wrong.
+// `away`: after a refusal, the path length the march has to cover before a look-up can succeed ((g - 1) cells, k_macro_hints); 0 when
+// the table does not say (the box is free but the budget too small, or one of the rare directions)
+__device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget, int &away) {
+  // the position has a voxel or sits on the far face: 0 <= p <= dim (or -0.0)
+  const unsigned cx = min((unsigned)(int)p.x >> a.macro_shift, (unsigned)a.MNX - 1u), cy = min((unsigned)(int)p.y >> a.macro_shift, (unsigned)a.MNY - 1u),
+                 cz = min((unsigned)(int)p.z >> a.macro_shift, (unsigned)a.MNZ - 1u);
+  const unsigned octant = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+  const int entry = a.macro[(((cz * (unsigned)a.MNY + cy) * (unsigned)a.MNX + cx) << 3) | octant];  // (at most 2^22 entries)
+  const bool refused = (entry & (int)kCertRefused) != 0;
+  const int box_min = refused ? 0 : entry;
+  away = refused ? ((entry & 0x7F) - 1) << a.macro_shift : 0;
+  // One kind of position is outside the reasoning below: a coordinate that landed exactly ON the far face (== dimension: not exited,
+  // utility_ray.cl:112-117) reads the border SDF 0 and advances 0.5 |d| per step; with a direction component too small to move that
+  // coordinate (0.5 x 2^-10 is above half an ulp of every dimension below 2^13) the reference can crawl along the face and even run
+  // out of its 70 steps.  Such directions get no certificate and march literally; for all others the next step leaves (the 5).
+  const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+  const float dsum = d.x + d.y + d.z;  // NaN direction: the position turns NaN and never leaves
+  // Every step inside the box is max(sdf, 0.5) >= box_min long and the direction has unit length, so after (budget - 5) steps the march has
+  // travelled T = (budget - 5) * box_min along the ray (an integer below 2^14: exact) and has passed the face of an axis as soon as
+  // T * |d_axis| >= its distance to that face -- one axis is enough; the 5 steps kept back cover the roundings of the march, of these three
+  // products, and the strictness of exited_volume.  (Round 3 first took the smallest (face - p) / d over the axes: three reciprocals,
+  // quarter-rate instructions, for the same decision.)
+  const float T = (float)((budget - 5) * box_min);
+  const float fx = d.x < 0.0f ? p.x : (float)a.X - p.x, fy = d.y < 0.0f ? p.y : (float)a.Y - p.y, fz = d.z < 0.0f ? p.z : (float)a.Z - p.z;
+  const bool leaves = T * fabsf(d.x) >= fx || T * fabsf(d.y) >= fy || T * fabsf(d.z) >= fz;
+  return box_min != 0 && budget > 5 && leaves && dmin >= 0.0009765625f && dsum == dsum;
+}
+__device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
+  int away;
+  return certify_exit(a, p, d, budget, away);
+}
+
+// ---- what k_bounce and k_bounce2 share word for word: the LDS index tables, the home queue and the scheduling statistics
+// SMALL == 2: the per-axis index terms are read from LDS (packed_volume.hpp); the block's `threads` threads fill the tables
+template <int SMALL>
+__device__ __forceinline__ void index_tables_to_lds(VolumePacked &vol, const RenderArgs &a, int threads) {
+  extern __shared__ uint32_t lds_parts[];
+  if (SMALL == 2) {
+    vol.parts = lds_parts;
+    vol.parts_y0 = a.X;
+    vol.parts_z0 = a.X + a.Y;
+    for (int k = (int)threadIdx.x; k < a.X + a.Y + a.Z; k += threads)
+      lds_parts[k] = k < a.X ? vol.part_x<1>((unsigned)k) : (k < a.X + a.Y ? vol.part_y<1>((unsigned)(k - a.X)) : vol.part_z<1>((unsigned)(k - a.X - a.Y)));
+  }
+}
+// the unit queue a wave serves first
+__device__ __forceinline__ unsigned home_queue_of(const RenderArgs &a, unsigned waves_per_block) {
+  // HW_REG_XCC_ID (id 20), bits [3:0]: the XCD this wave runs on
+  unsigned home_queue = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;
+  if (a.unit_affinity == 1) home_queue = (blockIdx.x * waves_per_block + (threadIdx.x >> 6)) & 7u;
+  if (a.unit_affinity == 2) home_queue = 0u;
+  return home_queue;
+}
+
+// Scheduling statistics of a launch (-DCLVR_BOUNCE_STATS, experiment builds: clwh_render.hip prints them).  A wave counts in
+// registers and lane 0 adds the sums to the CTR_* slots when the wave ends.  In a product build the struct is empty and so is every
+// method, ballots included.
+#ifdef CLVR_BOUNCE_STATS
+constexpr bool kBounceStats = true;
+#else
+constexpr bool kBounceStats = false;
+#endif
+template <bool ON> struct BounceStatsT;
+template <> struct BounceStatsT<false> {
+  __device__ void step(int) {}
+  __device__ void cert_begin(int, int) {}
+  __device__ void cert_end(int, int) {}
+  __device__ void closing_half(int) {}
+  __device__ void event_phase(int) {}
+  __device__ void refill(uint32_t) {}
+  __device__ void fresh_items(int, int) {}
+  __device__ void swap_point() {}
+  template <bool TWO_RAYS> __device__ void flush(uint32_t *) {}
+};
+template <> struct BounceStatsT<true> {
+  uint32_t step_iters = 0, step_lanes = 0, event_phases = 0, event_lanes = 0, refills = 0, refill_lanes = 0;
+  uint32_t ev_kind[4] = {0, 0, 0, 0};
+  uint32_t cert_phases = 0, cert_lanes = 0, cert_granted = 0;
+  uint32_t step_idle = 0;  // idle lanes, summed over the step iterations
+  uint32_t swaps = 0;      // k_bounce2's swap points
+  uint32_t closing = 0, marching_before = 0;  // lanes of this pass's closing half; marching lanes before this certificate phase
+  // a step iteration
+  __device__ __forceinline__ void step(int st) {
+    step_iters += 1; step_lanes += (uint32_t)__popcll(__ballot(st == ST_MARCH));
+    step_idle += (uint32_t)__popcll(__ballot(st == ST_IDLE));
+  }
+  // a certificate phase of `n_cert` lanes, before and after the look-ups
+  __device__ __forceinline__ void cert_begin(int st, int n_cert) {
+    cert_phases += 1; cert_lanes += (uint32_t)n_cert;
+    marching_before = (uint32_t)__popcll(__ballot(st == ST_MARCH));
+  }
+  __device__ __forceinline__ void cert_end(int st, int n_cert) { cert_granted += (uint32_t)(n_cert - (__popcll(__ballot(st == ST_MARCH)) - (int)marching_before)); }
+  // k_bounce: the closing half of an event phase
+  __device__ __forceinline__ void closing_half(int st) {
+    closing = (uint32_t)__popcll(__ballot(st >= ST_EVENT));
+    event_lanes += closing;
+    ev_kind[1] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_EXIT || st == ST_EVENT + EV_CHECK));
+    ev_kind[2] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_HIT || st == ST_EVENT + EV_HIT_COLOR_PENDING));
+    ev_kind[3] += (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_NONE));
+  }
+  // k_bounce2: its one-piece event phase
+  __device__ __forceinline__ void event_phase(int st) {
+    if (__ballot(st >= ST_EVENT) != 0ull) { event_phases += 1; event_lanes += (uint32_t)__popcll(__ballot(st >= ST_EVENT)); }
+  }
+  __device__ __forceinline__ void refill(uint32_t count) { refills += 1; refill_lanes += count; }
+  // k_bounce, before the opening half: a fresh item's start counts as an event of this phase (as when it was served from its parked state)
+  __device__ __forceinline__ void fresh_items(int st, int o) {
+    const uint32_t n_fresh = (uint32_t)__popcll(__ballot(st == ST_EVENT + EV_START && o == 1));
+    ev_kind[0] += n_fresh; event_lanes += n_fresh;
+    if (closing + n_fresh != 0u) event_phases += 1;  // one phase, two halves
+  }
+  __device__ __forceinline__ void swap_point() { swaps += 1; }
+  // lane 0 of a wave that ends
+  template <bool TWO_RAYS> __device__ __forceinline__ void flush(uint32_t *counters) {
+    atomicAdd(&counters[CTR_STEP_ITERS], step_iters); atomicAdd(&counters[CTR_STEP_LANES], step_lanes);
+    atomicAdd(&counters[CTR_EVENT_PHASES], event_phases); atomicAdd(&counters[CTR_EVENT_LANES], event_lanes);
+    atomicAdd(&counters[CTR_REFILLS], refills); atomicAdd(&counters[CTR_REFILL_LANES], refill_lanes);
+    if (TWO_RAYS) { atomicAdd(&counters[CTR_SWAPS], swaps); return; }
+    for (int k = 0; k < 4; ++k) atomicAdd(&counters[CTR_EV_KIND + k], ev_kind[k]);
+    atomicAdd(&counters[CTR_CERT_PHASES], cert_phases); atomicAdd(&counters[CTR_CERT_LANES], cert_lanes);
+    atomicAdd(&counters[CTR_CERT_GRANTED], cert_granted); atomicAdd(&counters[CTR_STEP_IDLE], step_idle);
+  }
+};
+using BounceStats = BounceStatsT<kBounceStats>;
+
+}  // namespace clvr

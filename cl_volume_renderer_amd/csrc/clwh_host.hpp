@@ -173,7 +173,7 @@ struct PrimaryHits {
 
 // work buffers of one pass
 struct PassScratch {
-  static constexpr size_t kCounters = 32 * 9;
+  static constexpr size_t kCounters = CTR_QUEUE_STRIDE * 9;  // the first line and eight queue heads
   DeviceBuffer counters;      // kCounters x u32 on the device
   DeviceBuffer fixups, delta;
   DeviceBuffer sticky_flags;  // [0] fix-up buffer overflow: set by kernels, cleared only when the host has read it

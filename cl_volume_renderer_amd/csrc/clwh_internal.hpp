@@ -45,13 +45,27 @@ static_assert(sizeof(HitRec) == 64, "HitRec must be one 64-byte line");
 
 enum : uint32_t { PIX_HIT = 0x80000000u };  // pix_slot: PIX_HIT | hit index, else the miss colour (rgb)
 
+// format of the exit-certificate table, shared by its builder (scene_kernels.hip) and its reader (certify_exit, bounce_device.hpp)
+constexpr uint32_t kCertMinStep = 2u;     // a box whose smallest SDF value is below this counts as not free
+constexpr uint32_t kCertRefused = 0x80u;  // bit 7 of an entry: the box is not free (box minima are SDF values, at most 127)
+
+// slots of RenderArgs::counters (cleared per camera from CTR_HITS on, per launch behind it)
+enum : uint32_t {
+  CTR_HITS = 0, CTR_FIXUPS = 2,  // primary hits of this camera (k_primary); fix-up records of this launch
+  // -DCLVR_BOUNCE_STATS builds: scheduling statistics (BounceStats, bounce_device.hpp), sums over the launch's waves
+  CTR_STEP_ITERS = 8, CTR_STEP_LANES, CTR_EVENT_PHASES, CTR_EVENT_LANES, CTR_REFILLS, CTR_REFILL_LANES,
+  CTR_EV_KIND,     // four slots: start / exit / hit / none
+  CTR_CERT_PHASES = CTR_EV_KIND + 4, CTR_CERT_LANES, CTR_CERT_GRANTED,
+  CTR_SWAPS, CTR_STEP_IDLE, CTR_STATS_END,  // k_bounce2 only: swap points; k_bounce only: idle lanes, summed over the step iterations
+  CTR_QUEUE_STRIDE = 32,  // head of unit queue q: slot CTR_QUEUE_STRIDE * (q + 1), every head on its own 128-byte line
+};
 struct RenderArgs {
   int32_t X, Y, Z;
   const uint2 *grec;       // bricked hit records {gx, gy, gz, class} (packed_volume.hpp)
   const uint8_t *stepb;    // bricked per-step bytes (packed_volume.hpp)
   const int16_t *volume_lin;  // the caller's images (x fastest): literal taps of the rare paths
   const int8_t *sdf_lin;
-  // exit certificates (render_kernels.hip, certify_exit): eight bytes per macro cell of 16^3 voxels; byte o: the smallest SDF value in
+  // exit certificates (bounce_device.hpp, certify_exit): eight bytes per macro cell of 16^3 voxels; byte o: the smallest SDF value in
   // the box a march from this cell in direction octant o crosses until it leaves the volume (1..127), or, when the box is not free,
   // 0x80 | the number of cells along the octant's diagonal until it is (k_macro_hints)
   const uint8_t *macro;
@@ -81,13 +95,13 @@ struct RenderArgs {
   const uint32_t *grants;
   uint32_t *pix_slot;      // tile-major, per pixel: PIX_HIT | hit index, or the miss colour
   HitRec *hits;            // compacted primary hits of this camera
-  uint32_t *counters;      // [0] hits (k_primary), [2] fix-up records, [32*(q+1)] unit-queue heads, one per 128-B line
+  uint32_t *counters;      // the CTR_* slots above
   uint32_t *fixups;        // 128-byte records of samples whose env lookup needs the exact route
   uint32_t fixup_capacity;
   uint32_t *sticky_flags;  // [0] fix-up overflow (outside the per-launch reset range: survives until the host reads it)
-  uint32_t n_hits;         // host copy of counters[0], or an upper bound of it when n_hits_on_device
+  uint32_t n_hits;         // host copy of counters[CTR_HITS], or an upper bound of it when n_hits_on_device
   uint32_t n_hits_estimate;  // the likely count (the count itself once known): picks the scheduling class of the launch
-  int32_t n_hits_on_device;  // 1: kernels read the hit count from counters[0] (no host round trip after k_primary)
+  int32_t n_hits_on_device;  // 1: kernels read the hit count from counters[CTR_HITS] (no host round trip after k_primary)
   int32_t shading;         // clwh_shading
   int64_t *hit_index_out;  // optional, row-major over launch_w x launch_h
   uint32_t *contrib_out;   // optional, row-major uint32[4] (single seed)

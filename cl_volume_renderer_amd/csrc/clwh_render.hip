@@ -1,5 +1,5 @@
 // clwh_render.hip -- clwh_render on the host: the registry of derived scene data, the camera's primary hits, one pass;
-// and the entry points that resolve an image-space accumulation.  The kernels are in render_kernels.hip.
+// and the entry points that resolve an image-space accumulation.  The kernels: {scene,primary,render,accumulate}_kernels.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -301,7 +301,7 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
   // the camera's hit count follows on the stream into page-locked memory; nobody waits for it
   CLWH_TRY(p.host_n_hits.ensure());
   CLWH_TRY(p.n_hits_event.ensure(hipEventDisableTiming));
-  HIP_TRY(hipMemcpyAsync(p.host_n_hits.ptr, a.counters, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(p.host_n_hits.ptr, a.counters + CTR_HITS, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipEventRecord(p.n_hits_event.ev, ctx->stream));
   p.n_hits_in_flight = true;
   ctx->vox.valid = false;
@@ -313,7 +313,7 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
 
 // stage 5: the hit count, or what stands in for it.
 // No host round trip per camera (the reference's queue is one in-order queue without a readback between camera and pass,
-// app/renderer.cpp:145-150).  The kernels read the hit count from counters[0] themselves; the host only needs a bound of it
+// app/renderer.cpp:145-150).  The kernels read the hit count from counters[CTR_HITS] themselves; the host only needs a bound of it
 // for grid and buffer sizes, and uses the real count as soon as the copy above has arrived by itself.
 static int pick_up_hit_count(clwh_ctx *ctx, RenderArgs &a) {
   PrimaryHits &p = ctx->primary;
@@ -360,7 +360,7 @@ static int size_pass_buffers(clwh_ctx *ctx, RenderArgs &a) {
   return CLWH_OK;
 }
 
-// stage 6b: a voxel-cache launch of several seeds deals its tokens out beforehand (render_kernels.hip "planned voxel-cache
+// stage 6b: a voxel-cache launch of several seeds deals its tokens out beforehand (accumulate_kernels.hip "planned voxel-cache
 // launches"); one seed per launch -- the reference's call pattern, and the per-pixel contribution output of the parity tests --
 // keeps the reference's token-per-sample protocol
 static int plan_voxel_grants(clwh_ctx *ctx, RenderArgs &a) {
@@ -392,17 +392,17 @@ static int plan_voxel_grants(clwh_ctx *ctx, RenderArgs &a) {
 
 #ifdef CLVR_BOUNCE_STATS  // experiment builds only (CLVR_EXTRA_HIPCC_FLAGS=-DCLVR_BOUNCE_STATS): scheduling statistics of the launch
 static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
-  uint32_t h[23];
+  uint32_t h[CTR_STATS_END];
   HIP_TRY(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  auto per = [&](int sum, int n) { return h[n] ? (double)h[sum] / h[n] : 0.0; };
   std::fprintf(stderr, "[bounce stats] items=%llu step_iters=%u avg_march_lanes=%.2f event_phases=%u avg_event_lanes=%.2f "
                "refills=%u avg_refill=%.2f events start/exit/hit/none=%u/%u/%u/%u cert_phases=%u avg_cert_lanes=%.2f cert_granted=%u\n",
-               (unsigned long long)h[0] * (unsigned long long)a.n_seeds, h[8], h[8] ? (double)h[9] / h[8] : 0.0, h[10],
-               h[10] ? (double)h[11] / h[10] : 0.0, h[12], h[12] ? (double)h[13] / h[12] : 0.0, h[14], h[15], h[16], h[17], h[18],
-               h[18] ? (double)h[19] / h[18] : 0.0, h[20]);
-  if (h[21]) std::fprintf(stderr, "[bounce stats] two rays per lane: %u swap points\n", h[21]);
-  // k_bounce: idle lanes while the wave steps ([21] belongs to k_bounce2)
-  std::fprintf(stderr, "[bounce stats] per step iteration: avg_idle_lanes=%.2f (lane sum %u)\n", h[8] ? (double)h[22] / h[8] : 0.0, h[22]);
+               (unsigned long long)h[CTR_HITS] * (unsigned long long)a.n_seeds, h[CTR_STEP_ITERS], per(CTR_STEP_LANES, CTR_STEP_ITERS),
+               h[CTR_EVENT_PHASES], per(CTR_EVENT_LANES, CTR_EVENT_PHASES), h[CTR_REFILLS], per(CTR_REFILL_LANES, CTR_REFILLS), h[CTR_EV_KIND],
+               h[CTR_EV_KIND + 1], h[CTR_EV_KIND + 2], h[CTR_EV_KIND + 3], h[CTR_CERT_PHASES], per(CTR_CERT_LANES, CTR_CERT_PHASES), h[CTR_CERT_GRANTED]);
+  if (h[CTR_SWAPS]) std::fprintf(stderr, "[bounce stats] two rays per lane: %u swap points\n", h[CTR_SWAPS]);
+  std::fprintf(stderr, "[bounce stats] per step iteration: avg_idle_lanes=%.2f (lane sum %u)\n", per(CTR_STEP_IDLE, CTR_STEP_ITERS), h[CTR_STEP_IDLE]);
   return CLWH_OK;
 }
 #endif
@@ -447,7 +447,7 @@ int clwh_render(clwh_kernel *k, const clwh_render_desc *d) {
   CLWH_TRY(ensure_primary_hits(ctx, d, a));
   CLWH_TRY(pick_up_hit_count(ctx, a));
 
-  HIP_TRY(hipMemsetAsync(a.counters + 1, 0, (PassScratch::kCounters - 1) * sizeof(uint32_t), ctx->stream));
+  HIP_TRY(hipMemsetAsync(a.counters + CTR_HITS + 1, 0, (PassScratch::kCounters - CTR_HITS - 1) * sizeof(uint32_t), ctx->stream));
   if (a.contrib_out) HIP_TRY(hipMemsetAsync(a.contrib_out, 0, launch_pixels(a) * 16, ctx->stream));  // misses contribute nothing
 
   if (d->resolve_only) {

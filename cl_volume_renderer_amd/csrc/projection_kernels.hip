@@ -15,7 +15,7 @@ namespace clvr {
 
 // ------------------------------------------------------------------------------------------------
 // k_proj_repack: a block turns a 64 x 8 x 8 box of the caller's x-fastest image (eight bricks side by side, whole 128-byte lines of each
-// row) into brick order.  The box is read once with coalesced 16-byte loads into LDS (the staging of k_repack, render_kernels.hip); every
+// row) into brick order.  The box is read once with coalesced 16-byte loads into LDS (the staging of k_repack, scene_kernels.hip); every
 // wave then writes whole sub-bricks (64 lanes x 2 bytes = one line) and takes their minimum and maximum with the DPP wave minimum.
 constexpr int kProjRepackX = 64;
 __global__ __launch_bounds__(256) void k_proj_repack(const ProjRepackArgs a) {

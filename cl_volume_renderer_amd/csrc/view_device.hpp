@@ -157,7 +157,7 @@ struct NeverSkip {
 
 // ------------------------------------------------------------------------------------------------
 // a lane's pixel, its camera ray and its outputs
-// one wave per 8x8 pixel tile, tiles in XCD-contiguous order (as k_primary, render_kernels.hip), one lane per pixel
+// one wave per 8x8 pixel tile, tiles in XCD-contiguous order (as k_primary, primary_kernels.hip), one lane per pixel
 __device__ __forceinline__ void view_pixel(const ViewFrame &f, uint32_t &x, uint32_t &y) {
   const uint32_t slot = xcd_contiguous_slot(blockIdx.x, (uint32_t)f.num_tiles);
   const uint32_t tx = slot % (uint32_t)f.tiles_x, ty = slot / (uint32_t)f.tiles_x;

@@ -1,4 +1,4 @@
-"""-m gpu: the exit-certificate table says how long a refused march should stay away (csrc/render_kernels.hip k_macro_hints;
+"""-m gpu: the exit-certificate table says how long a refused march should stay away (csrc/scene_kernels.hip k_macro_hints;
 k_bounce packs the distance beside its step budget; CLWH_TUNE_CERT_HINT=0 ignores it).
 
 The table is read back through clwh_debug_macro_table and compared, cell by cell and octant by octant, with a numpy

@@ -1,5 +1,5 @@
 """-m gpu: the scheduling of the LONG k_bounce launch (lanes refill at 16 idle, the step loop ends at 16 marching lanes,
-exit certificates on: csrc/render_kernels.hip launch_bounce) against the oracle.
+exit certificates on: csrc/render_kernels.hip launch_bounce; certify_exit in csrc/bounce_device.hpp) against the oracle.
 
 Small scenes are short launches, where every wave marches its samples to completion and certificates are off, so the
 other parity tests do not reach that code.  `gpu_ctx_long` (conftest.py) is a context created under
