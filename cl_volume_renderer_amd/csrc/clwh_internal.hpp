@@ -188,7 +188,7 @@ hipError_t launch_ao(const RenderArgs &a, hipStream_t s);
 hipError_t launch_accum_resolve(const RenderArgs &a, const float4 *accum_all, hipStream_t s);
 hipError_t launch_accum_resolve_tiles(const RenderArgs &a, const float4 *accum, uint32_t *tiles_out, hipStream_t s);
 hipError_t launch_frame_from_tiles(const RenderArgs &a, const uint32_t *tiles_all, hipStream_t s);
-// ---- fused SDF build: one breadth-first layer over the active 8x8x8 tiles (sdf_kernels.hip)
+// ---- fused SDF build: one breadth-first layer over the active 8x8x8 tiles (sdf_front_kernels.hip)
 struct SdfFrontArgs {
   int8_t *sdf;
   int32_t X, Y, Z;
@@ -202,7 +202,7 @@ struct SdfFrontArgs {
   int32_t *counters;          // [i] != 0: layer i settled a voxel to a value < max_iterations; [0] != 0: some |v| == 1
 };
 
-// ---- fused SDF build, bit-parallel (sdf_kernels.hip): one bit per voxel, eight layers per launch
+// ---- fused SDF build, bit-parallel (sdf_bits_kernels.hip, sdf_bits_layers_kernels.hip): one bit per voxel, eight layers per launch
 struct SdfBitArgs {
   int8_t *sdf;
   const uint32_t *ev;      // event bit per voxel, rows of WP 32-bit words
@@ -232,6 +232,9 @@ hipError_t launch_sdfbit_expand(const SdfBitArgs &a, const uint32_t *reached, in
 hipError_t launch_sdfbit_state(const SdfBitArgs &a, hipStream_t s);                              // block states of a.r_in
 hipError_t launch_sdfbit_layers(const SdfBitArgs &a, int waves, unsigned grid_blocks, bool rec_in_lds, hipStream_t s);
 
+// block and grid of the kernels that give a thread one voxel of an x-row (k_sdf_base, k_sdf_layer, k_apply_clip): blockIdx = (row chunk, y, z)
+inline unsigned row_block(int X) { return X <= 64 ? 64u : (X <= 128 ? 128u : 256u); }
+inline dim3 row_grid(int X, int Y, int Z) { return dim3(((unsigned)X + row_block(X) - 1u) / row_block(X), (unsigned)Y, (unsigned)Z); }
 hipError_t launch_sdf_base(const SdfArgs &a, hipStream_t s);
 hipError_t launch_sdf_base_front(const SdfArgs &a, uint8_t *flags, int32_t TX, int32_t TY, hipStream_t s);
 hipError_t launch_sdf_front(const SdfFrontArgs &a, hipStream_t s);

@@ -1,6 +1,6 @@
 // clwh_launch.hip -- clwh_kernel_get / clwh_launch: the reference's kernels found by their (file, entry) names and launched with
 // the reference kernels' own argument lists, by position.  One function per kernel; the pre-processing kernels they launch are in
-// volume_kernels.hip and sdf_kernels.hip, the render kernel goes through clwh_render.
+// volume_kernels.hip and sdf_layer_kernels.hip, the render kernel goes through clwh_render.
 #include <cmath>
 #include <cstring>
 #include <new>

@@ -1,5 +1,5 @@
 // clwh_sdf.hip -- clwh_sdf_build on the host: the signed distance field of (volume, transfer function) in one call.
-// The kernels are in sdf_kernels.hip.
+// The kernels are in sdf_front_kernels.hip, sdf_bits_kernels.hip and sdf_bits_layers_kernels.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +21,7 @@ static int read_settled(clwh_ctx *ctx, std::vector<int32_t> &settled) {
   return CLWH_OK;
 }
 
-// the byte front: one launch per layer over the active 8x8x8 tiles (sdf_kernels.hip); CLWH_TUNE_SDF=front
+// the byte front: one launch per layer over the active 8x8x8 tiles (sdf_front_kernels.hip); CLWH_TUNE_SDF=front
 static int sdf_build_front(clwh_ctx *ctx, SdfArgs &b, std::vector<int32_t> &settled) {
   const int X = b.X, Y = b.Y, Z = b.Z;
   const int TX = (X + 7) / 8, TY = (Y + 7) / 8, TZ = (Z + 7) / 8;
@@ -43,10 +43,7 @@ static int sdf_build_front(clwh_ctx *ctx, SdfArgs &b, std::vector<int32_t> &sett
 
   // layers that can still settle a voxel: i + 1 < max_iterations; the host looks at the per-layer
   // counts every kSdfLayersPerCheck launches and stops once a layer settled nothing (nothing can change after it)
-#ifndef CLVR_SDF_LAYERS_PER_CHECK
-#define CLVR_SDF_LAYERS_PER_CHECK 32  // measured 16 / 32 / 64 / 128: 5.31 / 5.21 / 5.14 / 5.19 ms for the 512^3 build
-#endif
-  constexpr int kSdfLayersPerCheck = CLVR_SDF_LAYERS_PER_CHECK;
+  constexpr int kSdfLayersPerCheck = 32;  // measured 16 / 32 / 64 / 128: 5.31 / 5.21 / 5.14 / 5.19 ms for the 512^3 build
   const int last_layer = a.max_iterations - 2;
   int i = 1;
   bool quiet = false;
@@ -88,7 +85,7 @@ static int print_sdfbit_regions(const SdfBitArgs &a, const uint32_t *queue, int 
   return CLWH_OK;
 }
 
-// the bit-parallel build: event bits -> seeds + base image -> eight layers per launch on one bit per voxel (sdf_kernels.hip)
+// the bit-parallel build: event bits -> seeds + base image -> eight layers per launch on one bit per voxel (sdf_bits_kernels.hip, sdf_bits_layers_kernels.hip)
 static int sdf_build_bits(clwh_ctx *ctx, SdfArgs &b, std::vector<int32_t> &settled) {
   const int X = b.X, Y = b.Y, Z = b.Z;
   SdfBitArgs a;

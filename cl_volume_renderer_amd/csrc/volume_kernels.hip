@@ -557,8 +557,6 @@ __global__ __launch_bounds__(256) void k_tf_flush_color_frame(uint32_t *color_fr
   color_frame[(size_t)y * fw + x] = c | (c << 8) | (c << 16) | (255u << 24);
 }
 
-static unsigned row_block(int X) { return X <= 64 ? 64u : (X <= 128 ? 128u : 256u); }
-
 hipError_t launch_bilateral_filter(const int16_t *src, int X, int Y, int Z, int16_t *dst, const float *weights, hipStream_t s) {
   const dim3 grid(((unsigned)X + kBfB - 1u) / kBfB, ((unsigned)Y + kBfB - 1u) / kBfB, ((unsigned)Z + kBfB - 1u) / kBfB);
   hipLaunchKernelGGL(k_bilateral_filter2, grid, dim3(kBfB * kBfB * kBfB / 2), 0, s, src, X, Y, Z, dst, weights);
@@ -592,9 +590,7 @@ hipError_t launch_apply_clip(const int16_t *src, int SX, int SY, int SZ, int16_t
     hipLaunchKernelGGL(k_apply_clip8, dim3((items + 255u) / 256u, (unsigned)DZ), dim3(256), 0, s, src, SX, SY, SZ, dst, DX, DY, DZ, start, len);
     return hipGetLastError();
   }
-  const unsigned b = row_block(DX);
-  hipLaunchKernelGGL(k_apply_clip, dim3(((unsigned)DX + b - 1u) / b, (unsigned)DY, (unsigned)DZ), dim3(b), 0, s, src, SX, SY,
-                     SZ, dst, DX, DY, DZ, start, len);
+  hipLaunchKernelGGL(k_apply_clip, row_grid(DX, DY, DZ), dim3(row_block(DX)), 0, s, src, SX, SY, SZ, dst, DX, DY, DZ, start, len);
   return hipGetLastError();
 }
 

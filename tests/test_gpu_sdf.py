@@ -159,6 +159,24 @@ def test_every_build_variant_on_awkward_shapes(gpu_ctx, gpu_ctx_sdf_waves16, gpu
     v.release(); s.release()
 
 
+@pytest.mark.parametrize("dims", [(512, 17, 6), (1024, 20, 5), (2048, 5, 3)])
+def test_wide_rows_take_the_sixteen_row_seed_and_expand_kernels(gpu_ctx, orc, dims):
+    """Rows of 16 / 32 / 64 words (X = 512 / 1024 / 2048) are seeded by k_sdfbit_seed_rows16<16 / 32 / 64> and expanded by
+    k_sdfbit_expand16_rows16<32 / 64 / 64>: launch branches that only wide volumes reach.  Y is no multiple of 16, so the last block of
+    sixteen rows leaves early for some of them; max_iterations is 127, so all sixteen layer launches run.  Every value and the
+    reference's launch count against the oracle."""
+    vol = _blobs(dims, seed=sum(dims) + 1)  # (+ 1: the blobs of seed sum(dims) fill (1024, 20, 5) completely -- nothing to build)
+    tf = scene.tf_default_source()
+    want, n_want, _ = orc.sdf_build(vol, orc.parse_tf(tf))
+    v, s = _upload(gpu_ctx, vol)
+    n = gpu_ctx.sdf_build(v, tf, s)
+    got = s.pull()
+    assert np.array_equal(got, want)
+    assert n == n_want
+    assert (np.abs(want.astype(np.int32)) > 1).any() or min(dims) < 4  # something was propagated
+    v.release(); s.release()
+
+
 def test_rebuild_after_a_transfer_function_change(gpu_ctx, orc):
     """the build's scratch (bit sets, block states, lists) is reused across builds: a second build with another table must not see the first"""
     vol = scene.phantom(96)
