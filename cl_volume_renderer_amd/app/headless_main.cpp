@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,6 +12,11 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
+// --grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
+// (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
+// JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
+// view, the mesh or the path-traced frames then show the masked volume.
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -41,6 +46,10 @@ int main(int argc_in, char const *argv_in[]) {
   float slice_position = 0.0f;
   bool mesh = false, mesh_below = false;
   float mesh_value = 0.0f;
+  bool grow = false, grow_remove = false;
+  uint32_t grow_seed[3] = {0, 0, 0};
+  int grow_lo = 0, grow_hi = 0, grow_flags = 0, grow_fill = -32768;
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -101,6 +110,46 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--mesh", 0) == 0) {
       std::cout << "Unknown option '" << a << "' (--mesh=VALUE or --mesh=VALUE,below)\n";
       return 1;
+    } else if (a.rfind("--grow=", 0) == 0) {
+      std::string rest = a.substr(7);
+      bool ok = true;
+      int field = 0;
+      for (; ok && (field == 0 || !rest.empty()); ++field) {
+        const size_t comma = rest.find(',');
+        const std::string v = rest.substr(0, comma);
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+        if (comma != std::string::npos && rest.empty()) ok = false;  // a trailing comma
+        char *end = nullptr;
+        if (field < 5) {
+          const long long n = std::strtoll(v.c_str(), &end, 10);
+          ok = ok && !v.empty() && *end == '\0';
+          if (field < 3) {
+            ok = ok && n >= 0 && n <= 0x7fffffffLL;
+            grow_seed[field] = (uint32_t)n;
+          } else {
+            ok = ok && n >= -32768 && n <= 32767;
+            (field == 3 ? grow_lo : grow_hi) = (int)n;
+          }
+        } else if (v == "26") {
+          grow_flags |= CLWH_GROW_26;
+        } else if (v == "keep" || v == "remove") {
+          grow_remove = v == "remove";
+        } else if (v.rfind("fill=", 0) == 0) {
+          const long n = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && n >= -32768 && n <= 32767;
+          grow_fill = (int)n;
+        } else {
+          ok = false;
+        }
+      }
+      if (!ok || field < 5 || grow_lo > grow_hi) {
+        std::cout << "Unknown option '" << a << "' " << kGrowUsage << "\n";
+        return 1;
+      }
+      grow = true;
+    } else if (a.rfind("--grow", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' " << kGrowUsage << "\n";
+      return 1;
     } else if (a.rfind("--slice=", 0) == 0) {
       std::string rest = a.substr(8);
       bool ok = true;
@@ -155,7 +204,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -175,6 +224,23 @@ int main(int argc_in, char const *argv_in[]) {
   image em = iloader.load_file(argv[2]);
   env_map emap(ctx, em);
   emitter->image_set(&rv, &emap);
+
+  if (grow) {  // first: everything below sees the masked volume
+    const auto &size = rv.get_volume_size();
+    for (int q = 0; q < 3; ++q)
+      if (grow_seed[q] >= size[q]) {
+        std::cout << "The --grow seed (" << grow_seed[0] << ", " << grow_seed[1] << ", " << grow_seed[2] << ") lies outside the volume\n";
+        return 1;
+      }
+    ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
+    const clwh_grow_result g = r.grow_region(none, {grow_seed[0], grow_seed[1], grow_seed[2]}, grow_lo, grow_hi, grow_flags);
+    r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
+    std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
+                "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d}\n",
+                grow_seed[0], grow_seed[1], grow_seed[2], grow_lo, grow_hi, (grow_flags & CLWH_GROW_26) ? 26 : 6, grow_remove ? "remove" : "keep",
+                grow_fill, (unsigned long long)g.count, g.bbox_lo[0], g.bbox_lo[1], g.bbox_lo[2], g.bbox_hi[0], g.bbox_hi[1], g.bbox_hi[2],
+                g.count ? (double)g.sum / (double)g.count : 0.0, g.vmin, g.vmax);
+  }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera
     ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};

@@ -134,6 +134,14 @@ void clvr_host_extract_mesh(clvr_host *h, float iso, int flags, unsigned long lo
 }
 // write_ply of that mesh; 1 on success
 int clvr_host_write_mesh_ply(clvr_host *h, const char *path) { return write_ply(path, h->mesh) ? 1 : 0; }
+// renderer::grow_region from n_seeds (x, y, z) triples: the statistics go to *result (a clwh_grow_result); the mask stays on the device
+void clvr_host_grow_region(clvr_host *h, const unsigned *seeds, unsigned n_seeds, int lo, int hi, int flags, void *result) {
+  const std::vector<uint32_t> list(seeds, seeds + (size_t)n_seeds * 3);
+  const clwh_grow_result r = h->rend.grow_region(h->state, list, lo, hi, flags);
+  std::memcpy(result, &r, sizeof r);
+}
+// renderer::apply_mask: the last grown mask applied to the renderer's volume in place
+void clvr_host_apply_mask(clvr_host *h, int fill, int flags) { h->rend.apply_mask(h->state, fill, flags); }
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

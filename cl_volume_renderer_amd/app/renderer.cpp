@@ -23,6 +23,7 @@ renderer::renderer(clw_context &c)
       buffer_volume(ctx, std::vector<unsigned short>(8 * 4)),
       tfframe(ctx, std::vector<unsigned char>(2 * 2 * 4), {2, 2, 1}),
       composite_lut(ctx, std::vector<float>(4)),
+      region_mask(ctx, std::vector<uint32_t>(2)),
       sdf(ctx) {}
 
 void renderer::image_set(const reference_volume *rv, const env_map *map) {
@@ -236,6 +237,36 @@ mesh_data renderer::extract_mesh(struct ui_state &, float iso, int flags) {
   out.keys.assign(&keys[0], &keys[0] + keys.size());
   out.triangles.assign(&triangles[0], &triangles[0] + triangles.size());
   return out;
+}
+
+clwh_grow_result renderer::grow_region(struct ui_state &, const std::vector<uint32_t> &seeds, int lo, int hi, int flags) {
+  const auto &size = volume->get_volume_size();
+  const size_t words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];  // the mask layout of clwh_segment_grow
+  if (region_mask.size() != words) {
+    if (flags & CLWH_GROW_FROM_MASK) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask of this volume to continue from
+    region_mask = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(words), false);
+  }
+  clwh_grow_result result{};
+  clwh_grow_desc d{};
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.mask = region_mask.get_device_reference();
+  d.lo = lo;
+  d.hi = hi;
+  d.flags = flags;
+  d.n_seeds = (uint32_t)(seeds.size() / 3);
+  d.seeds = seeds.data();
+  d.result = &result;
+  clw_fail_hard_on_error(clwh_segment_grow(ctx.get_handle(), &d));
+  return result;
+}
+
+void renderer::apply_mask(struct ui_state &, int fill, int flags) {
+  clwh_apply_mask_desc d{};
+  d.volume_in = d.volume_out = volume->get_reference_volume().get_device_reference();
+  d.mask = region_mask.get_device_reference();
+  d.fill = fill;
+  d.flags = flags;
+  clw_fail_hard_on_error(clwh_volume_apply_mask(ctx.get_handle(), &d));
 }
 
 // (the host is little-endian, like every target of the library: the arrays go out as they lie in memory)

@@ -81,6 +81,16 @@ class renderer : public frame_emitter {
   // Unlike the views it waits for the device; no camera takes part (`state` is not read).
   mesh_data extract_mesh(struct ui_state &state, float iso, int flags = 0);
 
+  // not in the reference: seeded region growing (clwh_segment_grow) on the volume the views show: the connected set of voxels with
+  // lo <= value <= hi that hangs together with `seeds` (x, y, z triples in voxels) under 6-connectivity, with CLWH_GROW_26 under
+  // 26-connectivity (flags: CLWH_GROW_26 | CLWH_GROW_FROM_MASK | CLWH_GROW_DENSE; FROM_MASK continues from the last mask).  The mask
+  // stays on the device for apply_mask; the statistics come back.  Waits for the device; no camera takes part (`state` is not read).
+  clwh_grow_result grow_region(struct ui_state &state, const std::vector<uint32_t> &seeds, int lo, int hi, int flags = 0);
+  // ... and the last grown mask applied to the volume in place (clwh_volume_apply_mask): voxels outside the region become `fill`, with
+  // CLWH_MASK_INVERT those inside.  Every view, the mesh and -- after the next flush_changes -- the path tracer then show the masked
+  // volume.  The host copy of the volume keeps the loaded values.
+  void apply_mask(struct ui_state &state, int fill = -32768, int flags = 0);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }
@@ -93,6 +103,7 @@ class renderer : public frame_emitter {
   clw_image<unsigned char, 4> tfframe;
   clw_vector<float> composite_lut;           // render_composite's table on the device (host copy = the last one pushed)
   bool composite_lut_pushed = false;
+  clw_vector<uint32_t> region_mask;          // grow_region's mask on the device (never pulled: the host side only sizes it)
   const reference_volume *volume = nullptr;  // borrowed
   const env_map *emap = nullptr;             // borrowed
   signed_distance_field sdf;

@@ -1,7 +1,7 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces and slices; clwh_mesh.hip: the
-// isosurface mesh).
+// isosurface mesh; clwh_grow.hip: region growing and masked volumes).
 // No kernel needs this header.
 #pragma once
 
@@ -208,6 +208,15 @@ struct SdfScratch {
 #endif
 };
 
+// clwh_segment_grow's scratch: the admissible bit image (one bit per voxel in the mask's layout); per tile of 64 x 16 x 16 voxels the round it
+// is to be visited in and its place in the round's list, behind them the round counters and the reduction's result; the copied seeds; and
+// the pinned line the counters and the result travel to the host in.  Every call rewrites what it reads, so nothing here outlives a
+// call: only the allocations are kept, and they go with the context.
+struct GrowScratch {
+  DeviceBuffer admissible, tiles, seeds;
+  PinnedWord host;
+};
+
 // intensity projections and compositing: the volume in brick order + the per-brick {min, max} table (one allocation, per context,
 // shared by clwh_render_projection and clwh_render_composite), and the key of the content it was built from (device pointer, shared
 // content version, dims).  Beside it the derived data of compositing's colour/opacity table: the prefix count of entries with
@@ -259,6 +268,7 @@ struct clwh_ctx {
   clvr::VoxelPlan vox;
   clvr::TfClasses classes;
   clvr::SdfScratch sdf;
+  clvr::GrowScratch grow;
   clvr::ProjectionData proj;
   clvr::DeviceBuffer bilateral_weights;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)
   // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per
@@ -330,6 +340,8 @@ inline bool is_image(const clwh_mem *m, int dims_n, int channels, int elem_kind)
   if (dims_n == 2) return m->dims[2] == 1;
   return true;
 }
+// an output of the mesher, a mask: a plain device buffer (clwh_mem_create / clwh_mem_wrap), not an image
+inline bool is_plain_buffer(const clwh_mem *m) { return m && m->dptr && !m->is_image; }
 inline bool same_dims(const clwh_mem *a, const clwh_mem *b) {
   return a->dims[0] == b->dims[0] && a->dims[1] == b->dims[1] && a->dims[2] == b->dims[2];
 }

@@ -364,4 +364,36 @@ hipError_t launch_mesh_count(const MeshArgs &a, hipStream_t s);
 hipError_t launch_mesh_scan(void *temp, size_t &temp_bytes, const uint64_t *counts, uint64_t *bases, size_t n, hipStream_t s);
 hipError_t launch_mesh_fill(const MeshArgs &a, hipStream_t s);  // k_mesh_vertices, then k_mesh_triangles if `triangles` is given
 
+// ---- seeded region growing and masked volumes (grow_kernels.hip; host side clwh_grow.hip).  Bit images (the mask R, the admissible
+// image A) hold a row of the volume as W64 = ceil(X / 64) 64-bit words, row (z * Y + y); the volume is cut into tiles of 64 x 16 x 16
+// voxels, tile (tx, ty, tz) at (tz * TY + ty) * TX + tx: one word of each of its 256 rows.
+constexpr int kGrowBatch = 8;  // rounds enqueued between two reads of the device's counters: {listed, ticket} x 8 = the 64 pinned bytes
+struct GrowDeviceResult {      // what k_grow_reduce accumulates (grow_result_identity: the start values)
+  unsigned long long count, sum, sum_sq;  // sum: int64 in two's complement
+  int32_t vmin, vmax;
+  uint32_t lo[3], hi[3];       // hi inclusive here
+};
+struct GrowArgs {
+  const int16_t *volume;       // the caller's image, x fastest
+  unsigned long long *mask;    // R
+  unsigned long long *adm;     // A
+  int32_t X, Y, Z, W64;
+  int32_t TX, TY, TZ;
+  int32_t lo, hi;              // the window
+  int32_t box_lo[3], box_hi[3];
+  int32_t conn26, from_mask, dense;
+  uint32_t *stamps;            // per tile: the round (1, 2, ...) in which it is to be visited
+  uint32_t *list;              // the tiles of the round being run
+  uint32_t *counters;          // kGrowBatch x {tiles listed, ticket}
+  const uint32_t *seeds;       // device copy, uint32[n_seeds][3]
+  uint32_t n_seeds;
+  GrowDeviceResult *result;
+};
+hipError_t launch_grow_admissible(const GrowArgs &a, hipStream_t s);  // A; mask &= A or mask = 0; stamps of the tiles that hold a bit
+hipError_t launch_grow_seeds(const GrowArgs &a, hipStream_t s);
+hipError_t launch_grow_round(const GrowArgs &a, uint32_t round, int slot, hipStream_t s);  // k_grow_list + k_grow_round, counters[2 * slot]
+hipError_t launch_grow_reduce(const GrowArgs &a, hipStream_t s);
+hipError_t launch_apply_mask(const int16_t *in, int16_t *out, const unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64,
+                             int32_t fill, int32_t invert, hipStream_t s);
+
 }  // namespace clvr

@@ -9,9 +9,6 @@
 
 using namespace clvr;
 
-// an output of the mesher: a plain device buffer (clwh_mem_create / clwh_mem_wrap), not an image
-static bool is_plain_buffer(const clwh_mem *m) { return m && m->dptr && !m->is_image; }
-
 extern "C" int clwh_mesh_isosurface(clwh_ctx *ctx, const clwh_mesh_desc *d) {
   if (!ctx || !d || !d->n_vertices || !d->n_triangles) return CLWH_ERR_INVALID_VALUE;
   if (!is_image(d->volume, 3, 1, CLWH_ELEM_S16)) return CLWH_ERR_INVALID_VALUE;

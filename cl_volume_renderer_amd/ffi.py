@@ -25,6 +25,9 @@ ISO_DENSE, ISO_BELOW = 1, 2
 SLICE_MAX, SLICE_MIN, SLICE_MEAN = 0, 1, 2
 SLICE_DENSE = 1
 MESH_DENSE, MESH_BELOW = 1, 2
+GROW_26, GROW_FROM_MASK, GROW_DENSE = 1, 2, 4
+GROW_MAX_SEEDS = 65536
+MASK_INVERT = 1
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -143,6 +146,38 @@ class MeshDesc(C.Structure):
     ]
 
 
+class GrowResult(C.Structure):
+    _fields_ = [
+        ("count", C.c_uint64),
+        ("bbox_lo", C.c_uint32 * 3), ("bbox_hi", C.c_uint32 * 3),
+        ("sum", C.c_int64), ("sum_sq", C.c_uint64),
+        ("vmin", C.c_int32), ("vmax", C.c_int32),
+        ("rounds", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        """the contract's fields (`rounds` is informational and left out)"""
+        return {"count": int(self.count), "bbox_lo": tuple(self.bbox_lo), "bbox_hi": tuple(self.bbox_hi), "sum": int(self.sum),
+                "sum_sq": int(self.sum_sq), "vmin": int(self.vmin), "vmax": int(self.vmax)}
+
+
+class GrowDesc(C.Structure):
+    _fields_ = [
+        ("volume", C.c_void_p), ("mask", C.c_void_p),
+        ("lo", C.c_int32), ("hi", C.c_int32), ("flags", C.c_int32),
+        ("n_seeds", C.c_uint32), ("seeds", C.POINTER(C.c_uint32)),
+        ("box_lo", C.c_uint32 * 3), ("box_hi", C.c_uint32 * 3),
+        ("result", C.POINTER(GrowResult)),
+    ]
+
+
+class ApplyMaskDesc(C.Structure):
+    _fields_ = [
+        ("volume_in", C.c_void_p), ("volume_out", C.c_void_p), ("mask", C.c_void_p),
+        ("fill", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -182,6 +217,8 @@ _PROTOTYPES = [
     ("clwh_render_isosurface", C.c_int, [C.c_void_p, C.POINTER(IsosurfaceDesc)]),
     ("clwh_render_slice", C.c_int, [C.c_void_p, C.POINTER(SliceDesc)]),
     ("clwh_mesh_isosurface", C.c_int, [C.c_void_p, C.POINTER(MeshDesc)]),
+    ("clwh_segment_grow", C.c_int, [C.c_void_p, C.POINTER(GrowDesc)]),
+    ("clwh_volume_apply_mask", C.c_int, [C.c_void_p, C.POINTER(ApplyMaskDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -542,6 +579,58 @@ class Context:
             for b in bufs:
                 if b is not None:
                     b.release()
+
+    def grow_region_raw(self, volume: Mem, seeds, lo, hi, flags=0, box=None, mask: Mem = None):
+        """one clwh_segment_grow call: (status, GrowResult); nothing is raised.  seeds: rows of (x, y, z), or None."""
+        d, res = GrowDesc(), GrowResult()
+        d.volume, d.mask = _handle(volume), _handle(mask)
+        d.lo, d.hi, d.flags = int(lo), int(hi), int(flags)
+        if seeds is not None:
+            s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint32).reshape(-1, 3))
+            d.n_seeds = len(s)
+            d.seeds = s.ctypes.data_as(C.POINTER(C.c_uint32))
+        if box is not None:
+            for k in range(3):
+                d.box_lo[k], d.box_hi[k] = int(box[0][k]), int(box[1][k])
+        d.result = C.pointer(res)
+        return lib().clwh_segment_grow(self.h, C.byref(d)), res
+
+    def grow_region(self, volume: Mem, seeds, lo, hi, connectivity=6, box=None, mask: Mem = None, from_mask=False, dense=False):
+        """the connected set of voxels of `volume` (S16) with lo <= value <= hi (inside box = ((lo), (hi)) in voxels, hi exclusive)
+        that hangs together with `seeds` (rows of (x, y, z)) under 6- or 26-connectivity: (mask, GrowResult).  The mask is one bit per
+        voxel in the layout scene.mask_pack / mask_unpack describe; it is allocated when none is given.  from_mask: the admissible
+        bits of `mask` on entry are seeds too (seeds may then be empty or None).  dense: every tile in every round (tests, timing).
+        The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        own = mask is None
+        if own:
+            from . import scene
+
+            if volume.shape is None or len(volume.shape) != 3:
+                raise ValueError("a volume without a [z][y][x] shape (a wrap): pass the mask buffer")
+            X, Y, Z = volume.shape[::-1]
+            n = scene.mask_words_per_row(X) * Y * Z
+            mask = self.buffer(4 * n, np.uint32, (n,))
+        flags = (GROW_26 if connectivity == 26 else 0) | (GROW_FROM_MASK if from_mask else 0) | (GROW_DENSE if dense else 0)
+        status, res = self.grow_region_raw(volume, seeds, lo, hi, flags, box, mask)
+        if status != OK and own:
+            mask.release()
+        _check(status, "clwh_segment_grow")
+        return mask, res
+
+    def apply_mask_raw(self, volume_in: Mem, mask: Mem, volume_out: Mem, fill=-32768, flags=0):
+        """one clwh_volume_apply_mask call: its status; nothing is raised"""
+        d = ApplyMaskDesc()
+        d.volume_in, d.volume_out, d.mask = _handle(volume_in), _handle(volume_out), _handle(mask)
+        d.fill, d.flags = int(fill), int(flags)
+        return lib().clwh_volume_apply_mask(self.h, C.byref(d))
+
+    def apply_mask(self, volume: Mem, mask: Mem, out: Mem = None, fill=-32768, invert=False):
+        """out = volume where the mask's bit is set (invert: where it is clear), `fill` elsewhere; out=None: in place.  Counts as a
+        rewrite of `out`: every view of it rebuilds its derived data at its next use."""
+        _check(self.apply_mask_raw(volume, mask, out if out is not None else volume, fill, MASK_INVERT if invert else 0),
+               "clwh_volume_apply_mask")
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -514,6 +514,87 @@ typedef struct clwh_mesh_desc {
 } clwh_mesh_desc;
 int clwh_mesh_isosurface(clwh_ctx *ctx, const clwh_mesh_desc *desc);
 
+/* ---- seeded region growing: the connected set of voxels inside a value window that hangs together with the seeds, as one bit per
+ * voxel, with its statistics (not in the reference): the first operation that says "this structure, not that one".  Every decision is
+ * an integer comparison and the result is a set, so it is defined bit for bit and does not depend on how the device schedules anything.
+ * The volume is V[z][y][x], an S16 3-D image with one channel and dims X, Y, Z.
+ * Admissible.  Voxel p is admissible iff lo <= V(p) <= hi (-32768 <= lo <= hi <= 32767) and box_lo.c <= p.c < box_hi.c on every axis.
+ * The box is given in voxels, box_lo.c <= box_hi.c <= dim_c; box_hi all zero means the whole volume; an empty box gives the empty set
+ * and CLWH_OK.
+ * Neighbours.  Two voxels are neighbours iff they differ by 1 in exactly one coordinate (6-connectivity); with CLWH_GROW_26 iff they
+ * differ by at most 1 in every coordinate and are not equal.  No clamping, no wrap-around: the border has no neighbours outside.
+ * Seeds.  `seeds` is a HOST pointer to uint32[n_seeds][3] = (x, y, z), n_seeds <= 65536, duplicates allowed.  A seed that is not
+ * admissible contributes nothing.  With CLWH_GROW_FROM_MASK every bit set in `mask` on entry whose voxel is admissible is a seed as
+ * well (n_seeds may then be 0): growing in two steps with different windows, or continuing after an edit.  Without the flag the
+ * contents of `mask` on entry are ignored.
+ * Result.  R is the smallest set that contains the admissible seeds and, with each of its voxels, that voxel's admissible neighbours.
+ * On return `mask` holds exactly R.
+ * Mask layout.  One bit per voxel, rows x-fastest, in 32-bit words: words_per_row = 2 * ((X + 63) / 64) (even: a row is a run of
+ * aligned 64-bit pairs); voxel (x, y, z) is bit x & 31 of word (z * Y + y) * words_per_row + (x >> 5).  Bits at x >= X and the padding
+ * words are zero on return, whatever the buffer held on entry without CLWH_GROW_FROM_MASK.  `mask` is a plain device buffer
+ * (clwh_mem_create, clwh_mem_wrap) whose device pointer is 8-byte aligned, of at least 4 * words_per_row * Y * Z bytes.
+ * Statistics.  *result (HOST, required), all exact integers: count; bbox_lo / bbox_hi, the smallest box holding R, hi exclusive (all
+ * zero when count == 0); sum of V over R; sum_sq of V * V over R; vmin / vmax over R (0 when count == 0); rounds, the number of rounds
+ * the iteration took: informational, may differ between calls, not part of the contract.
+ * SYNCHRONOUS, like clwh_mesh_isosurface: ordered on the context's stream, waits for the device, returns with mask and *result
+ * written.  The number of launches depends on the data (a vessel tree has a geodesic depth in the thousands).  CLWH_GROW_DENSE
+ * visits every tile of 64 x 16 x 16 voxels in every round instead of the worklist of tiles a neighbour's change woke: same bytes, by
+ * the contract.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a NULL or wrong-kind volume; a NULL
+ * mask, a mask that is an image or whose device pointer is not 8-byte aligned; unknown flag bits; a window or a box that breaks the
+ * rules above; n_seeds > 65536, n_seeds > 0 with NULL seeds, n_seeds == 0 without CLWH_GROW_FROM_MASK; a seed outside the volume;
+ * volume dims beyond the projections' rule.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than the layout needs.  CLWH_ERR_OUT_OF_MEMORY:
+ * scratch that cannot be allocated.  Nothing is written to `mask` or *result on any of these.  (CLWH_ERR_INTERNAL_OVERFLOW: the iteration
+ * passed its hard cap of X * Y * Z + 2 rounds, which no input can cause; the mask then holds a subset of R.)
+ * The caller's volume image is read directly: no derived data is built or invalidated.  The scratch (one bit per voxel, four bytes per
+ * tile, the copied seeds) is kept with the context and holds nothing between calls. */
+enum clwh_grow_flags {
+  CLWH_GROW_26 = 1,         /* 26-connectivity instead of 6 */
+  CLWH_GROW_FROM_MASK = 2,  /* the admissible bits of `mask` on entry are seeds too */
+  CLWH_GROW_DENSE = 4       /* every tile in every round: same result by contract; for tests and timing */
+};
+#define CLWH_GROW_MAX_SEEDS 65536
+typedef struct clwh_grow_result {
+  uint64_t count;
+  uint32_t bbox_lo[3], bbox_hi[3];
+  int64_t sum;
+  uint64_t sum_sq;
+  int32_t vmin, vmax;
+  uint32_t rounds;
+  uint32_t reserved;
+} clwh_grow_result;
+typedef struct clwh_grow_desc {
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  clwh_mem *mask;             /* plain device buffer in the mask layout */
+  int32_t lo, hi;             /* the value window, both ends included */
+  int32_t flags;
+  uint32_t n_seeds;
+  const uint32_t *seeds;      /* host; uint32[n_seeds][3] = x, y, z */
+  uint32_t box_lo[3], box_hi[3];  /* voxels; box_hi all zero = the whole volume */
+  clwh_grow_result *result;   /* host; required */
+} clwh_grow_desc;
+int clwh_segment_grow(clwh_ctx *ctx, const clwh_grow_desc *desc);
+
+/* ---- a mask applied to a volume (not in the reference): out(p) = (bit(p) != invert) ? in(p) : fill for every voxel, with bit(p) read in
+ * clwh_segment_grow's mask layout and invert = the flag CLWH_MASK_INVERT.  "Keep" with fill = -32768 followed by clwh_mesh_isosurface
+ * or clwh_render_isosurface at the window's lower bound shows or meshes only the grown structure; CLWH_MASK_INVERT with the value of
+ * air removes it.  volume_out may be volume_in, or another handle to the same pointer: the in-place case.
+ * Asynchronous and ordered on the context's stream, like the views.  It counts as a rewrite of volume_out: the content version that
+ * clwh_mem_push and clwh_mem_mark_dirty bump is bumped, so every derived data set keyed on that pointer (the bricked copy, the dilated
+ * tables, the packed scene) rebuilds at its next use, in this context and in contexts that share the pointer.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a NULL or wrong-kind volume_in or volume_out; a
+ * NULL mask, a mask that is an image or whose device pointer is not 8-byte aligned; unknown flag bits; fill outside [-32768, 32767];
+ * volume dims beyond the projections' rule.  CLWH_ERR_SIZE_MISMATCH: volumes of different dims; a mask smaller than the layout needs. */
+enum clwh_apply_mask_flags { CLWH_MASK_INVERT = 1 };
+typedef struct clwh_apply_mask_desc {
+  clwh_mem *volume_in;        /* S16 3-D image, 1 channel */
+  clwh_mem *volume_out;       /* the same dims; may name volume_in's memory */
+  clwh_mem *mask;             /* plain device buffer in the mask layout */
+  int32_t fill;               /* -32768 .. 32767 */
+  int32_t flags;
+} clwh_apply_mask_desc;
+int clwh_volume_apply_mask(clwh_ctx *ctx, const clwh_apply_mask_desc *desc);
+
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
  * per layer.  `sdf` is an S8 3-D image of the volume's dims.  n_launches (optional) receives the
