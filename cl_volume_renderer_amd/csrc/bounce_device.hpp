@@ -105,6 +105,14 @@ __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, in
   const bool leaves = T * fabsf(d.x) >= fx || T * fabsf(d.y) >= fy || T * fabsf(d.z) >= fz;
   return box_min != 0 && budget > 5 && leaves && dmin >= 0.0009765625f && dsum == dsum;
 }
+// Start certificates: `mask` is the byte of the first leg's start voxel in the "free from here" table (k_start_*, scene_kernels.hip), `d`
+// the leg's direction, `dmin_needed` start_cert_dmin (clwh_internal.hpp).  Octants as above; a NaN direction never leaves.
+__device__ __forceinline__ bool start_certificate(uint32_t mask, f3 d, float dmin_needed) {
+  const unsigned octant = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+  const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+  const float dsum = d.x + d.y + d.z;
+  return ((mask >> octant) & 1u) != 0u && dmin >= dmin_needed && dsum == dsum;
+}
 __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
   int away;
   return certify_exit(a, p, d, budget, away);
@@ -135,10 +143,14 @@ __device__ __forceinline__ unsigned home_queue_of(const RenderArgs &a, unsigned 
 // Scheduling statistics of a launch (-DCLVR_BOUNCE_STATS, experiment builds: clwh_render.hip prints them).  A wave counts in
 // registers and lane 0 adds the sums to the CTR_* slots when the wave ends.  In a product build the struct is empty and so is every
 // method, ballots included.
+// -DCLVR_BOUNCE_STATS also VERIFIES k_bounce's start certificates: a granted first leg is marched literally all the same and counted as
+// wrong unless it ends in Exit.  -DCLVR_BOUNCE_STATS=2 takes them as the product build does (its counts are the product build's).
 #ifdef CLVR_BOUNCE_STATS
 constexpr bool kBounceStats = true;
+constexpr bool kStartCertVerify = (CLVR_BOUNCE_STATS + 0) != 2;
 #else
 constexpr bool kBounceStats = false;
+constexpr bool kStartCertVerify = false;
 #endif
 template <bool ON> struct BounceStatsT;
 template <> struct BounceStatsT<false> {
@@ -150,6 +162,8 @@ template <> struct BounceStatsT<false> {
   __device__ void refill(uint32_t) {}
   __device__ void fresh_items(int, int) {}
   __device__ void swap_point() {}
+  __device__ void start_cert(bool, bool) {}
+  __device__ void march_end(uint32_t *, int) {}
   template <bool TWO_RAYS> __device__ void flush(uint32_t *) {}
 };
 template <> struct BounceStatsT<true> {
@@ -190,6 +204,18 @@ template <> struct BounceStatsT<true> {
     if (closing + n_fresh != 0u) event_phases += 1;  // one phase, two halves
   }
   __device__ __forceinline__ void swap_point() { swaps += 1; }
+  // k_bounce's start certificates; kStartCertVerify: a granted first leg is marched literally all the same, and when its march
+  // ends (closing half, any lane on its own) it counts as WRONG unless it ended in Exit -- a Hit, or 70 steps without an event
+  uint32_t start_tried = 0, start_granted = 0;
+  bool start_open = false;  // this lane's current march holds a start certificate
+  __device__ __forceinline__ void start_cert(bool tried, bool granted) {
+    start_tried += (uint32_t)__popcll(__ballot(tried)); start_granted += (uint32_t)__popcll(__ballot(granted));
+    start_open = start_open || granted;
+  }
+  __device__ __forceinline__ void march_end(uint32_t *counters, int ev) {
+    if (start_open && ev != EV_EXIT) atomicAdd(&counters[CTR_START_WRONG], 1u);
+    start_open = false;
+  }
   // lane 0 of a wave that ends
   template <bool TWO_RAYS> __device__ __forceinline__ void flush(uint32_t *counters) {
     atomicAdd(&counters[CTR_STEP_ITERS], step_iters); atomicAdd(&counters[CTR_STEP_LANES], step_lanes);
@@ -199,6 +225,7 @@ template <> struct BounceStatsT<true> {
     for (int k = 0; k < 4; ++k) atomicAdd(&counters[CTR_EV_KIND + k], ev_kind[k]);
     atomicAdd(&counters[CTR_CERT_PHASES], cert_phases); atomicAdd(&counters[CTR_CERT_LANES], cert_lanes);
     atomicAdd(&counters[CTR_CERT_GRANTED], cert_granted); atomicAdd(&counters[CTR_STEP_IDLE], step_idle);
+    atomicAdd(&counters[CTR_START_TRIED], start_tried); atomicAdd(&counters[CTR_START_GRANTED], start_granted);
   }
 };
 using BounceStats = BounceStatsT<kBounceStats>;

@@ -39,7 +39,8 @@ struct HitRec {
   int32_t entry_hi;
   uint32_t xy;         // global pixel: x | y<<16  (feeds the per-pixel RNG, utility_sampling.cl:41)
   uint32_t pslot;      // tile-major pixel slot of this rank (accumulation / scratch index)
-  uint32_t pad[2];
+  uint32_t start_free; // bits 0-7: the start-certificate byte at the voxel the hit's distribution rays start from (k_primary), else 0
+  uint32_t pad;
 };
 static_assert(sizeof(HitRec) == 64, "HitRec must be one 64-byte line");
 
@@ -56,7 +57,9 @@ enum : uint32_t {
   CTR_STEP_ITERS = 8, CTR_STEP_LANES, CTR_EVENT_PHASES, CTR_EVENT_LANES, CTR_REFILLS, CTR_REFILL_LANES,
   CTR_EV_KIND,     // four slots: start / exit / hit / none
   CTR_CERT_PHASES = CTR_EV_KIND + 4, CTR_CERT_LANES, CTR_CERT_GRANTED,
-  CTR_SWAPS, CTR_STEP_IDLE, CTR_STATS_END,  // k_bounce2 only: swap points; k_bounce only: idle lanes, summed over the step iterations
+  CTR_SWAPS, CTR_STEP_IDLE,  // k_bounce2 only: swap points; k_bounce only: idle lanes, summed over the step iterations
+  CTR_START_TRIED, CTR_START_GRANTED, CTR_START_WRONG,  // k_bounce only: start certificates (first legs of long launches); wrong: see BounceStats
+  CTR_STATS_END,
   CTR_QUEUE_STRIDE = 32,  // head of unit queue q: slot CTR_QUEUE_STRIDE * (q + 1), every head on its own 128-byte line
 };
 struct RenderArgs {
@@ -73,6 +76,10 @@ struct RenderArgs {
   int32_t cert_min_step;   // a march asks for a certificate once its next step is at least this long; 0 = certificates off
   int32_t cert_min_lanes;  // ... and the wave looks them up once this many lanes wait for one (launch_bounce sets it)
   int32_t cert_hint;       // 1: a refused march stays off the table for the distance the refusing entry names (k_macro_hints)
+  // start certificates (k_start_* in scene_kernels.hip): one byte per voxel, x fastest; bit o: no voxel of the box from this voxel to the
+  // volume corner of octant o may be an event.  k_primary copies the byte of a hit's start voxel into the hit record; nullptr: not built
+  const uint8_t *start_free;
+  float start_cert_dmin;   // a first leg is granted its certificate only if min |direction component| is at least this (start_cert_dmin below)
   int32_t NBX, NBY;
   const uint32_t *env;     // RGBA8 packed, row-major
   int32_t env_w, env_h;
@@ -166,6 +173,45 @@ inline int macro_cell_shift(int X, int Y, int Z, int forced) {
   return shift;
 }
 hipError_t launch_macro_table(const uint32_t *brick_min, int NBX, int NBY, int NBZ, uint8_t *macro, int X, int Y, int Z, int shift, hipStream_t s);
+// The start-certificate table of scene_kernels.hip: `regular` (one word) and `table` (X * Y * Z bytes) are written.
+hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s);
+// The largest step value the start certificate's bound counts on: the SDF build's layer count, min(127, largest dimension / 2)
+// (signed_distance_field.cpp), at which its values saturate.
+inline int start_cert_cap(int X, int Y, int Z) {
+  const int longest = X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z);
+  return longest / 2 < 127 ? longest / 2 : 127;
+}
+// The smallest min |direction component| (a multiple of 1/64) with which a first leg that holds a start certificate is PROVEN to leave
+// the volume within its 70 steps.  The leg's box -- from its start voxel to the volume corner its octant heads for -- holds no event
+// voxel, every one of its positions lies in that box (a march's coordinates are monotone in binary32), and the table is only built
+// from step bytes for which k_start_regular has checked that a voxel m >= 1 voxels (Chebyshev) from the nearest voxel that touches an
+// event has a step of at least min(cap, m + 1), cap = start_cert_cap, and every voxel that is no event a step of at least 1 (what
+// the converged SDF, min(D + 1, cap) with D the corner-neighbour distance to the nearest non-homogeneous voxel, gives: every
+// non-homogeneous voxel touches an event voxel).  After a path of length t every coordinate has moved at least t * dmin away from the
+// box's three inner faces, so the voxel is at least floor(t * dmin) - 2 voxels from each of them (one voxel for the start position's
+// fraction, one for the accumulated rounding of at most 70 additions), all voxels that close are in the box and hence no events, and
+// the step taken there is at least max(1, min(cap, floor(t * dmin) - 2)).  The bound grows with t and the real steps are no shorter,
+// so by induction the real path is at least as long as this recurrence's after every step.  Once t exceeds sqrt(3) * (largest
+// dimension + 1) the largest direction component (at least (1 - 2^-20) / sqrt(3) for a normalised direction) has carried its
+// coordinate out of the volume.  That has to happen within 70 - 5 steps: the 5 are certify_exit's reserve (a coordinate exactly on
+// the far face, the strictness of exited_volume).  The result is never below 1/64, far above the 2^-10 under which a ray can crawl
+// along the far face (certify_exit); 2 = no direction qualifies.
+inline float start_cert_dmin(int X, int Y, int Z) {
+  const double longest = (double)(X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z));
+  const double reach = 1.7320508075688772 * (longest + 1.0), cap = (double)start_cert_cap(X, Y, Z);
+  for (int k = 1; k <= 64; ++k) {
+    const double dmin = (double)k / 64.0;
+    double t = 0.0;  // (integers throughout: exact)
+    for (int step = 0; step < 70 - 5 && t <= reach; ++step) {
+      const double m = (double)(long long)(t * dmin) - 2.0;
+      const double bound = m > cap ? cap : m;
+      t += bound < 1.0 ? 1.0 : bound;
+    }
+    if (t > reach) return (float)dmin;
+  }
+  return 2.0f;
+}
+constexpr uint64_t kStartTableBudget = 2ull << 30;  // bytes (= voxels): larger volumes get no start certificates
 hipError_t launch_primary(const RenderArgs &a, hipStream_t s);
 hipError_t launch_bounce(const RenderArgs &a, hipStream_t s);
 // the bounce kernel's queue arithmetic needs ceil(hits / 64) x seeds below 2^24 (64 seeds: 16.7 M hit pixels); udivmod24

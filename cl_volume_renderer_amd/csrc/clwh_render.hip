@@ -26,9 +26,17 @@ PackedScene::~PackedScene() {
 // layout of a PackedScene's allocation
 struct PackedLayout {
   int X, Y, Z, NBX, NBY, NBZ, mshift, MNX, MNY, MNZ;
-  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, bytes;
+  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, off_start, bytes;
+  bool start_table;  // the start-certificate table is part of the allocation
 };
-static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift) {
+// Start certificates (k_start_*, scene_kernels.hip) are built for tables the step byte decides alone (no rule reads `gradient`), under
+// which the border texel is no event (the other exit certificates are off there too), for volumes whose table fits the budget (and the
+// build's grids), unless CLWH_TUNE_START_CERT=0.
+static bool wants_start_table(const Tuning &t, const TfDev &tf, const clwh_mem *volume) {
+  return t.start_cert != 0 && tf.uses_gradient == 0 && tf.border_class == 0 && fits_grid_yz(volume) &&
+         (uint64_t)volume->dims[0] * volume->dims[1] * volume->dims[2] <= kStartTableBudget;
+}
+static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift, bool start_table) {
   PackedLayout L;
   L.X = (int)volume->dims[0]; L.Y = (int)volume->dims[1]; L.Z = (int)volume->dims[2];
   L.NBX = (L.X + 7) / 8; L.NBY = (L.Y + 7) / 8; L.NBZ = (L.Z + 7) / 8;
@@ -41,13 +49,16 @@ static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift
   L.off_stepb = L.records * sizeof(uint2);
   L.off_brick_min = (L.records * (sizeof(uint2) + 1u) + 15u) & ~(size_t)15u;
   L.off_macro = (L.off_brick_min + L.n_bricks * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-  L.bytes = L.off_macro + (size_t)L.MNX * L.MNY * L.MNZ * 8u;  // eight octant entries per cell
+  L.off_start = (L.off_macro + (size_t)L.MNX * L.MNY * L.MNZ * 8u + 15u) & ~(size_t)15u;  // eight octant entries per cell
+  // the start-certificate table: 16 bytes for the `regular` word, then one byte per voxel, x fastest
+  L.start_table = start_table;
+  L.bytes = L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u);
   return L;
 }
 
 static bool packed_matches(const PackedScene &p, int device, const PackedLayout &L, const clwh_mem *volume, const clwh_mem *sdf,
                            const TfDev &tf, const std::string &tf_identity) {
-  return !p.stale && p.device == device && p.data.bytes == L.bytes && p.macro_shift == L.mshift && p.vol == volume->dptr &&
+  return !p.stale && p.device == device && p.data.bytes == L.bytes && p.macro_shift == L.mshift && p.start_table == L.start_table && p.vol == volume->dptr &&
          p.sdf == sdf->dptr && p.vol_ver == volume->version() && p.sdf_ver == sdf->version() &&
          !std::memcmp(&p.tf, &tf, sizeof tf) && p.tf_identity == tf_identity;
 }
@@ -108,6 +119,10 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
     if (e != hipSuccess) return e;
     return launch_macro_table(r.brick_min, L.NBX, L.NBY, L.NBZ, data + L.off_macro, L.X, L.Y, L.Z, L.mshift, ctx->stream);
   }));
+  if (L.start_table)
+    CLWH_TRY(timed(ctx, CLWH_TIMER_REPACK, [&] {
+      return launch_start_table(r.stepb, data + L.off_start + 16u, reinterpret_cast<uint32_t *>(data + L.off_start), L.X, L.Y, L.Z, L.NBX, L.NBY, L.NBZ, ctx->stream);
+    }));
   HIP_TRY(hipEventRecord(entry->ready.ev, ctx->stream));
   ctx->scene = entry;
   {
@@ -119,6 +134,7 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
     entry->tf = tf;
     entry->tf_identity = tf_identity;
     entry->macro_shift = L.mshift;
+    entry->start_table = L.start_table;
     entry->dims[0] = L.X; entry->dims[1] = L.Y; entry->dims[2] = L.Z;
     entry->generation = ++g_packed_generation;
     entry->stale = false;
@@ -231,6 +247,7 @@ static int describe_launch(const clwh_ctx *ctx, const clwh_render_desc *d, Rende
   a.unit_affinity = t.unit_affinity;
   a.unit_queues = t.unit_queues;
   a.cert_hint = t.cert_hint;
+  a.start_cert_dmin = start_cert_dmin(a.X, a.Y, a.Z);
   return CLWH_OK;
 }
 
@@ -240,7 +257,7 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   const uint8_t *cls_in = nullptr;
   CLWH_TRY(kernel_tf(k, d->volume, a.tf, &cls_in));
   a.tf.literal_gradient_taps = ctx->tune.literal_gradient;
-  const PackedLayout L = packed_layout(d->volume, ctx->tune.macro_shift);
+  const PackedLayout L = packed_layout(d->volume, ctx->tune.macro_shift, wants_start_table(ctx->tune, a.tf, d->volume));
   CLWH_TRY(ensure_packed(ctx, L, d->volume, d->sdf, a.tf, cls_in, k->jit ? k->jit->source : std::string()));
   const uint8_t *packed = ctx->scene->data.as<uint8_t>();
   a.grec = reinterpret_cast<const uint2 *>(packed);
@@ -250,6 +267,7 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   a.volume_lin = (const int16_t *)d->volume->dptr;
   a.sdf_lin = (const int8_t *)d->sdf->dptr;
   a.macro = packed + L.off_macro;
+  a.start_free = L.start_table ? packed + L.off_start + 16u : nullptr;
   a.macro_shift = L.mshift;
   a.MNX = L.MNX; a.MNY = L.MNY; a.MNZ = L.MNZ;
   // An exit certificate proves "this march leaves the volume without a Hit"; a position with a coordinate == dimension or NaN
@@ -403,6 +421,10 @@ static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
                h[CTR_EV_KIND + 1], h[CTR_EV_KIND + 2], h[CTR_EV_KIND + 3], h[CTR_CERT_PHASES], per(CTR_CERT_LANES, CTR_CERT_PHASES), h[CTR_CERT_GRANTED]);
   if (h[CTR_SWAPS]) std::fprintf(stderr, "[bounce stats] two rays per lane: %u swap points\n", h[CTR_SWAPS]);
   std::fprintf(stderr, "[bounce stats] per step iteration: avg_idle_lanes=%.2f (lane sum %u)\n", per(CTR_STEP_IDLE, CTR_STEP_ITERS), h[CTR_STEP_IDLE]);
+  // -DCLVR_BOUNCE_STATS=2 takes the start certificates as the product build does; any other value marches a granted leg all the same and checks it
+  std::fprintf(stderr, "[bounce stats] lane_steps=%u event_lanes=%u start certificates (%s) tried/granted/wrong=%u/%u/%u dmin=%.6f\n", h[CTR_STEP_LANES],
+               h[CTR_EVENT_LANES], (CLVR_BOUNCE_STATS + 0) == 2 ? "taken" : "verified: marched literally", h[CTR_START_TRIED], h[CTR_START_GRANTED],
+               h[CTR_START_WRONG], (double)a.start_cert_dmin);
   return CLWH_OK;
 }
 #endif
@@ -550,22 +572,59 @@ int clwh_ctx_scene_info(clwh_ctx *ctx, uint64_t *scene_id, uint64_t *bytes, int3
   return CLWH_OK;
 }
 
+// the layout of the context's derived scene data
+static PackedLayout scene_layout(clwh_ctx *ctx) {
+  std::lock_guard<std::mutex> lock(g_scenes_mutex);
+  clwh_mem shape{};
+  for (int q = 0; q < 3; ++q) shape.dims[q] = (size_t)ctx->scene->dims[q];
+  return packed_layout(&shape, ctx->scene->macro_shift, ctx->scene->start_table);
+}
+
 int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
   if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
   if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
-  PackedLayout L;
-  {
-    std::lock_guard<std::mutex> lock(g_scenes_mutex);
-    clwh_mem shape{};
-    for (int q = 0; q < 3; ++q) shape.dims[q] = (size_t)ctx->scene->dims[q];
-    L = packed_layout(&shape, ctx->scene->macro_shift);
-  }
+  const PackedLayout L = scene_layout(ctx);
   info_out[0] = L.MNX; info_out[1] = L.MNY; info_out[2] = L.MNZ; info_out[3] = L.mshift;
-  const size_t bytes = L.bytes - L.off_macro;
+  const size_t bytes = (size_t)L.MNX * L.MNY * L.MNZ * 8u;
   if (!host_out) return CLWH_OK;  // the size alone
   if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + L.off_macro, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
+int clwh_debug_start_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
+  const PackedLayout L = scene_layout(ctx);
+  info_out[0] = L.X; info_out[1] = L.Y; info_out[2] = L.Z; info_out[3] = L.start_table ? 1 : 0;
+  if (!host_out || !L.start_table) return CLWH_OK;  // the size alone; or there is no table
+  const size_t bytes = (size_t)L.X * L.Y * L.Z;
+  if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + L.off_start + 16u, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
+int clwh_debug_start_cert_dmin(int32_t X, int32_t Y, int32_t Z, float *dmin_out) {
+  if (!dmin_out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
+  *dmin_out = start_cert_dmin(X, Y, Z);
+  return CLWH_OK;
+}
+
+int clwh_debug_hit_records(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out) {
+  if (!ctx || !n_hits_out) return CLWH_ERR_INVALID_VALUE;
+  PrimaryHits &p = ctx->primary;
+  if (!p.valid || !p.hits.ptr || !ctx->pass.counters.ptr) return CLWH_ERR_BAD_ARGS;  // no camera rendered yet
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(n_hits_out, ctx->pass.counters.as<uint32_t>() + CTR_HITS, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!host_out) return CLWH_OK;  // the count alone
+  const size_t bytes = (size_t)*n_hits_out * sizeof(HitRec);
+  if (capacity < bytes || p.hits.bytes < bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipMemcpyAsync(host_out, p.hits.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return CLWH_OK;
 }

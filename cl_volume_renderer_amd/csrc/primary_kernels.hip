@@ -67,7 +67,16 @@ __global__ __launch_bounds__(64) void k_primary(const RenderArgs a) {
     q1.z = __float_as_uint(normal.x); q1.w = __float_as_uint(normal.y);
     q2.x = __float_as_uint(normal.z); q2.y = current_color;
     q2.z = (uint32_t)((uint64_t)entry & 0xFFFFFFFFull); q2.w = (uint32_t)((uint64_t)entry >> 32);
-    q3.x = x | (y << 16); q3.y = pslot; q3.z = 0u; q3.w = 0u;
+    // start certificate (k_start_*, scene_kernels.hip): both distribution rays of every sample start from P = (origin + direction) +
+    // normal * 2, formed with k_bounce's own operations; the table byte of P's voxel travels with the hit (three unsigned compares:
+    // has P a voxel?  see k_bounce's step loop)
+    uint32_t start_free = 0u;
+    if (a.start_free) {
+      const f3 p = (current_ray.origin + current_ray.direction) + normal * 2.0f;
+      if (__float_as_uint(p.x) < __float_as_uint(dx) && __float_as_uint(p.y) < __float_as_uint(dy) && __float_as_uint(p.z) < __float_as_uint(dz))
+        start_free = a.start_free[((size_t)(int)p.z * (size_t)a.Y + (size_t)(int)p.y) * (size_t)a.X + (size_t)(int)p.x];
+    }
+    q3.x = x | (y << 16); q3.y = pslot; q3.z = start_free; q3.w = 0u;
     uint4 *dst = reinterpret_cast<uint4 *>(&a.hits[h]);
     dst[0] = q0; dst[1] = q1; dst[2] = q2; dst[3] = q3;
     a.pix_slot[pslot] = PIX_HIT | h;

@@ -8,10 +8,13 @@
 //
 //   k_repack   (when volume / SDF / TF changed)  bricked step bytes + hit records (packed_volume.hpp);      scene_kernels.hip
 //                                                k_macro_*: the exit-certificate table
+//                                                k_start_*: the start-certificate table (a byte per voxel)
 //   k_primary  (when the camera changed)         one lane per pixel: ray, box entry, primary march;         primary_kernels.hip
 //                                                hits are compacted into 64-byte records with a
 //                                                wave ballot + prefix (one atomic per wave);
 //                                                misses keep their environment colour
+//                                                a hit carries the start-certificate byte of the voxel
+//                                                its distribution rays start from
 //   k_bounce   (every launch, 1..64 seeds)       persistent waves pull (hit, seed) items from eight         this file
 //                                                work queues; each lane runs the sample's two               (k_bounce2, two rays per
 //                                                distribution rays as a small state machine; idle           lane: bounce_two_rays.hpp)
@@ -79,12 +82,15 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // is the number of waves in flight that sets the pace.
   enum : int { C_START_X, C_START_Y, C_START_Z,  // hit origin + hit direction: where both distribution rays start from
                C_NORMAL_X, C_NORMAL_Y, C_NORMAL_Z,
-               C_ENTRY_LO, C_ENTRY_HI, C_PIXEL, C_HIT, C_SEED,
+               C_ENTRY_LO,
+               C_ENTRY_HI,  // bits 0-23: the entry's (a stored entry is -1, -2 or below 2^34: bit 23 is its sign); bits 24-31: the hit's start-certificate byte
+               C_PIXEL, C_HIT, C_SEED,
                C_FIX,  // (fix + 2) << 2 | npend; fix: fix-up record of the sample (-1: none, -2: dropped, the buffer overflowed),
                        // npend: pending environment terms written to it
                C_BV_R, C_BV_G, C_BV_B, C_FIELDS };
   __shared__ uint32_t cold[C_FIELDS][kBounceThreads];
 #define COLD(f) cold[f][threadIdx.x]
+#define COLD_ENTRY_HI() ((uint32_t)((int32_t)(COLD(C_ENTRY_HI) << 8) >> 8))
   // path state; energies and colour carry over from distribution ray 1 into ray 2 (SURVEY "hard parts")
   Ray ray{{0, 0, 0}, {0, 0, 0}};
   float atten = 0.0f, r_energy = 0.0f, g_energy = 0.0f, b_energy = 0.0f;
@@ -103,6 +109,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   const int cert_min_lanes = a.cert_min_lanes;
   // a lane asks for an exit certificate when its next step is at least this long (wave-uniform)
   const int cert_at = a.cert_min_step != 0 ? a.cert_min_step : kCertNever;
+  // first legs ask the hit's start-certificate byte: long launches only (launch_bounce); tables with `gradient` rules have no such table
+  const bool start_cert = !USE_GRAD && a.cert_min_step != 0;
   bool exhausted = false;  // wave-uniform: the queue has no more items
   BounceStats stats;
 
@@ -200,6 +208,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           march -= kOneStep;
         }
       }
+      stats.march_end(a.counters, ev);
       bool ended = false;  // distribution ray `o` has ended: the next one starts from the primary hit, or the sample is complete
 
       if (ev == EV_EXIT) {
@@ -225,7 +234,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
               uint32_t *rec = a.fixups + (size_t)slot * kFixupDwords;
               rec[0] = COLD(C_HIT);
               rec[1] = COLD(C_ENTRY_LO);
-              rec[2] = COLD(C_ENTRY_HI);
+              rec[2] = COLD_ENTRY_HI();
               rec[3] = COLD(C_PIXEL);
               rec[4] = COLD(C_BV_R); rec[5] = COLD(C_BV_G); rec[6] = COLD(C_BV_B);
             } else {
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
       if (ended && o > 2) {
         const int fix = (int)(COLD(C_FIX) >> 2) - 2;
         if (fix == -1)
-          finish_item<MODE>(a, (int64_t)(((uint64_t)COLD(C_ENTRY_HI) << 32) | (uint64_t)COLD(C_ENTRY_LO)), COLD(C_HIT), COLD(C_PIXEL) & 0xFFFFu,
+          finish_item<MODE>(a, (int64_t)(((uint64_t)COLD_ENTRY_HI() << 32) | (uint64_t)COLD(C_ENTRY_LO)), COLD(C_HIT), COLD(C_PIXEL) & 0xFFFFu,
                             COLD(C_PIXEL) >> 16, COLD(C_BV_R), COLD(C_BV_G), COLD(C_BV_B));
         else if (fix >= 0) a.fixups[(size_t)fix * kFixupDwords + 7] = COLD(C_FIX) & 3u;  // k_env_fixup finishes it
         st = ST_IDLE;
@@ -345,7 +354,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             if (granted) {
               COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
               COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
-              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = q2.w;
+              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = (q2.w & 0x00FFFFFFu) | (q3.z << 24);
               COLD(C_PIXEL) = q3.x;
               COLD(C_HIT) = h;
               COLD(C_SEED) = (uint32_t)a.seeds[s];
@@ -372,6 +381,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
     }
 
     // ---- event phase, opening half: the bounce is one shared block, then the march's first SDF read ---------
+    bool sc_tried = false, sc_granted = false;  // this lane's first leg asked for / holds a start certificate
     if (st >= ST_EVENT) {
       const int ev = st - ST_EVENT;
       bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
@@ -423,16 +433,32 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         } else {
           atten = d;
           i = 8;
+          if (start_cert) {
+            // Start certificate.  All first legs of a hit start from the same point, whose voxel k_primary has looked up in the
+            // "free from here" table (k_start_*, scene_kernels.hip): bit `octant` says that the box from that voxel to the volume
+            // corner this direction heads for holds no voxel that may be an event.  The march's coordinates are monotone, so it can
+            // only end in Exit_volume or run out of steps, and start_cert_dmin (clwh_internal.hpp) is the smallest direction
+            // component with which it provably leaves within its 70 steps.  Like every exit certificate it ends the march at once:
+            // only the direction is used from here on, and not one step byte is fetched.
+            sc_tried = true;
+            sc_granted = start_certificate(COLD(C_ENTRY_HI) >> 24, nr.direction, a.start_cert_dmin);
+          }
         }
         ray = nr;
       }
 
-      // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
-      sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
-      march = 70u * kOneStep + kCertReady;
-      st = ST_MARCH;
+      if (sc_granted && !kStartCertVerify) {
+        st = ST_EVENT + EV_EXIT;  // the next closing half takes it from here
+      } else {
+        // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
+        sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
+        march = 70u * kOneStep + kCertReady;
+        st = ST_MARCH;
+      }
     }
+    stats.start_cert(sc_tried, sc_granted);
   }
+#undef COLD_ENTRY_HI
 #undef COLD
 }
 

@@ -1,4 +1,4 @@
-// scene_kernels.hip -- what the `render` pass derives from the scene: step bytes and hit records (k_repack), the exit-certificate table (k_macro_*)
+// scene_kernels.hip -- what the `render` pass derives from the scene: step bytes and hit records (k_repack), the exit-certificate table (k_macro_*), the start-certificate table (k_start_*)
 #include "render_device.hpp"
 
 namespace clvr {
@@ -262,6 +262,98 @@ hipError_t launch_macro_table(const uint32_t *brick_min, int NBX, int NBY, int N
     hipLaunchKernelGGL(k_macro_octants, dim3(((unsigned)lines[axis] + 63u) / 64u), dim3(64), 0, s, macro, MNX, MNY, MNZ, axis);
   hipLaunchKernelGGL(k_macro_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, macro, MNX, MNY, MNZ);
   hipLaunchKernelGGL(k_macro_hints, dim3((n + 255u) / 256u), dim3(256), 0, s, macro, MNX, MNY, MNZ);
+  return hipGetLastError();
+}
+
+// ---- start certificates: a per-voxel, per-octant "free from here" table (k_primary copies a hit's byte into its record, k_bounce ends
+// a first leg before its first fetch: render_kernels.hip).  One byte per voxel, x fastest; bit o (certify_exit's octant numbering) is
+// set when no voxel of the axis-aligned box from this voxel (inclusive) to the volume corner octant o heads for may be an event (step
+// byte bit 7).  Three separable passes extend "an event lies that way" along x, y and z, each in both directions.
+
+// The certificate's step bound (start_cert_dmin, clwh_internal.hpp) needs steps that grow with the distance from the events, which is
+// a property of the caller's SDF image, not of the table.  It is checked on the step bytes themselves: a voxel with a step value of 0
+// or 1 must be an event or (value 1) touch one (Chebyshev distance 1); a voxel with a larger value s must have s >= min(cap, 1 + the
+// smallest value among its eight corner neighbours, clamped to the volume as the SDF build clamps them), cap = start_cert_cap.  By
+// induction over m: every voxel m >= 1 away from all voxels that touch an event has a value of at least min(cap, m + 1).  The
+// converged SDF of the volume passes; one built with fewer layers, or any other image, clears `regular` and the table stays 0.
+__global__ __launch_bounds__(256) void k_start_regular(const uint8_t *__restrict__ stepb, int X, int Y, int Z, int NBX, int NBY, unsigned cap, uint32_t *regular) {
+  const unsigned brick = blockIdx.x;
+  const int bx = (int)(brick % (unsigned)NBX), by = (int)((brick / (unsigned)NBX) % (unsigned)NBY), bz = (int)(brick / (unsigned)(NBX * NBY));
+  auto at = [&](int x, int y, int z) -> unsigned { return stepb[VolumePacked::record_index(x, y, z, NBX, NBY)]; };
+  bool ok = true;
+  for (unsigned inner = threadIdx.x; inner < 512u; inner += 256u) {
+    unsigned ix, iy, iz;
+    VolumePacked::inner_coords(inner, ix, iy, iz);
+    const int x = bx * 8 + (int)ix, y = by * 8 + (int)iy, z = bz * 8 + (int)iz;
+    if (x >= X || y >= Y || z >= Z) continue;
+    const unsigned q = stepb[((size_t)brick << 9) + inner], s = q & 0x7Fu;
+    if (s >= 2u) {
+      unsigned m = 127u;
+      for (int c = 0; c < 8; ++c)
+        m = min(m, at(min(max(x + ((c & 1) ? 1 : -1), 0), X - 1), min(max(y + ((c & 2) ? 1 : -1), 0), Y - 1), min(max(z + ((c & 4) ? 1 : -1), 0), Z - 1)) & 0x7Fu);
+      ok = ok && s >= min(cap, m + 1u);
+    } else {
+      bool touches = false;
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx)
+            touches = touches || (at(min(max(x + dx, 0), X - 1), min(max(y + dy, 0), Y - 1), min(max(z + dz, 0), Z - 1)) & 0x80u) != 0u;
+      ok = ok && touches && (s == 1u || (q & 0x80u) != 0u);
+    }
+  }
+  if (!ok) *regular = 0u;
+}
+// x: a wave per row finds the row's first and last event voxel; bits of the octants that head for x = X - 1 (even o) are set behind the
+// last one, those of the octants that head for x = 0 before the first.  A block takes the 4 x 4 rows of a row of sub-bricks.
+__global__ __launch_bounds__(256) void k_start_rows(const uint8_t *__restrict__ stepb, uint8_t *__restrict__ table, int X, int Y, int Z, int NBX, int NBY) {
+  const int lane = (int)(threadIdx.x & 63u), y = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (y >= Y) return;
+  for (int k = 0; k < 4; ++k) {
+    const int z = (int)blockIdx.y * 4 + k;
+    if (z >= Z) break;
+    int first = X, last = -1;
+    for (int x0 = 0; x0 < X; x0 += 64) {
+      const int x = x0 + lane;
+      const unsigned long long ev = __ballot(x < X && (stepb[VolumePacked::record_index(min(x, X - 1), y, z, NBX, NBY)] & 0x80u) != 0u);
+      if (ev != 0ull) {
+        if (first == X) first = x0 + __ffsll((long long)ev) - 1;
+        last = x0 + 63 - __clzll((long long)ev);
+      }
+    }
+    uint8_t *row = table + ((size_t)z * (size_t)Y + (size_t)y) * (size_t)X;
+    for (int x = lane; x < X; x += 64) row[x] = (uint8_t)((x > last ? 0x55u : 0u) | (x < first ? 0xAAu : 0u));
+  }
+}
+// y (axis 1) and z (axis 2): one thread per line, neighbouring threads neighbouring x.  A bit survives only if it is set in every voxel
+// from here to the end of the line in its octant's direction.  The last pass clears everything when the step bytes are not `regular`.
+__global__ __launch_bounds__(256) void k_start_scan(uint8_t *__restrict__ table, int X, int Y, int Z, int axis, const uint32_t *regular) {
+  const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), other = (int)blockIdx.y;
+  if (x >= X) return;
+  const int len = axis == 1 ? Y : Z;
+  const size_t stride = axis == 1 ? (size_t)X : (size_t)X * (size_t)Y;
+  uint8_t *line = table + (axis == 1 ? (size_t)other * (size_t)Y * (size_t)X : (size_t)other * (size_t)X) + (size_t)x;
+  const unsigned up = axis == 1 ? 0x33u : 0x0Fu;  // the octants that head for the line's far end
+  const unsigned keep = (regular == nullptr || *regular != 0u) ? 0xFFu : 0u;
+  unsigned run = 0xFFu;
+  for (int i = len - 1; i >= 0; --i) {
+    const unsigned v = line[(size_t)i * stride];
+    run &= v;
+    line[(size_t)i * stride] = (uint8_t)((v & ~up) | (run & up));
+  }
+  run = 0xFFu;
+  for (int i = 0; i < len; ++i) {
+    const unsigned v = line[(size_t)i * stride];
+    run &= v;
+    line[(size_t)i * stride] = (uint8_t)(((v & up) | (run & ~up)) & keep);
+  }
+}
+hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(regular, 1, sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_start_regular, dim3((unsigned)(NBX * NBY * NBZ)), dim3(256), 0, s, stepb, X, Y, Z, NBX, NBY, (unsigned)start_cert_cap(X, Y, Z), regular);
+  hipLaunchKernelGGL(k_start_rows, dim3(((unsigned)Y + 3u) / 4u, ((unsigned)Z + 3u) / 4u), dim3(256), 0, s, stepb, table, X, Y, Z, NBX, NBY);
+  hipLaunchKernelGGL(k_start_scan, dim3(((unsigned)X + 255u) / 256u, (unsigned)Z), dim3(256), 0, s, table, X, Y, Z, 1, (const uint32_t *)nullptr);
+  hipLaunchKernelGGL(k_start_scan, dim3(((unsigned)X + 255u) / 256u, (unsigned)Y), dim3(256), 0, s, table, X, Y, Z, 2, (const uint32_t *)regular);
   return hipGetLastError();
 }
 

@@ -228,6 +228,9 @@ _PROTOTYPES = [
     ("clwh_debug_float_conversions", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("clwh_debug_wave_min", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("clwh_debug_macro_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("clwh_debug_start_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("clwh_debug_start_cert_dmin", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    ("clwh_debug_hit_records", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("clwh_strerror", C.c_char_p, [C.c_int]),
     ("clwh_last_hip_error", C.c_int, []),
     ("clwh_version", C.c_char_p, []),
@@ -269,6 +272,13 @@ def parse_tf(source: str) -> Tf:
     tf = Tf()
     _check(lib().clwh_tf_parse(source.encode(), C.byref(tf)), "clwh_tf_parse")
     return tf
+
+
+def start_cert_dmin(X: int, Y: int, Z: int) -> float:
+    """the smallest min |direction component| a start certificate needs in an X x Y x Z volume (2.0: never granted)"""
+    v = C.c_float(0)
+    _check(lib().clwh_debug_start_cert_dmin(X, Y, Z, C.byref(v)), "clwh_debug_start_cert_dmin")
+    return float(v.value)
 
 
 def cache_len(X, Y, Z) -> int:
@@ -646,6 +656,25 @@ class Context:
         out = np.empty((info[2], info[1], info[0], 8), np.uint8)
         _check(lib().clwh_debug_macro_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_macro_table")
         return out, int(info[3])
+
+    def start_table(self):
+        """the start-certificate table of the scene data this context rendered from last: uint8 [z][y][x], bit o set = the box from
+        the voxel to the volume corner of direction octant o holds no voxel that may be an event; None when it was not built"""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_start_table(self.h, None, C.c_uint64(0), info), "clwh_debug_start_table")
+        if not info[3]:
+            return None
+        out = np.empty((info[2], info[1], info[0]), np.uint8)
+        _check(lib().clwh_debug_start_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_start_table")
+        return out
+
+    def hit_records(self):
+        """the hit records of the camera this context rendered last: uint32 [n_hits][16] (clwh_debug_hit_records)"""
+        n = C.c_uint32(0)
+        _check(lib().clwh_debug_hit_records(self.h, None, C.c_uint64(0), C.byref(n)), "clwh_debug_hit_records")
+        out = np.empty((int(n.value), 16), np.uint32)
+        _check(lib().clwh_debug_hit_records(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), C.byref(n)), "clwh_debug_hit_records")
+        return out[:int(n.value)]
 
     def image_wrap(self, device_ptr: int, dims, channels, dtype, shape=None) -> Mem:
         """adopt device memory somebody else allocated (a graphics-interop mapping, a torch tensor) as an image"""

@@ -670,6 +670,18 @@ int clwh_debug_wave_min(clwh_ctx *ctx, clwh_mem *u32_in, uint64_t n, clwh_mem *u
  * its smallest step value; 0x80 | g = it is not, and g (saturating at 127) cells along the octant's diagonal is the nearest cell
  * whose box is free or that lies outside the volume.  CLWH_ERR_BAD_ARGS: the context holds no scene data */
 int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
+/* the start-certificate table of the derived scene data the context rendered from last: info_out = {X, Y, Z,
+ * 1 if the table was built else 0}; host_out (may be null: the shape alone) receives one byte per voxel, x fastest: bit o is set when
+ * no voxel of the box from this voxel (inclusive) to the volume corner direction octant o heads for may be an event.  Nothing is
+ * written when the table was not built.  CLWH_ERR_BAD_ARGS: the context holds no scene data */
+int clwh_debug_start_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
+/* the smallest min |direction component| with which a start certificate is granted in a volume of X x Y x Z voxels (a multiple of
+ * 1/64; 2: never) */
+int clwh_debug_start_cert_dmin(int32_t X, int32_t Y, int32_t Z, float *dmin_out);
+/* the hit records of the camera the context rendered last: *n_hits_out = their number; host_out (may be null: the count alone) receives
+ * 64 bytes per hit: float origin[3], direction[3], normal[3]; uint32 colour; int64 cache entry; uint32 x | y << 16, pixel slot,
+ * start-certificate byte, 0.  CLWH_ERR_BAD_ARGS: no camera yet */
+int clwh_debug_hit_records(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out);
 const char *clwh_strerror(int status);
 int clwh_last_hip_error(void);
 const char *clwh_version(void);
