@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -17,6 +17,11 @@
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
 // view, the mesh or the path-traced frames then show the masked volume.
+// --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
+// labelled (renderer::label_components), the K largest or those of at least N voxels (default: all) become the mask
+// (renderer::select_components) and are applied in place like --grow's region.  One JSON line has n_components, n_voxels, the selected
+// rank range ([0, 0]: none) and count / first / bbox of up to the 8 largest.  --grow and --components exclude each other.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -49,6 +54,10 @@ int main(int argc_in, char const *argv_in[]) {
   bool grow = false, grow_remove = false;
   uint32_t grow_seed[3] = {0, 0, 0};
   int grow_lo = 0, grow_hi = 0, grow_flags = 0, grow_fill = -32768;
+  bool comps = false, comps_remove = false;
+  int comps_lo = 0, comps_hi = 0, comps_flags = 0, comps_fill = -32768;
+  long long comps_largest = -1, comps_min = -1;
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V])";
   static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
@@ -150,6 +159,46 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--grow", 0) == 0) {
       std::cout << "Unknown option '" << a << "' " << kGrowUsage << "\n";
       return 1;
+    } else if (a.rfind("--components=", 0) == 0) {
+      std::string rest = a.substr(13);
+      bool ok = true;
+      int field = 0;
+      for (; ok && (field == 0 || !rest.empty()); ++field) {
+        const size_t comma = rest.find(',');
+        const std::string v = rest.substr(0, comma);
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+        if (comma != std::string::npos && rest.empty()) ok = false;  // a trailing comma
+        char *end = nullptr;
+        if (field < 2) {
+          const long long n = std::strtoll(v.c_str(), &end, 10);
+          ok = ok && !v.empty() && *end == '\0' && n >= -32768 && n <= 32767;
+          (field == 0 ? comps_lo : comps_hi) = (int)n;
+        } else if (v == "26") {
+          comps_flags |= CLWH_LABEL_26;
+        } else if (v == "keep" || v == "remove") {
+          comps_remove = v == "remove";
+        } else if (v.rfind("fill=", 0) == 0) {
+          const long n = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && n >= -32768 && n <= 32767;
+          comps_fill = (int)n;
+        } else if (v.rfind("largest=", 0) == 0) {
+          comps_largest = std::strtoll(v.c_str() + 8, &end, 10);
+          ok = ok && v.size() > 8 && *end == '\0' && comps_largest >= 1 && comps_largest <= 0x7fffffffLL;
+        } else if (v.rfind("min=", 0) == 0) {
+          comps_min = std::strtoll(v.c_str() + 4, &end, 10);
+          ok = ok && v.size() > 4 && *end == '\0' && comps_min >= 1 && comps_min <= 0x7fffffffLL;
+        } else {
+          ok = false;
+        }
+      }
+      if (!ok || field < 2 || comps_lo > comps_hi || (comps_largest >= 0 && comps_min >= 0)) {
+        std::cout << "Unknown option '" << a << "' " << kCompsUsage << "\n";
+        return 1;
+      }
+      comps = true;
+    } else if (a.rfind("--components", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' " << kCompsUsage << "\n";
+      return 1;
     } else if (a.rfind("--slice=", 0) == 0) {
       std::string rest = a.substr(8);
       bool ok = true;
@@ -185,6 +234,10 @@ int main(int argc_in, char const *argv_in[]) {
       args.push_back(argv_in[i]);
     }
   }
+  if (grow && comps) {
+    std::cout << "--grow and --components exclude each other\n";
+    return 1;
+  }
   if (mesh && (projection >= 0 || composite >= 0 || isosurface || slice >= 0)) {
     std::cout << "--mesh excludes --projection, --composite, --isosurface and --slice\n";
     return 1;
@@ -204,7 +257,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -240,6 +293,37 @@ int main(int argc_in, char const *argv_in[]) {
                 grow_seed[0], grow_seed[1], grow_seed[2], grow_lo, grow_hi, (grow_flags & CLWH_GROW_26) ? 26 : 6, grow_remove ? "remove" : "keep",
                 grow_fill, (unsigned long long)g.count, g.bbox_lo[0], g.bbox_lo[1], g.bbox_lo[2], g.bbox_hi[0], g.bbox_hi[1], g.bbox_hi[2],
                 g.count ? (double)g.sum / (double)g.count : 0.0, g.vmin, g.vmax);
+  }
+
+  if (comps) {  // like --grow: everything below sees the masked volume
+    ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
+    renderer::component_summary c = r.label_components(none, comps_lo, comps_hi, comps_flags, 8);
+    uint64_t keep = c.n_components;  // the selected ranks are 1 .. keep
+    if (comps_largest >= 0) keep = std::min<uint64_t>(keep, (uint64_t)comps_largest);
+    if (comps_min >= 0) {
+      // "at least N voxels" is a prefix of the ranks; if the eight records do not show its end, the whole table does
+      renderer::component_summary all;
+      const bool undecided = c.top.size() < c.n_components && !c.top.empty() && c.top.back().count >= (uint64_t)comps_min;
+      if (undecided) all = r.label_components(none, comps_lo, comps_hi, comps_flags, (unsigned)c.n_components);
+      const std::vector<clwh_label_component> &table = undecided ? all.top : c.top;
+      keep = 0;
+      while (keep < table.size() && table[keep].count >= (uint64_t)comps_min) ++keep;
+    }
+    // (no component selected: a rank nobody has gives the empty mask)
+    if (keep > 0) r.select_components(none, 1, (uint32_t)keep);
+    else r.select_components(none, (uint32_t)c.n_components + 1u, (uint32_t)c.n_components + 1u);
+    r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
+    std::printf("{\"components\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"n_components\": %llu, \"n_voxels\": %llu, "
+                "\"selected\": [%u, %llu], \"largest\": [",
+                comps_lo, comps_hi, (comps_flags & CLWH_LABEL_26) ? 26 : 6, comps_remove ? "remove" : "keep", comps_fill,
+                (unsigned long long)c.n_components, (unsigned long long)c.n_voxels, keep > 0 ? 1u : 0u, (unsigned long long)keep);
+    for (size_t k = 0; k < c.top.size(); ++k) {
+      const clwh_label_component &t = c.top[k];
+      std::printf("%s{\"count\": %llu, \"first\": [%u, %u, %u], \"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u]}", k ? ", " : "",
+                  (unsigned long long)t.count, t.first[0], t.first[1], t.first[2], t.bbox_lo[0], t.bbox_lo[1], t.bbox_lo[2], t.bbox_hi[0],
+                  t.bbox_hi[1], t.bbox_hi[2]);
+    }
+    std::printf("]}\n");
   }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera

@@ -142,6 +142,18 @@ void clvr_host_grow_region(clvr_host *h, const unsigned *seeds, unsigned n_seeds
 }
 // renderer::apply_mask: the last grown mask applied to the renderer's volume in place
 void clvr_host_apply_mask(clvr_host *h, int fill, int flags) { h->rend.apply_mask(h->state, fill, flags); }
+// renderer::label_components: *n_components and *n_voxels, and up to top_k records (clwh_label_component, 48 bytes each) into
+// `records`; returns how many were written.  The labels stay on the device
+unsigned clvr_host_label_components(clvr_host *h, int lo, int hi, int flags, unsigned top_k, unsigned long long *n_components,
+                                    unsigned long long *n_voxels, void *records) {
+  const renderer::component_summary s = h->rend.label_components(h->state, lo, hi, flags, top_k);
+  *n_components = s.n_components;
+  *n_voxels = s.n_voxels;
+  if (!s.top.empty()) std::memcpy(records, s.top.data(), s.top.size() * sizeof(clwh_label_component));
+  return (unsigned)s.top.size();
+}
+// renderer::select_components: ranks rank_lo .. rank_hi of the last labelling become the mask clvr_host_apply_mask applies
+void clvr_host_select_components(clvr_host *h, unsigned rank_lo, unsigned rank_hi) { h->rend.select_components(h->state, rank_lo, rank_hi); }
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

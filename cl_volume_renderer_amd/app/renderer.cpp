@@ -24,6 +24,7 @@ renderer::renderer(clw_context &c)
       tfframe(ctx, std::vector<unsigned char>(2 * 2 * 4), {2, 2, 1}),
       composite_lut(ctx, std::vector<float>(4)),
       region_mask(ctx, std::vector<uint32_t>(2)),
+      region_labels(ctx, std::vector<uint32_t>(1)),
       sdf(ctx) {}
 
 void renderer::image_set(const reference_volume *rv, const env_map *map) {
@@ -267,6 +268,50 @@ void renderer::apply_mask(struct ui_state &, int fill, int flags) {
   d.fill = fill;
   d.flags = flags;
   clw_fail_hard_on_error(clwh_volume_apply_mask(ctx.get_handle(), &d));
+}
+
+renderer::component_summary renderer::label_components(struct ui_state &, int lo, int hi, int flags, unsigned top_k) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2], mask_words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];
+  if ((flags & CLWH_LABEL_FROM_MASK) && region_mask.size() != mask_words) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask to split
+  if (region_labels.size() != voxels) region_labels = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  constexpr size_t record_words = sizeof(clwh_label_component) / sizeof(uint32_t);
+  clw_vector<uint32_t> table(ctx, std::vector<uint32_t>(std::max<size_t>(top_k, 1) * record_words), false);
+  clwh_label_result result{};
+  clwh_label_desc d{};
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  d.components = table.get_device_reference();
+  d.component_capacity = top_k;
+  d.mask = (flags & CLWH_LABEL_FROM_MASK) ? region_mask.get_device_reference() : nullptr;
+  d.lo = lo;
+  d.hi = hi;
+  d.flags = flags;
+  d.result = &result;
+  clw_fail_hard_on_error(clwh_segment_label(ctx.get_handle(), &d));
+  component_summary out;
+  out.n_components = result.n_components;
+  out.n_voxels = result.n_voxels;
+  out.top.resize((size_t)std::min<uint64_t>(result.n_components, top_k));
+  if (!out.top.empty()) {
+    table.pull();
+    std::memcpy(out.top.data(), &table[0], out.top.size() * sizeof(clwh_label_component));
+  }
+  return out;
+}
+
+void renderer::select_components(struct ui_state &, uint32_t rank_lo, uint32_t rank_hi) {
+  const auto &size = volume->get_volume_size();
+  const size_t words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];
+  if (region_labels.size() != (size_t)size[0] * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // nothing was labelled
+  if (region_mask.size() != words) region_mask = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(words), false);
+  clwh_labels_to_mask_desc d{};
+  d.labels = region_labels.get_device_reference();
+  d.mask = region_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.rank_lo = rank_lo;
+  d.rank_hi = rank_hi;
+  clw_fail_hard_on_error(clwh_labels_to_mask(ctx.get_handle(), &d));
 }
 
 // (the host is little-endian, like every target of the library: the arrays go out as they lie in memory)

@@ -91,6 +91,18 @@ class renderer : public frame_emitter {
   // volume.  The host copy of the volume keeps the loaded values.
   void apply_mask(struct ui_state &state, int fill = -32768, int flags = 0);
 
+  // not in the reference: all connected components of the window lo <= value <= hi at once (clwh_segment_label; flags: CLWH_LABEL_26 |
+  // CLWH_LABEL_FROM_MASK, the latter splits the last mask into its parts), ranked by descending voxel count: their number, the
+  // admissible total and the records of the `top_k` largest.  The labels stay on the device for select_components.  Waits for the
+  // device; no camera takes part (`state` is not read).
+  struct component_summary {
+    uint64_t n_components = 0, n_voxels = 0;
+    std::vector<clwh_label_component> top;  // min(n_components, top_k) records, rank 1 first
+  };
+  component_summary label_components(struct ui_state &state, int lo, int hi, int flags = 0, unsigned top_k = 8);
+  // ... and the components of ranks rank_lo .. rank_hi of the last labelling as the region mask (clwh_labels_to_mask), for apply_mask
+  void select_components(struct ui_state &state, uint32_t rank_lo, uint32_t rank_hi);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }
@@ -104,6 +116,7 @@ class renderer : public frame_emitter {
   clw_vector<float> composite_lut;           // render_composite's table on the device (host copy = the last one pushed)
   bool composite_lut_pushed = false;
   clw_vector<uint32_t> region_mask;          // grow_region's mask on the device (never pulled: the host side only sizes it)
+  clw_vector<uint32_t> region_labels;        // label_components' ranks on the device, one word per voxel (never pulled)
   const reference_volume *volume = nullptr;  // borrowed
   const env_map *emap = nullptr;             // borrowed
   signed_distance_field sdf;

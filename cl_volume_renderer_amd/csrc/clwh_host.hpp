@@ -1,7 +1,7 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces and slices; clwh_mesh.hip: the
-// isosurface mesh; clwh_grow.hip: region growing and masked volumes).
+// isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling).
 // No kernel needs this header.
 #pragma once
 
@@ -219,6 +219,13 @@ struct GrowScratch {
   PinnedWord host;
 };
 
+// clwh_segment_label's scratch: the admissible bit image; the components' sort keys (in | out) and the sort's work space; the three
+// counters and the pinned line two of them travel to the host in.  Every call rewrites what it reads: only the allocations are kept.
+struct LabelScratch {
+  DeviceBuffer admissible, keys, temp, counters;
+  PinnedWord host;
+};
+
 // intensity projections and compositing: the volume in brick order + the per-brick {min, max} table (one allocation, per context,
 // shared by clwh_render_projection and clwh_render_composite), and the key of the content it was built from (device pointer, shared
 // content version, dims).  Beside it the derived data of compositing's colour/opacity table: the prefix count of entries with
@@ -271,6 +278,7 @@ struct clwh_ctx {
   clvr::TfClasses classes;
   clvr::SdfScratch sdf;
   clvr::GrowScratch grow;
+  clvr::LabelScratch label;
   clvr::ProjectionData proj;
   clvr::DeviceBuffer bilateral_weights;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)
   // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per

@@ -442,4 +442,32 @@ hipError_t launch_grow_reduce(const GrowArgs &a, hipStream_t s);
 hipError_t launch_apply_mask(const int16_t *in, int16_t *out, const unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64,
                              int32_t fill, int32_t invert, hipStream_t s);
 
+// ---- connected-component labelling and rank selections (label_kernels.hip; host side clwh_label.hip), over grow's bit rows
+struct LabelRecord {           // clwh_label_component, as the kernels write it
+  unsigned long long count;
+  uint32_t first[3], lo[3], hi[3];  // hi exclusive
+  uint32_t reserved;
+};
+struct LabelArgs {
+  const int16_t *volume;       // the caller's image, x fastest
+  const unsigned long long *mask;  // CLWH_LABEL_FROM_MASK: the caller's mask, read only; else null
+  unsigned long long *adm;     // A
+  uint32_t *labels;            // the caller's buffer: the runs' parent words until the last kernel writes every word
+  int32_t X, Y, Z, W64;
+  int32_t lo, hi;              // the window
+  int32_t box_lo[3], box_hi[3];
+  int32_t conn26;
+  unsigned long long *counters;  // {roots, admissible voxels, slots handed out}
+  unsigned long long *keys_in, *keys_out;  // ~count << 32 | first, per component
+  uint32_t n_roots;            // known to the host after launch_label_classes
+  uint32_t n_records;          // min(n_roots, component_capacity), 0 without a table
+  LabelRecord *records;
+};
+hipError_t launch_label_classes(const LabelArgs &a, hipStream_t s);  // A, runs, unions, flatten; counters[0], [1]
+hipError_t launch_label_keys(const LabelArgs &a, hipStream_t s);     // keys_in
+hipError_t launch_label_sort(void *temp, size_t &temp_bytes, const LabelArgs &a, hipStream_t s);  // keys_in -> keys_out
+hipError_t launch_label_ranks(const LabelArgs &a, hipStream_t s);    // the table, every word of labels
+hipError_t launch_labels_to_mask(const uint32_t *labels, unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64, uint32_t rank_lo,
+                                 uint32_t rank_hi, hipStream_t s);
+
 }  // namespace clvr

@@ -27,6 +27,7 @@ SLICE_DENSE = 1
 MESH_DENSE, MESH_BELOW = 1, 2
 GROW_26, GROW_FROM_MASK, GROW_DENSE = 1, 2, 4
 GROW_MAX_SEEDS = 65536
+LABEL_26, LABEL_FROM_MASK = 1, 2
 MASK_INVERT = 1
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
@@ -178,6 +179,45 @@ class ApplyMaskDesc(C.Structure):
     ]
 
 
+class LabelComponent(C.Structure):
+    _fields_ = [
+        ("count", C.c_uint64),
+        ("first", C.c_uint32 * 3), ("bbox_lo", C.c_uint32 * 3), ("bbox_hi", C.c_uint32 * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {"count": int(self.count), "first": tuple(self.first), "bbox_lo": tuple(self.bbox_lo), "bbox_hi": tuple(self.bbox_hi)}
+
+
+# the same record as a numpy dtype: what Context.label_components returns the table in
+LABEL_COMPONENT_DTYPE = np.dtype([("count", np.uint64), ("first", np.uint32, (3,)), ("bbox_lo", np.uint32, (3,)),
+                                  ("bbox_hi", np.uint32, (3,)), ("reserved", np.uint32)])
+assert LABEL_COMPONENT_DTYPE.itemsize == C.sizeof(LabelComponent) == 48
+
+
+class LabelResult(C.Structure):
+    _fields_ = [("n_components", C.c_uint64), ("n_voxels", C.c_uint64), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        """the contract's fields (`passes` is informational and left out)"""
+        return {"n_components": int(self.n_components), "n_voxels": int(self.n_voxels)}
+
+
+class LabelDesc(C.Structure):
+    _fields_ = [
+        ("volume", C.c_void_p), ("labels", C.c_void_p), ("components", C.c_void_p), ("component_capacity", C.c_uint64),
+        ("mask", C.c_void_p),
+        ("lo", C.c_int32), ("hi", C.c_int32), ("flags", C.c_int32),
+        ("box_lo", C.c_uint32 * 3), ("box_hi", C.c_uint32 * 3),
+        ("result", C.POINTER(LabelResult)),
+    ]
+
+
+class LabelsToMaskDesc(C.Structure):
+    _fields_ = [("labels", C.c_void_p), ("mask", C.c_void_p), ("dims", C.c_uint32 * 3), ("rank_lo", C.c_uint32), ("rank_hi", C.c_uint32)]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -219,6 +259,8 @@ _PROTOTYPES = [
     ("clwh_mesh_isosurface", C.c_int, [C.c_void_p, C.POINTER(MeshDesc)]),
     ("clwh_segment_grow", C.c_int, [C.c_void_p, C.POINTER(GrowDesc)]),
     ("clwh_volume_apply_mask", C.c_int, [C.c_void_p, C.POINTER(ApplyMaskDesc)]),
+    ("clwh_segment_label", C.c_int, [C.c_void_p, C.POINTER(LabelDesc)]),
+    ("clwh_labels_to_mask", C.c_int, [C.c_void_p, C.POINTER(LabelsToMaskDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -641,6 +683,96 @@ class Context:
         rewrite of `out`: every view of it rebuilds its derived data at its next use."""
         _check(self.apply_mask_raw(volume, mask, out if out is not None else volume, fill, MASK_INVERT if invert else 0),
                "clwh_volume_apply_mask")
+
+    def label_components_raw(self, volume: Mem, lo, hi, flags=0, box=None, mask: Mem = None, labels: Mem = None, components: Mem = None,
+                             capacity=0):
+        """one clwh_segment_label call: (status, LabelResult); nothing is raised"""
+        d, res = LabelDesc(), LabelResult()
+        d.volume, d.labels, d.components, d.mask = _handle(volume), _handle(labels), _handle(components), _handle(mask)
+        d.component_capacity = int(capacity)
+        d.lo, d.hi, d.flags = int(lo), int(hi), int(flags)
+        if box is not None:
+            for k in range(3):
+                d.box_lo[k], d.box_hi[k] = int(box[0][k]), int(box[1][k])
+        d.result = C.pointer(res)
+        return lib().clwh_segment_label(self.h, C.byref(d)), res
+
+    def label_components(self, volume: Mem, lo, hi, connectivity=6, box=None, mask: Mem = None, labels: Mem = None, capacity=256):
+        """all connected components of the voxels of `volume` (S16) with lo <= value <= hi (inside box = ((lo), (hi)) in voxels, hi
+        exclusive; with `mask`: only where its bit is set as well) under 6- or 26-connectivity, ranked by descending voxel count, ties
+        by the earlier first voxel: (labels, LabelResult, table).  labels: uint32 [z][y][x] on the device, 0 or the component's rank;
+        allocated when none is given.  table: the records of the min(n_components, capacity) largest as a structured numpy array
+        (LABEL_COMPONENT_DTYPE).  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        if volume.shape is None or len(volume.shape) != 3:
+            raise ValueError("a volume without a [z][y][x] shape (a wrap): use label_components_raw")
+        own = labels is None
+        if own:
+            labels = self.buffer(4 * int(np.prod(volume.shape)), np.uint32, tuple(volume.shape))
+        capacity = int(capacity)
+        table = self.buffer(max(capacity, 1) * 48, np.uint8)
+        try:
+            flags = (LABEL_26 if connectivity == 26 else 0) | (LABEL_FROM_MASK if mask is not None else 0)
+            status, res = self.label_components_raw(volume, lo, hi, flags, box, mask, labels, table if capacity else None, capacity)
+            if status != OK and own:
+                labels.release()
+            _check(status, "clwh_segment_label")
+            n = min(int(res.n_components), capacity)
+            records = table.pull(np.uint8)[:48 * n].view(LABEL_COMPONENT_DTYPE).copy() if n else np.zeros(0, LABEL_COMPONENT_DTYPE)
+            return labels, res, records
+        finally:
+            table.release()
+
+    def labels_to_mask_raw(self, labels: Mem, mask: Mem, dims, rank_lo, rank_hi):
+        """one clwh_labels_to_mask call: its status; nothing is raised.  dims = (X, Y, Z)"""
+        d = LabelsToMaskDesc()
+        d.labels, d.mask = _handle(labels), _handle(mask)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        d.rank_lo, d.rank_hi = int(rank_lo), int(rank_hi)
+        return lib().clwh_labels_to_mask(self.h, C.byref(d))
+
+    def labels_to_mask(self, labels: Mem, dims, rank_lo, rank_hi, mask: Mem = None) -> Mem:
+        """the components of ranks rank_lo .. rank_hi (both included) of `labels` (uint32 [z][y][x] of dims = (X, Y, Z)) as a mask in
+        clwh_segment_grow's layout, allocated when none is given.  Ordered on the context's stream; does not wait."""
+        own = mask is None
+        if own:
+            from . import scene
+
+            n = scene.mask_words_per_row(int(dims[0])) * int(dims[1]) * int(dims[2])
+            mask = self.buffer(4 * n, np.uint32, (n,))
+        status = self.labels_to_mask_raw(labels, mask, dims, rank_lo, rank_hi)
+        if status != OK and own:
+            mask.release()
+        _check(status, "clwh_labels_to_mask")
+        return mask
+
+    def keep_components(self, volume: Mem, lo, hi, largest=None, min_count=None, connectivity=6, box=None, mask: Mem = None, capacity=256):
+        """the mask of the `largest` biggest components of the window, or of those with at least `min_count` voxels (exactly one of
+        the two): (mask, LabelResult, number of components kept).  None kept: an empty mask.  min_count is decided from the table of
+        the `capacity` largest; if that table is truncated and its last record still has min_count voxels, ValueError asks for a
+        larger capacity."""
+        if (largest is None) == (min_count is None):
+            raise ValueError("exactly one of largest and min_count")
+        labels, res, table = self.label_components(volume, lo, hi, connectivity, box, mask, capacity=capacity)
+        try:
+            n = int(res.n_components)
+            if largest is not None:
+                if int(largest) < 1:
+                    raise ValueError("largest is at least 1")
+                keep = min(n, int(largest))
+            else:
+                keep = int(np.count_nonzero(table["count"] >= int(min_count)))
+                if keep == len(table) and len(table) < n:
+                    raise ValueError("min_count=%d is not decided by the %d largest of %d components: pass a larger capacity"
+                                     % (int(min_count), len(table), n))
+            dims = volume.shape[::-1]
+            # (no component kept: a rank nobody has gives the empty mask)
+            out = self.labels_to_mask(labels, dims, 1 if keep else n + 1, keep if keep else n + 1)
+            return out, res, keep
+        finally:
+            labels.release()
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

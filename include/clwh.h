@@ -595,6 +595,79 @@ typedef struct clwh_apply_mask_desc {
 } clwh_apply_mask_desc;
 int clwh_volume_apply_mask(clwh_ctx *ctx, const clwh_apply_mask_desc *desc);
 
+/* ---- connected-component labelling (not in the reference): ALL components of a value window at once, ranked largest first, where
+ * clwh_segment_grow gives the one under the seeds.  "How many pieces", "keep the largest", "drop the specks below N voxels" are then a
+ * table lookup and a rank interval.  Integers and sets only: defined bit for bit, independent of how the device schedules anything.
+ * Admissible, neighbours.  Exactly clwh_segment_grow's: lo <= V(p) <= hi, inside the box (hi exclusive, box_hi all zero = the whole
+ * volume, an empty box = nothing admissible and CLWH_OK); 6-connectivity, with CLWH_LABEL_26 26-connectivity.  With
+ * CLWH_LABEL_FROM_MASK `mask` (grow's mask layout; read only, never written) is required and a voxel is admissible only if its bit
+ * is set as well: a grown or edited mask split into its parts.  Without the flag `mask` is ignored.
+ * Components and their order.  The components are the classes of the admissible voxels under the transitive closure of "neighbour".
+ * A component's `first` voxel is its member with the smallest flat index (z * Y + y) * X + x.  Components are ranked 1, 2, ... by
+ * descending voxel count, ties by ascending flat index of `first`: rank 1 is the largest, and "at least N voxels" is a prefix.
+ * Outputs.  `labels`: a plain device buffer, 4-byte aligned, of at least 4 * X * Y * Z bytes, uint32 [z][y][x] without padding; on
+ * return 0 for a voxel that is not admissible and the component's rank otherwise; every one of the X * Y * Z words is written.
+ * `components` (optional) with component_capacity: a plain device buffer, 8-byte aligned, of clwh_label_component records (48 bytes);
+ * records 0 .. min(n, capacity) - 1 are written, record k for rank k + 1 (bbox_hi exclusive, reserved = 0); records from n on are not
+ * touched; a capacity below n is no error ("the 16 largest").  *result (HOST, required): n_components, n_voxels (the admissible
+ * total); passes, the number of kernels launched: informational, not part of the contract.
+ * Limits.  X * Y * Z <= 2^31 - 1: ranks and flat indices then fit 31 bits and a word of `labels` has a spare bit, which the call uses
+ * while it runs (labels doubles as the union-find's memory: there is no second word per voxel).
+ * SYNCHRONOUS, like clwh_segment_grow: ordered on the context's stream, returns with everything written.  The volume is read
+ * directly; no derived data is built or invalidated.  The scratch is kept with the context and holds nothing between calls: one bit
+ * per voxel, and 16 bytes per component plus the sort's work space (about as much again).
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a NULL or wrong-kind volume; NULL
+ * labels, labels that are an image or whose device pointer is not 4-byte aligned; components that are an image or not 8-byte aligned,
+ * or NULL components with component_capacity > 0; CLWH_LABEL_FROM_MASK with a mask that breaks grow's rules (NULL, an image, not
+ * 8-byte aligned); unknown flag bits; a window or a box that breaks grow's rules; volume dims beyond the projections' rule or
+ * X * Y * Z > 2^31 - 1.  CLWH_ERR_SIZE_MISMATCH: labels smaller than 4 * X * Y * Z bytes, components smaller than 48 * capacity
+ * bytes, a mask smaller than its layout.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written to labels,
+ * components or *result on any of these. */
+enum clwh_label_flags {
+  CLWH_LABEL_26 = 1,        /* 26-connectivity instead of 6 */
+  CLWH_LABEL_FROM_MASK = 2  /* admissible only where the bit of `mask` is set as well */
+};
+typedef struct clwh_label_component {
+  uint64_t count;
+  uint32_t first[3];                  /* x, y, z of the member with the smallest flat index */
+  uint32_t bbox_lo[3], bbox_hi[3];    /* hi exclusive */
+  uint32_t reserved;                  /* 0 */
+} clwh_label_component;
+typedef struct clwh_label_result {
+  uint64_t n_components;
+  uint64_t n_voxels;
+  uint32_t passes;
+  uint32_t reserved;
+} clwh_label_result;
+typedef struct clwh_label_desc {
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  clwh_mem *labels;           /* plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *components;       /* optional plain device buffer of clwh_label_component[component_capacity] */
+  uint64_t component_capacity;
+  clwh_mem *mask;             /* CLWH_LABEL_FROM_MASK: plain device buffer in the mask layout; read only */
+  int32_t lo, hi;             /* the value window, both ends included */
+  int32_t flags;
+  uint32_t box_lo[3], box_hi[3];  /* voxels; box_hi all zero = the whole volume */
+  clwh_label_result *result;  /* host; required */
+} clwh_label_desc;
+int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *desc);
+
+/* ---- a selection of components as a mask: bit(p) = (rank_lo <= labels(p) <= rank_hi), 1 <= rank_lo <= rank_hi, in
+ * clwh_segment_grow's mask layout for dims = X, Y, Z, with the bits at x >= X and the padding words zero whatever the buffer held.
+ * `labels` is what clwh_segment_label wrote (uint32 [z][y][x], a plain device buffer, 4-byte aligned).  The mask is what
+ * clwh_volume_apply_mask and CLWH_GROW_FROM_MASK read.  Asynchronous and ordered on the context's stream, like clwh_volume_apply_mask.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; NULL labels, labels that are an image or not
+ * 4-byte aligned; a NULL mask, a mask that is an image or not 8-byte aligned; a dim of 0, dims beyond the projections' rule or
+ * X * Y * Z > 2^31 - 1; rank_lo == 0 or rank_lo > rank_hi.  CLWH_ERR_SIZE_MISMATCH: labels smaller than 4 * X * Y * Z bytes, a mask
+ * smaller than the layout needs. */
+typedef struct clwh_labels_to_mask_desc {
+  clwh_mem *labels;
+  clwh_mem *mask;
+  uint32_t dims[3];           /* X, Y, Z of the labelled volume */
+  uint32_t rank_lo, rank_hi;  /* both ends included */
+} clwh_labels_to_mask_desc;
+int clwh_labels_to_mask(clwh_ctx *ctx, const clwh_labels_to_mask_desc *desc);
+
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
  * per layer.  `sdf` is an S8 3-D image of the volume's dims.  n_launches (optional) receives the
