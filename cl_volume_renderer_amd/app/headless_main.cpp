@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,15 +12,18 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
 // view, the mesh or the path-traced frames then show the masked volume.
-// --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
+// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
 // labelled (renderer::label_components), the K largest or those of at least N voxels (default: all) become the mask
 // (renderer::select_components) and are applied in place like --grow's region.  One JSON line has n_components, n_voxels, the selected
 // rank range ([0, 0]: none) and count / first / bbox of up to the 8 largest.  --grow and --components exclude each other.
+// dilate=R | erode=R | open=R | close=R, an item of --grow and of --components: the mask is dilated, eroded, opened or closed by a ball
+// of R x-voxels (renderer::morph_mask: lengths in 1/16 x-voxel, the axes weighted by the file's voxel sizes) before it is applied; the
+// JSON line then ends with "morph": {"op", "radius_sq", "weight", "count"}, count being the voxels of the mask that is applied.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -57,8 +60,25 @@ int main(int argc_in, char const *argv_in[]) {
   bool comps = false, comps_remove = false;
   int comps_lo = 0, comps_hi = 0, comps_flags = 0, comps_fill = -32768;
   long long comps_largest = -1, comps_min = -1;
-  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V])";
+  int morph_op = -1;  // clwh_morph_op of the dilate= | erode= | open= | close= item, or -1
+  float morph_radius = 0.0f;
+  // whether `v` is that item; *ok is cleared if its radius is not a number >= 0
+  const auto morph_item = [&](const std::string &v, bool *ok) {
+    static const char *const names[4] = {"dilate=", "erode=", "open=", "close="};
+    for (int op = 0; op < 4; ++op) {
+      const std::string name = names[op];
+      if (v.rfind(name, 0) != 0) continue;
+      char *end = nullptr;
+      const float radius = std::strtof(v.c_str() + name.size(), &end);
+      *ok = *ok && v.size() > name.size() && *end == '\0' && radius >= 0.0f && radius <= 4095.0f && morph_op < 0;
+      morph_op = op;
+      morph_radius = radius;
+      return true;
+    }
+    return false;
+  };
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -141,6 +161,7 @@ int main(int argc_in, char const *argv_in[]) {
           }
         } else if (v == "26") {
           grow_flags |= CLWH_GROW_26;
+        } else if (morph_item(v, &ok)) {
         } else if (v == "keep" || v == "remove") {
           grow_remove = v == "remove";
         } else if (v.rfind("fill=", 0) == 0) {
@@ -175,6 +196,7 @@ int main(int argc_in, char const *argv_in[]) {
           (field == 0 ? comps_lo : comps_hi) = (int)n;
         } else if (v == "26") {
           comps_flags |= CLWH_LABEL_26;
+        } else if (morph_item(v, &ok)) {
         } else if (v == "keep" || v == "remove") {
           comps_remove = v == "remove";
         } else if (v.rfind("fill=", 0) == 0) {
@@ -257,13 +279,14 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
   const int width = argc > 4 ? std::atoi(argv[4]) : 1920;
   const int height = argc > 5 ? std::atoi(argv[5]) : 1080;
 
+  static const char *const kMorphNames[4] = {"dilate", "erode", "open", "close"};
   clw_context ctx;
   renderer r(ctx);
   frame_emitter *emitter = &r;
@@ -287,12 +310,18 @@ int main(int argc_in, char const *argv_in[]) {
       }
     ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
     const clwh_grow_result g = r.grow_region(none, {grow_seed[0], grow_seed[1], grow_seed[2]}, grow_lo, grow_hi, grow_flags);
+    renderer::morph_summary m;
+    if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
     r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
-                "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d}\n",
+                "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
                 grow_seed[0], grow_seed[1], grow_seed[2], grow_lo, grow_hi, (grow_flags & CLWH_GROW_26) ? 26 : 6, grow_remove ? "remove" : "keep",
                 grow_fill, (unsigned long long)g.count, g.bbox_lo[0], g.bbox_lo[1], g.bbox_lo[2], g.bbox_hi[0], g.bbox_hi[1], g.bbox_hi[2],
                 g.count ? (double)g.sum / (double)g.count : 0.0, g.vmin, g.vmax);
+    if (morph_op >= 0)
+      std::printf(", \"morph\": {\"op\": \"%s\", \"radius_sq\": %u, \"weight\": [%u, %u, %u], \"count\": %llu}", kMorphNames[morph_op], m.radius_sq,
+                  m.weight[0], m.weight[1], m.weight[2], (unsigned long long)m.count);
+    std::printf("}\n");
   }
 
   if (comps) {  // like --grow: everything below sees the masked volume
@@ -312,6 +341,8 @@ int main(int argc_in, char const *argv_in[]) {
     // (no component selected: a rank nobody has gives the empty mask)
     if (keep > 0) r.select_components(none, 1, (uint32_t)keep);
     else r.select_components(none, (uint32_t)c.n_components + 1u, (uint32_t)c.n_components + 1u);
+    renderer::morph_summary m;
+    if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
     r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"components\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"n_components\": %llu, \"n_voxels\": %llu, "
                 "\"selected\": [%u, %llu], \"largest\": [",
@@ -323,7 +354,11 @@ int main(int argc_in, char const *argv_in[]) {
                   (unsigned long long)t.count, t.first[0], t.first[1], t.first[2], t.bbox_lo[0], t.bbox_lo[1], t.bbox_lo[2], t.bbox_hi[0],
                   t.bbox_hi[1], t.bbox_hi[2]);
     }
-    std::printf("]}\n");
+    std::printf("]");
+    if (morph_op >= 0)
+      std::printf(", \"morph\": {\"op\": \"%s\", \"radius_sq\": %u, \"weight\": [%u, %u, %u], \"count\": %llu}", kMorphNames[morph_op], m.radius_sq,
+                  m.weight[0], m.weight[1], m.weight[2], (unsigned long long)m.count);
+    std::printf("}\n");
   }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera

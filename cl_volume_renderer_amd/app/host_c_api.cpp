@@ -154,6 +154,24 @@ unsigned clvr_host_label_components(clvr_host *h, int lo, int hi, int flags, uns
 }
 // renderer::select_components: ranks rank_lo .. rank_hi of the last labelling become the mask clvr_host_apply_mask applies
 void clvr_host_select_components(clvr_host *h, unsigned rank_lo, unsigned rank_hi) { h->rend.select_components(h->state, rank_lo, rank_hi); }
+// the voxel sizes relative to x that renderer::mask_weights reads (clvr_host_load sets 1, 1, 1)
+void clvr_host_set_voxel_sizes(clvr_host *h, const float sizes[3]) { h->rv->set_voxel_sizes({sizes[0], sizes[1], sizes[2]}); }
+// renderer::distance_map of the region mask into out[Z][Y][X]
+void clvr_host_distance_map(clvr_host *h, int to_clear, unsigned cap, unsigned *out) {
+  const std::vector<uint32_t> map = h->rend.distance_map(h->state, to_clear != 0, cap);
+  std::memcpy(out, map.data(), map.size() * sizeof(uint32_t));
+}
+// renderer::morph_mask: the region mask morphed in place by a ball of `radius` x-voxels; out = {radius_sq, wx, wy, wz}; returns the
+// new region's voxel count
+unsigned long long clvr_host_morph_mask(clvr_host *h, int op, float radius, unsigned out[4]) {
+  const renderer::morph_summary s = h->rend.morph_mask(h->state, op, radius);
+  out[0] = s.radius_sq;
+  for (int q = 0; q < 3; ++q) out[1 + q] = s.weight[q];
+  return s.count;
+}
+// renderer::hold_mask / combine_masks: region = region op held
+void clvr_host_hold_mask(clvr_host *h) { h->rend.hold_mask(h->state); }
+void clvr_host_combine_masks(clvr_host *h, int op) { h->rend.combine_masks(h->state, op); }
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

@@ -14,6 +14,7 @@ reference_volume::reference_volume(clw_context &c, volume_block *b)
     : ctx(c),
       volume_size({b->m_voxel_count_x, b->m_voxel_count_y, b->m_voxel_count_z}),
       cropped_volume_size(volume_size),
+      voxel_sizes({b->m_voxel_size_x, b->m_voxel_size_y, b->m_voxel_size_z}),
       original_volume(ctx, std::move(b->m_voxels), volume_size, true),
       cropped_volume(ctx, std::vector<short>(8), {2, 2, 2}, false) {
   const int lowest = std::numeric_limits<int>::min(), highest = std::numeric_limits<int>::max();

@@ -34,6 +34,9 @@ class reference_volume {
   const std::array<size_t, 3> &get_original_volume_size() const { return volume_size; }
   const std::array<size_t, 3> &get_volume_size() const { return cropped_volume_size; }
   std::array<size_t, 3> get_volume_size_evenness(unsigned int l) const;
+  /// the block's voxel sizes relative to x (the NRRD loader's); not in the reference, which parses and drops them
+  const std::array<float, 3> &get_voxel_sizes() const { return voxel_sizes; }
+  void set_voxel_sizes(std::array<float, 3> sizes) { voxel_sizes = sizes; }
   size_t get_volume_length() const { return cropped_volume_size[0] * cropped_volume_size[1] * cropped_volume_size[2]; }
   const clw_image<short> &get_reference_volume() const { return is_cropped() ? cropped_volume : original_volume; }
   Volume_Stats get_volume_stats() const { return Volume_Stats(get_value_range(), get_gradient_range()); }
@@ -43,6 +46,7 @@ class reference_volume {
   clw_context &ctx;
   std::array<size_t, 3> volume_size;
   std::array<size_t, 3> cropped_volume_size;
+  std::array<float, 3> voxel_sizes{1.f, 1.f, 1.f};
   clw_image<short> original_volume;
   clw_image<short> cropped_volume;
   std::array<int, 2> value_range{0, 0};     // over the original volume

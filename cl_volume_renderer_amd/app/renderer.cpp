@@ -24,6 +24,7 @@ renderer::renderer(clw_context &c)
       tfframe(ctx, std::vector<unsigned char>(2 * 2 * 4), {2, 2, 1}),
       composite_lut(ctx, std::vector<float>(4)),
       region_mask(ctx, std::vector<uint32_t>(2)),
+      held_mask(ctx, std::vector<uint32_t>(2)),
       region_labels(ctx, std::vector<uint32_t>(1)),
       sdf(ctx) {}
 
@@ -312,6 +313,80 @@ void renderer::select_components(struct ui_state &, uint32_t rank_lo, uint32_t r
   d.rank_lo = rank_lo;
   d.rank_hi = rank_hi;
   clw_fail_hard_on_error(clwh_labels_to_mask(ctx.get_handle(), &d));
+}
+
+void renderer::mask_weights(uint32_t weight[3]) const {
+  const auto &sizes = volume->get_voxel_sizes();
+  for (int q = 0; q < 3; ++q) {
+    const double s = (double)sizes[q] * 16.0;
+    weight[q] = (uint32_t)std::max(1.0, std::nearbyint(s * s));  // round to nearest, halves to even, like Python's round
+  }
+}
+
+uint32_t renderer::mask_radius_sq(float radius) {
+  const double r = (double)radius * 16.0;
+  return (uint32_t)std::min(std::floor(r * r), 4294967295.0);
+}
+
+std::vector<uint32_t> renderer::distance_map(struct ui_state &, bool to_clear, uint32_t cap) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  clw_vector<uint32_t> map(ctx, std::vector<uint32_t>(size[0] * size[1] * size[2]), false);
+  clwh_distance_desc d{};
+  d.mask = region_mask.get_device_reference();
+  d.dist = map.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  mask_weights(d.weight);
+  d.cap = cap;
+  d.flags = to_clear ? CLWH_DIST_TO_CLEAR : 0;
+  clw_fail_hard_on_error(clwh_mask_distance(ctx.get_handle(), &d));
+  map.pull();
+  return std::vector<uint32_t>(&map[0], &map[0] + map.size());
+}
+
+renderer::morph_summary renderer::morph_mask(struct ui_state &, int op, float radius) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  morph_summary out;
+  out.op = op;
+  out.radius_sq = mask_radius_sq(radius);
+  mask_weights(out.weight);
+  clwh_morph_desc d{};
+  d.mask_in = d.mask_out = region_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    d.dims[q] = (uint32_t)size[q];
+    d.weight[q] = out.weight[q];
+  }
+  d.radius_sq = out.radius_sq;
+  d.op = op;
+  clw_fail_hard_on_error(clwh_mask_morph(ctx.get_handle(), &d));
+  region_mask.pull();  // (padding is clean: every set bit is a voxel)
+  for (size_t i = 0; i < region_mask.size(); ++i) out.count += (uint64_t)__builtin_popcount(region_mask[i]);
+  return out;
+}
+
+void renderer::hold_mask(struct ui_state &) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  if (held_mask.size() != region_mask.size()) held_mask = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(region_mask.size()), false);
+  clwh_mask_combine_desc d{};
+  d.a = d.b = region_mask.get_device_reference();  // region AND region: the copy, with clean padding
+  d.out = held_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.op = CLWH_MASK_AND;
+  clw_fail_hard_on_error(clwh_mask_combine(ctx.get_handle(), &d));
+}
+
+void renderer::combine_masks(struct ui_state &, int op) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  if (op != CLWH_MASK_NOT && held_mask.size() != region_mask.size()) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);   // nothing held
+  clwh_mask_combine_desc d{};
+  d.a = d.out = region_mask.get_device_reference();
+  d.b = op != CLWH_MASK_NOT ? held_mask.get_device_reference() : nullptr;
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.op = op;
+  clw_fail_hard_on_error(clwh_mask_combine(ctx.get_handle(), &d));
 }
 
 // (the host is little-endian, like every target of the library: the arrays go out as they lie in memory)

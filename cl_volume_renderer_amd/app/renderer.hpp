@@ -103,6 +103,30 @@ class renderer : public frame_emitter {
   // ... and the components of ranks rank_lo .. rank_hi of the last labelling as the region mask (clwh_labels_to_mask), for apply_mask
   void select_components(struct ui_state &state, uint32_t rank_lo, uint32_t rank_hi);
 
+  // not in the reference: distances, ball morphology and algebra of the region mask (clwh_mask_distance / clwh_mask_morph /
+  // clwh_mask_combine), whoever made it: grow_region, select_components or these.  Lengths are counted in 1/16 of an x-voxel: the
+  // weight of an axis is round((voxel size relative to x * 16)^2), at least 1, from the volume block's voxel sizes, and a radius r
+  // in x-voxels is radius_sq = floor((r * 16)^2); this rounding is the only place where float spacing becomes integers.  No camera
+  // takes part (`state` is not read).
+  void mask_weights(uint32_t weight[3]) const;
+  static uint32_t mask_radius_sq(float radius);
+  // the exact squared distance of every voxel to the nearest voxel of the region (to_clear: to the nearest voxel outside it) in that
+  // unit, uint32 [z][y][x], CLWH_DIST_NONE where there is none or the distance is above cap.  Waits for the device: the map comes back.
+  std::vector<uint32_t> distance_map(struct ui_state &state, bool to_clear = false, uint32_t cap = CLWH_DIST_NONE);
+  // the region dilated, eroded, opened or closed (clwh_morph_op) in place by a ball of `radius` x-voxels; the volume's border does
+  // not erode.  Returns what was asked of the library and the number of voxels of the new region (the mask is pulled and counted).
+  struct morph_summary {
+    int op = 0;
+    uint32_t radius_sq = 0, weight[3] = {1, 1, 1};
+    uint64_t count = 0;
+  };
+  morph_summary morph_mask(struct ui_state &state, int op, float radius);
+  // hold_mask keeps a copy of the region mask on the device; combine_masks replaces the region by (region op held), clwh_mask_op
+  // (CLWH_MASK_NOT: the complement of the region within the volume, nothing need be held): "the grown region with its margin,
+  // without the bone" is grow, hold, morph_mask(DILATE), combine_masks(ANDNOT).
+  void hold_mask(struct ui_state &state);
+  void combine_masks(struct ui_state &state, int op);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }
@@ -116,6 +140,7 @@ class renderer : public frame_emitter {
   clw_vector<float> composite_lut;           // render_composite's table on the device (host copy = the last one pushed)
   bool composite_lut_pushed = false;
   clw_vector<uint32_t> region_mask;          // grow_region's mask on the device (never pulled: the host side only sizes it)
+  clw_vector<uint32_t> held_mask;            // hold_mask's copy of region_mask (never pulled)
   clw_vector<uint32_t> region_labels;        // label_components' ranks on the device, one word per voxel (never pulled)
   const reference_volume *volume = nullptr;  // borrowed
   const env_map *emap = nullptr;             // borrowed

@@ -470,4 +470,19 @@ hipError_t launch_label_ranks(const LabelArgs &a, hipStream_t s);    // the tabl
 hipError_t launch_labels_to_mask(const uint32_t *labels, unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64, uint32_t rank_lo,
                                  uint32_t rank_hi, hipStream_t s);
 
+// ---- distance maps of masks, ball morphology and mask algebra (distance_kernels.hip; host side clwh_distance.hip), over grow's bit rows
+struct DistArgs {
+  int32_t X, Y, Z, W64;
+  uint32_t weight[3];          // wx, wy, wz >= 1
+  unsigned long long cap;      // values above it become NONE; ~0ull: no cap
+};
+hipError_t launch_dist_rows(const DistArgs &a, const unsigned long long *mask, uint32_t *out, int32_t flip, hipStream_t s);  // along x, from the bits
+hipError_t launch_dist_lines(const DistArgs &a, const uint32_t *src, uint32_t *dst, int32_t along_z, hipStream_t s);       // along y or z; src != dst
+// the same pass by two linear scans per line; `stack`: a map's worth of words, dst holds the other half of the stack meanwhile
+hipError_t launch_dist_lines_scan(const DistArgs &a, const uint32_t *src, uint32_t *dst, uint32_t *stack, int32_t along_z, hipStream_t s);
+// the pass along z with the comparison instead of the map: bit = (value <= cap) != invert, padding clean
+hipError_t launch_dist_lines_bits(const DistArgs &a, const uint32_t *src, unsigned long long *bits, int32_t invert, hipStream_t s);
+hipError_t launch_mask_combine(const unsigned long long *a, const unsigned long long *b, unsigned long long *out, int32_t X, int32_t Y,
+                               int32_t Z, int32_t W64, int32_t op, hipStream_t s);
+
 }  // namespace clvr

@@ -28,6 +28,10 @@ MESH_DENSE, MESH_BELOW = 1, 2
 GROW_26, GROW_FROM_MASK, GROW_DENSE = 1, 2, 4
 GROW_MAX_SEEDS = 65536
 LABEL_26, LABEL_FROM_MASK = 1, 2
+DIST_NONE = 0xFFFFFFFF
+DIST_TO_CLEAR = 1
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
@@ -218,6 +222,20 @@ class LabelsToMaskDesc(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("mask", C.c_void_p), ("dims", C.c_uint32 * 3), ("rank_lo", C.c_uint32), ("rank_hi", C.c_uint32)]
 
 
+class DistanceDesc(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("dist", C.c_void_p), ("dims", C.c_uint32 * 3), ("weight", C.c_uint32 * 3), ("cap", C.c_uint32),
+                ("flags", C.c_int32)]
+
+
+class MorphDesc(C.Structure):
+    _fields_ = [("mask_in", C.c_void_p), ("mask_out", C.c_void_p), ("dims", C.c_uint32 * 3), ("weight", C.c_uint32 * 3),
+                ("radius_sq", C.c_uint32), ("op", C.c_int32), ("flags", C.c_int32)]
+
+
+class MaskCombineDesc(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -261,6 +279,9 @@ _PROTOTYPES = [
     ("clwh_volume_apply_mask", C.c_int, [C.c_void_p, C.POINTER(ApplyMaskDesc)]),
     ("clwh_segment_label", C.c_int, [C.c_void_p, C.POINTER(LabelDesc)]),
     ("clwh_labels_to_mask", C.c_int, [C.c_void_p, C.POINTER(LabelsToMaskDesc)]),
+    ("clwh_mask_distance", C.c_int, [C.c_void_p, C.POINTER(DistanceDesc)]),
+    ("clwh_mask_morph", C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
+    ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -773,6 +794,78 @@ class Context:
             return out, res, keep
         finally:
             labels.release()
+
+    def mask_distance_raw(self, mask: Mem, dist: Mem, dims, weights=(1, 1, 1), cap=DIST_NONE, flags=0):
+        """one clwh_mask_distance call: its status; nothing is raised.  dims = (X, Y, Z), weights = (wx, wy, wz)"""
+        d = DistanceDesc()
+        d.mask, d.dist = _handle(mask), _handle(dist)
+        for k in range(3):
+            d.dims[k], d.weight[k] = int(dims[k]), int(weights[k])
+        d.cap, d.flags = int(cap), int(flags)
+        return lib().clwh_mask_distance(self.h, C.byref(d))
+
+    def mask_distance(self, mask: Mem, dims, weights=(1, 1, 1), to_clear=False, cap=None, dist: Mem = None) -> Mem:
+        """the exact squared distance of every voxel of a volume of dims = (X, Y, Z) to the nearest set voxel of `mask` (to_clear: to
+        the nearest clear one), wx dx^2 + wy dy^2 + wz dz^2 in integers: uint32 [z][y][x] on the device, DIST_NONE where there is no
+        such voxel or the distance is above `cap`; allocated when none is given.  Ordered on the context's stream; does not wait."""
+        own = dist is None
+        if own:
+            shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+            dist = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        status = self.mask_distance_raw(mask, dist, dims, weights, DIST_NONE if cap is None else cap, DIST_TO_CLEAR if to_clear else 0)
+        if status != OK and own:
+            dist.release()
+        _check(status, "clwh_mask_distance")
+        return dist
+
+    def _new_mask(self, dims) -> Mem:
+        from . import scene
+
+        n = scene.mask_words_per_row(int(dims[0])) * int(dims[1]) * int(dims[2])
+        return self.buffer(4 * n, np.uint32, (n,))
+
+    def mask_morph_raw(self, mask_in: Mem, mask_out: Mem, dims, op, radius_sq, weights=(1, 1, 1), flags=0):
+        """one clwh_mask_morph call: its status; nothing is raised"""
+        d = MorphDesc()
+        d.mask_in, d.mask_out = _handle(mask_in), _handle(mask_out)
+        for k in range(3):
+            d.dims[k], d.weight[k] = int(dims[k]), int(weights[k])
+        d.radius_sq, d.op, d.flags = int(radius_sq), int(op), int(flags)
+        return lib().clwh_mask_morph(self.h, C.byref(d))
+
+    def mask_morph(self, mask: Mem, dims, op, radius_sq, weights=(1, 1, 1), out: Mem = None) -> Mem:
+        """`mask` dilated, eroded, opened or closed (MORPH_*) by the ball wx dx^2 + wy dy^2 + wz dz^2 <= radius_sq
+        (scene.mask_weights / scene.radius_sq turn voxel sizes and a radius into these integers); the volume's border does not erode.
+        `out` may be `mask`; allocated when none is given.  Ordered on the context's stream; does not wait."""
+        own = out is None
+        if own:
+            out = self._new_mask(dims)
+        status = self.mask_morph_raw(mask, out, dims, op, radius_sq, weights)
+        if status != OK and own:
+            out.release()
+        _check(status, "clwh_mask_morph")
+        return out
+
+    def mask_combine_raw(self, a: Mem, b: Mem, out: Mem, dims, op):
+        """one clwh_mask_combine call: its status; nothing is raised"""
+        d = MaskCombineDesc()
+        d.a, d.b, d.out = _handle(a), _handle(b), _handle(out)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        d.op = int(op)
+        return lib().clwh_mask_combine(self.h, C.byref(d))
+
+    def mask_combine(self, a: Mem, b: Mem, op, dims, out: Mem = None) -> Mem:
+        """a AND b, a OR b, a XOR b, a AND NOT b or NOT a (MASK_*; b may be None for MASK_NOT) of two masks of a volume of dims =
+        (X, Y, Z), with clean padding; `out` may be `a` or `b`; allocated when none is given.  Does not wait."""
+        own = out is None
+        if own:
+            out = self._new_mask(dims)
+        status = self.mask_combine_raw(a, b, out, dims, op)
+        if status != OK and own:
+            out.release()
+        _check(status, "clwh_mask_combine")
+        return out
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -668,6 +668,83 @@ typedef struct clwh_labels_to_mask_desc {
 } clwh_labels_to_mask_desc;
 int clwh_labels_to_mask(clwh_ctx *ctx, const clwh_labels_to_mask_desc *desc);
 
+/* ---- the exact squared distance map of a mask (not in the reference): "how far is every voxel from this structure", "how deep inside
+ * it am I".  The squared Euclidean distance between voxel centres with an integer weight per axis is an integer, so the map, every
+ * threshold of it and the morphology below are defined bit for bit.
+ * Sites.  S = the voxels of the volume (dims = X, Y, Z) whose bit in `mask` (clwh_segment_grow's mask layout; read only) is set; with
+ * CLWH_DIST_TO_CLEAR the voxels of the volume whose bit is clear.  Voxels outside the volume do not exist: they are neither set nor
+ * clear.  Bits at x >= X and the padding words of `mask` are ignored, whatever they hold.
+ * Distance.  D(p) = min over q in S of wx (p.x - q.x)^2 + wy (p.y - q.y)^2 + wz (p.z - q.z)^2; CLWH_DIST_NONE if S is empty.
+ * Weights.  wx, wy, wz >= 1 and wx (X - 1)^2 + wy (Y - 1)^2 + wz (Z - 1)^2 <= 2^32 - 2 (computed in 64 bits): every finite D fits a
+ * uint32 and never equals CLWH_DIST_NONE.  (49, 49, 625) are voxels of 0.7 x 0.7 x 2.5 mm in units of 0.01 mm^2; (1, 1, 1) is voxels.
+ * Output.  `dist`: a plain device buffer, 4-byte aligned, uint32 [Z][Y][X] without padding; dist(p) = D(p) if D(p) <= cap, else
+ * CLWH_DIST_NONE (cap = CLWH_DIST_NONE: no cap).  All X * Y * Z words are written and nothing behind them.  A cap lets the kernels look
+ * no farther than sqrt(cap / w) along an axis: same bytes, by the contract.
+ * Limits.  Those of clwh_labels_to_mask: no dim of 0, dims within the projections' rule, X * Y * Z <= 2^31 - 1.
+ * Asynchronous and ordered on the context's stream, like clwh_volume_apply_mask; no host result, no derived data.  Scratch: two maps of
+ * 4 * X * Y * Z bytes each, 1 GiB together at 512^3 (a pass along an axis reads one buffer and writes another, so that a line of any
+ * length takes the same path, and keeps a stack of as many words), kept with the context like grow's; it holds nothing between calls.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a mask that breaks grow's rules (NULL, an image,
+ * not 8-byte aligned); a NULL dist, a dist that is an image or not 4-byte aligned; unknown flag bits; dims that break the limits; a
+ * weight of 0 or weights beyond the bound.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than its layout, dist smaller than 4 * X * Y * Z
+ * bytes.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written on any of these. */
+#define CLWH_DIST_NONE 0xFFFFFFFFu
+enum clwh_distance_flags { CLWH_DIST_TO_CLEAR = 1 };
+typedef struct clwh_distance_desc {
+  clwh_mem *mask;             /* plain device buffer in the mask layout; read only */
+  clwh_mem *dist;             /* plain device buffer, uint32[Z][Y][X] */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t weight[3];         /* wx, wy, wz >= 1 */
+  uint32_t cap;               /* CLWH_DIST_NONE = no cap */
+  int32_t flags;
+} clwh_distance_desc;
+int clwh_mask_distance(clwh_ctx *ctx, const clwh_distance_desc *desc);
+
+/* ---- dilation, erosion, opening and closing of a mask by a ball (not in the reference): "this lesion plus 5 mm", "peel one
+ * millimetre off", "close the pinholes", "break the thin bridge".  The ball is { d : wx d.x^2 + wy d.y^2 + wz d.z^2 <= radius_sq }:
+ * anisotropic through the weights, in their unit.  With D_set and D_clear clwh_mask_distance's maps of M = mask_in without and with
+ * CLWH_DIST_TO_CLEAR, and CLWH_DIST_NONE counting as farther than any radius_sq (0xFFFFFFFF included):
+ * DILATE(M) = { p : D_set(p) <= radius_sq };  ERODE(M) = { p in M : D_clear(p) > radius_sq };  OPEN = DILATE(ERODE(M));
+ * CLOSE = ERODE(DILATE(M)), both steps with the same ball.
+ * The volume's border does not erode: voxels outside the volume are not clear (they do not exist), so a structure that the scan box
+ * cuts through keeps its cut face, a full mask erodes to itself, and CLOSE has no artefacts along the border.
+ * Output.  On return mask_out holds exactly that set, the bits at x >= X and the padding words zero whatever the buffers held;
+ * radius_sq = 0 therefore copies M with clean padding.  mask_out may name mask_in's memory.  Any radius_sq is allowed.
+ * Asynchronous and ordered on the context's stream; limits and the weights' rule as for clwh_mask_distance.  The comparison is made
+ * in the last pass of the distance transform (every pass capped at radius_sq), so no finished map is written.  Scratch, kept with the
+ * context: two intermediate maps of 4 bytes per voxel each (1 GiB together at 512^3) and, for OPEN and CLOSE, one mask.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; mask_in or mask_out that breaks grow's rules;
+ * an op outside 0 .. 3; flags != 0; dims that break the limits; a weight of 0 or weights beyond the bound.  CLWH_ERR_SIZE_MISMATCH: a
+ * mask smaller than its layout.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written on any of these. */
+enum clwh_morph_op { CLWH_MORPH_DILATE = 0, CLWH_MORPH_ERODE = 1, CLWH_MORPH_OPEN = 2, CLWH_MORPH_CLOSE = 3 };
+typedef struct clwh_morph_desc {
+  clwh_mem *mask_in;          /* plain device buffer in the mask layout */
+  clwh_mem *mask_out;         /* the same layout; may name mask_in's memory */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t weight[3];         /* wx, wy, wz >= 1 */
+  uint32_t radius_sq;         /* in the weights' unit; any value */
+  int32_t op;                 /* clwh_morph_op */
+  int32_t flags;              /* 0 */
+} clwh_morph_desc;
+int clwh_mask_morph(clwh_ctx *ctx, const clwh_morph_desc *desc);
+
+/* ---- mask algebra on the device (not in the reference): out = a AND b, a OR b, a XOR b, a AND NOT b, or NOT a, for masks of dims =
+ * X, Y, Z in clwh_segment_grow's layout.  CLWH_MASK_NOT ignores b, which may then be NULL; the complement is taken within the volume.
+ * Bits at x >= X and the padding words of a and b are ignored and those of out are zero on return.  out may name a's or b's memory.
+ * One kernel; asynchronous and ordered on the context's stream.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a, out or (except for CLWH_MASK_NOT) b that
+ * breaks grow's rules for a mask (NULL, an image, not 8-byte aligned); an op outside 0 .. 4; a dim of 0, dims beyond the projections'
+ * rule or X * Y * Z > 2^31 - 1.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than the layout needs.  Nothing is written on any of these. */
+enum clwh_mask_op { CLWH_MASK_AND = 0, CLWH_MASK_OR = 1, CLWH_MASK_XOR = 2, CLWH_MASK_ANDNOT = 3, CLWH_MASK_NOT = 4 };
+typedef struct clwh_mask_combine_desc {
+  clwh_mem *a;
+  clwh_mem *b;                /* ignored by CLWH_MASK_NOT, may then be NULL */
+  clwh_mem *out;              /* may name a's or b's memory */
+  uint32_t dims[3];           /* X, Y, Z */
+  int32_t op;                 /* clwh_mask_op */
+} clwh_mask_combine_desc;
+int clwh_mask_combine(clwh_ctx *ctx, const clwh_mask_combine_desc *desc);
+
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
  * per layer.  `sdf` is an S8 3-D image of the volume's dims.  n_launches (optional) receives the
