@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,18 +12,22 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
 // view, the mesh or the path-traced frames then show the masked volume.
-// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
+// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
 // labelled (renderer::label_components), the K largest or those of at least N voxels (default: all) become the mask
 // (renderer::select_components) and are applied in place like --grow's region.  One JSON line has n_components, n_voxels, the selected
 // rank range ([0, 0]: none) and count / first / bbox of up to the 8 largest.  --grow and --components exclude each other.
 // dilate=R | erode=R | open=R | close=R, an item of --grow and of --components: the mask is dilated, eroded, opened or closed by a ball
 // of R x-voxels (renderer::morph_mask: lengths in 1/16 x-voxel, the axes weighted by the file's voxel sizes) before it is applied; the
 // JSON line then ends with "morph": {"op", "radius_sq", "weight", "count"}, count being the voxels of the mask that is applied.
+// measure, an item of --grow and of --components: a second JSON line with the exact record (renderer::measure_mask: count, sum, sum_sq,
+// min, max, sum_pos, bbox, faces, border_faces) of the mask that is applied, after any morphology and before the volume is changed:
+// {"measure": {...}}; for --components {"measure_components": [...]}, the records (renderer::measure_labels) of the selected ranks,
+// rank 1 first, at most 256 of them, and with a morphology item also "measure": the record of the morphed mask.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -62,6 +66,7 @@ int main(int argc_in, char const *argv_in[]) {
   long long comps_largest = -1, comps_min = -1;
   int morph_op = -1;  // clwh_morph_op of the dilate= | erode= | open= | close= item, or -1
   float morph_radius = 0.0f;
+  bool measure = false;  // the measure item
   // whether `v` is that item; *ok is cleared if its radius is not a number >= 0
   const auto morph_item = [&](const std::string &v, bool *ok) {
     static const char *const names[4] = {"dilate=", "erode=", "open=", "close="};
@@ -77,8 +82,8 @@ int main(int argc_in, char const *argv_in[]) {
     }
     return false;
   };
-  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V])";
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -162,6 +167,8 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (v == "26") {
           grow_flags |= CLWH_GROW_26;
         } else if (morph_item(v, &ok)) {
+        } else if (v == "measure") {
+          measure = true;
         } else if (v == "keep" || v == "remove") {
           grow_remove = v == "remove";
         } else if (v.rfind("fill=", 0) == 0) {
@@ -197,6 +204,8 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (v == "26") {
           comps_flags |= CLWH_LABEL_26;
         } else if (morph_item(v, &ok)) {
+        } else if (v == "measure") {
+          measure = true;
         } else if (v == "keep" || v == "remove") {
           comps_remove = v == "remove";
         } else if (v.rfind("fill=", 0) == 0) {
@@ -279,7 +288,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -287,6 +296,13 @@ int main(int argc_in, char const *argv_in[]) {
   const int height = argc > 5 ? std::atoi(argv[5]) : 1080;
 
   static const char *const kMorphNames[4] = {"dilate", "erode", "open", "close"};
+  const auto print_record = [](const clwh_region_stats &s) {
+    std::printf("{\"count\": %llu, \"sum\": %lld, \"sum_sq\": %llu, \"min\": %d, \"max\": %d, \"sum_pos\": [%llu, %llu, %llu], "
+                "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"faces\": [%u, %u, %u], \"border_faces\": [%u, %u, %u]}",
+                (unsigned long long)s.count, (long long)s.sum, (unsigned long long)s.sum_sq, s.vmin, s.vmax, (unsigned long long)s.sum_pos[0],
+                (unsigned long long)s.sum_pos[1], (unsigned long long)s.sum_pos[2], s.bbox_lo[0], s.bbox_lo[1], s.bbox_lo[2], s.bbox_hi[0],
+                s.bbox_hi[1], s.bbox_hi[2], s.faces[0], s.faces[1], s.faces[2], s.border_faces[0], s.border_faces[1], s.border_faces[2]);
+  };
   clw_context ctx;
   renderer r(ctx);
   frame_emitter *emitter = &r;
@@ -312,6 +328,8 @@ int main(int argc_in, char const *argv_in[]) {
     const clwh_grow_result g = r.grow_region(none, {grow_seed[0], grow_seed[1], grow_seed[2]}, grow_lo, grow_hi, grow_flags);
     renderer::morph_summary m;
     if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
+    clwh_mask_stats_result measured{};
+    if (measure) measured = r.measure_mask(none);  // of the volume as loaded: before the mask changes it
     r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
@@ -322,6 +340,11 @@ int main(int argc_in, char const *argv_in[]) {
       std::printf(", \"morph\": {\"op\": \"%s\", \"radius_sq\": %u, \"weight\": [%u, %u, %u], \"count\": %llu}", kMorphNames[morph_op], m.radius_sq,
                   m.weight[0], m.weight[1], m.weight[2], (unsigned long long)m.count);
     std::printf("}\n");
+    if (measure) {
+      std::printf("{\"measure\": ");
+      print_record(measured.stats);
+      std::printf("}\n");
+    }
   }
 
   if (comps) {  // like --grow: everything below sees the masked volume
@@ -343,6 +366,10 @@ int main(int argc_in, char const *argv_in[]) {
     else r.select_components(none, (uint32_t)c.n_components + 1u, (uint32_t)c.n_components + 1u);
     renderer::morph_summary m;
     if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
+    std::vector<clwh_region_stats> measured;
+    clwh_mask_stats_result measured_mask{};
+    if (measure && keep > 0) measured = r.measure_labels(none, (unsigned)std::min<uint64_t>(keep, 256));  // before the mask changes the volume
+    if (measure && morph_op >= 0) measured_mask = r.measure_mask(none);  // the morphed mask is no longer the union of the ranks
     r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"components\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"n_components\": %llu, \"n_voxels\": %llu, "
                 "\"selected\": [%u, %llu], \"largest\": [",
@@ -359,6 +386,19 @@ int main(int argc_in, char const *argv_in[]) {
       std::printf(", \"morph\": {\"op\": \"%s\", \"radius_sq\": %u, \"weight\": [%u, %u, %u], \"count\": %llu}", kMorphNames[morph_op], m.radius_sq,
                   m.weight[0], m.weight[1], m.weight[2], (unsigned long long)m.count);
     std::printf("}\n");
+    if (measure) {
+      std::printf("{\"measure_components\": [");
+      for (size_t k = 0; k < measured.size(); ++k) {
+        if (k) std::printf(", ");
+        print_record(measured[k]);
+      }
+      std::printf("]");
+      if (morph_op >= 0) {
+        std::printf(", \"measure\": ");
+        print_record(measured_mask.stats);
+      }
+      std::printf("}\n");
+    }
   }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera

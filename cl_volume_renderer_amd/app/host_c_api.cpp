@@ -172,6 +172,18 @@ unsigned long long clvr_host_morph_mask(clvr_host *h, int op, float radius, unsi
 // renderer::hold_mask / combine_masks: region = region op held
 void clvr_host_hold_mask(clvr_host *h) { h->rend.hold_mask(h->state); }
 void clvr_host_combine_masks(clvr_host *h, int op) { h->rend.combine_masks(h->state, op); }
+// renderer::measure_mask: the region mask's record into *out (a clwh_mask_stats_result, 120 bytes); n_bins > 0: its histogram into hist
+void clvr_host_measure_mask(clvr_host *h, int hist_lo, int bin_width, int n_bins, unsigned long long *hist, void *out) {
+  std::vector<uint64_t> bins;
+  const clwh_mask_stats_result r = h->rend.measure_mask(h->state, hist_lo, bin_width, n_bins, n_bins > 0 ? &bins : nullptr);
+  if (n_bins > 0) std::memcpy(hist, bins.data(), bins.size() * sizeof(uint64_t));
+  std::memcpy(out, &r, sizeof r);
+}
+// renderer::measure_labels: the records of ranks 1 .. capacity of the last labelling into out (104 bytes each)
+void clvr_host_measure_labels(clvr_host *h, unsigned capacity, void *out) {
+  const std::vector<clwh_region_stats> table = h->rend.measure_labels(h->state, capacity);
+  std::memcpy(out, table.data(), table.size() * sizeof(clwh_region_stats));
+}
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

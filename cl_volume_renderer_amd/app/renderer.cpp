@@ -389,6 +389,48 @@ void renderer::combine_masks(struct ui_state &, int op) {
   clw_fail_hard_on_error(clwh_mask_combine(ctx.get_handle(), &d));
 }
 
+clwh_mask_stats_result renderer::measure_mask(struct ui_state &, int hist_lo, int bin_width, int n_bins, std::vector<uint64_t> *hist) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  const bool with_hist = n_bins > 0 && hist != nullptr;
+  clw_vector<uint32_t> bins(ctx, std::vector<uint32_t>(with_hist ? 2 * (size_t)n_bins : 2), false);  // uint64 words, as pairs
+  clwh_mask_stats_result result{};
+  clwh_mask_stats_desc d{};
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.mask = region_mask.get_device_reference();
+  if (with_hist) {
+    d.hist = bins.get_device_reference();
+    d.hist_lo = hist_lo;
+    d.bin_width = bin_width;
+    d.n_bins = n_bins;
+  }
+  d.result = &result;
+  clw_fail_hard_on_error(clwh_mask_statistics(ctx.get_handle(), &d));
+  if (with_hist) {
+    bins.pull();
+    hist->resize((size_t)n_bins);
+    std::memcpy(hist->data(), &bins[0], (size_t)n_bins * sizeof(uint64_t));
+  }
+  return result;
+}
+
+std::vector<clwh_region_stats> renderer::measure_labels(struct ui_state &, unsigned capacity) {
+  const auto &size = volume->get_volume_size();
+  if (region_labels.size() != (size_t)size[0] * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // nothing was labelled
+  constexpr size_t record_words = sizeof(clwh_region_stats) / sizeof(uint32_t);
+  clw_vector<uint32_t> table(ctx, std::vector<uint32_t>(std::max<size_t>(capacity, 1) * record_words), false);
+  clwh_label_stats_desc d{};
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  d.stats = table.get_device_reference();
+  d.capacity = capacity;
+  clw_fail_hard_on_error(clwh_label_statistics(ctx.get_handle(), &d));
+  table.pull();  // (waits for the stream)
+  std::vector<clwh_region_stats> out(capacity);
+  if (capacity) std::memcpy(out.data(), &table[0], (size_t)capacity * sizeof(clwh_region_stats));
+  return out;
+}
+
 // (the host is little-endian, like every target of the library: the arrays go out as they lie in memory)
 bool write_ply(const std::string &path, const mesh_data &mesh) {
   const size_t nv = mesh.positions.size() / 3, nt = mesh.triangles.size() / 3;

@@ -127,6 +127,17 @@ class renderer : public frame_emitter {
   void hold_mask(struct ui_state &state);
   void combine_masks(struct ui_state &state, int op);
 
+  // not in the reference: measuring (clwh_mask_statistics / clwh_label_statistics) on the volume the views show.  measure_mask: the
+  // exact record of the region mask, whoever made it (count, sum, sum of squares, extremes, centroid numerators, bounding box, faces
+  // per axis inside the volume and on its border), and with n_bins > 0 the histogram of its values, n_bins bins of bin_width from
+  // hist_lo on, into *hist, the voxels under and over the range in the result.  Measure BEFORE apply_mask if the region is to be
+  // removed: the record is of the volume as it is on the device.  measure_labels: one record per rank 1 .. capacity of the last
+  // labelling (the zero record for a rank nobody has).  Both wait for the device; no camera takes part (`state` is not read).
+  // region_measures in scene.py shows how the integers become millimetres.
+  clwh_mask_stats_result measure_mask(struct ui_state &state, int hist_lo = 0, int bin_width = 0, int n_bins = 0,
+                                      std::vector<uint64_t> *hist = nullptr);
+  std::vector<clwh_region_stats> measure_labels(struct ui_state &state, unsigned capacity);
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }

@@ -165,6 +165,7 @@ Tuning clvr::tuning_from_environment() {
   if (const char *e = std::getenv("CLWH_TUNE_BOUNCE_RAYS")) t.bounce_rays = std::atoi(e) == 2 ? 2 : 1;
   if (const char *e = std::getenv("CLWH_TUNE_SDF")) t.sdf_front = std::strcmp(e, "front") == 0;
   if (const char *e = std::getenv("CLWH_TUNE_DIST_LINES")) t.dist_lines = std::strcmp(e, "scan") == 0 ? 1 : std::strcmp(e, "search") == 0 ? 2 : 0;
+  if (const char *e = std::getenv("CLWH_TUNE_LABEL_STATS")) t.label_stats = std::strcmp(e, "item") == 0 ? 1 : std::strcmp(e, "direct") == 0 ? 2 : 0;
   if (const char *e = std::getenv("CLWH_TUNE_SLICE_COARSE")) t.slice_coarse = std::atoi(e) != 0;
   if (const char *e = std::getenv("CLWH_TUNE_SDFBIT_WAVES")) t.sdfbit_waves = std::atoi(e) == 16 ? 16 : 8;
   if (const char *e = std::getenv("CLWH_TUNE_SDFBIT_GRID")) t.sdfbit_grid = std::max(1, std::atoi(e));

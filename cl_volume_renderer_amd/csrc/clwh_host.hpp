@@ -2,7 +2,7 @@
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces and slices; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
-// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra).
+// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
 #pragma once
 
@@ -146,6 +146,8 @@ struct Tuning {
   int32_t sdfbit_rec_lds = 0;  // CLWH_TUNE_SDFBIT_REC=lds: the layer records in LDS, three blocks of eight waves per CU (grid x 3 / 2)
   int32_t sdf_front = 0;       // CLWH_TUNE_SDF=front: the byte-front build (one launch per layer) instead of the bit-parallel one
   int32_t dist_lines = 0;      // CLWH_TUNE_DIST_LINES=search: clwh_mask_distance's passes along y and z by the outward search (2) instead of the two linear scans (0, 1)
+  int32_t label_stats = 0;     // CLWH_TUNE_LABEL_STATS=item: clwh_label_statistics' lanes hand their part on after every eight voxels (1); =direct: parts go
+                               // to memory, not through the block's table (2).  Both lost; same bytes either way
   int32_t slice_coarse = 1;    // CLWH_TUNE_SLICE_COARSE=0: k_slice's skipping walk asks the bricks' table only, not the cells of 4^3 bricks
 };
 Tuning tuning_from_environment();
@@ -235,6 +237,12 @@ struct DistanceScratch {
   DeviceBuffer map_a, map_b, bits;
 };
 
+// clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
+// Every call rewrites what it reads: only the allocation is kept.
+struct RegionStatsScratch {
+  DeviceBuffer result;
+};
+
 // intensity projections and compositing: the volume in brick order + the per-brick {min, max} table (one allocation, per context,
 // shared by clwh_render_projection and clwh_render_composite), and the key of the content it was built from (device pointer, shared
 // content version, dims).  Beside it the derived data of compositing's colour/opacity table: the prefix count of entries with
@@ -289,6 +297,7 @@ struct clwh_ctx {
   clvr::GrowScratch grow;
   clvr::LabelScratch label;
   clvr::DistanceScratch distance;
+  clvr::RegionStatsScratch region_stats;
   clvr::ProjectionData proj;
   clvr::DeviceBuffer bilateral_weights;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)
   // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per

@@ -485,4 +485,30 @@ hipError_t launch_dist_lines_bits(const DistArgs &a, const uint32_t *src, unsign
 hipError_t launch_mask_combine(const unsigned long long *a, const unsigned long long *b, unsigned long long *out, int32_t X, int32_t Y,
                                int32_t Z, int32_t W64, int32_t op, hipStream_t s);
 
+// ---- exact statistics of a mask's region and of every rank of a labelling (region_stats_kernels.hip; host side clwh_region_stats.hip).
+// Records are accumulated in place, in clwh_region_stats' layout: launch_stats_init sets the identities (extremes, bbox_lo), the sums'
+// kernels add with vector atomics, launch_stats_finish writes the empty record where nothing was added and makes bbox_hi exclusive.
+struct MaskStatsArgs {
+  const int16_t *volume;       // the caller's image, x fastest
+  const uint8_t *mask;         // grow's bit rows, read only
+  int32_t X, Y, Z, W64;
+  clwh_region_stats *result;   // one record
+  unsigned long long *tails;   // {hist_below, hist_above}, zero on entry
+  unsigned long long *hist;    // n_bins words, zero on entry; nullptr: no histogram
+  int32_t hist_lo;
+  uint32_t bin_width, n_bins;
+};
+struct LabelStatsArgs {
+  const int16_t *volume;
+  const uint32_t *labels;      // [z][y][x]
+  int32_t X, Y, Z;
+  uint32_t capacity;           // ranks 1 .. capacity have a record
+  int32_t mode;                // Tuning::label_stats: 0 as built; 1, 2: the experiments it was timed against
+  clwh_region_stats *stats;
+};
+hipError_t launch_stats_init(clwh_region_stats *stats, uint32_t n, hipStream_t s);
+hipError_t launch_stats_finish(clwh_region_stats *stats, uint32_t n, hipStream_t s);
+hipError_t launch_mask_stats(const MaskStatsArgs &a, hipStream_t s);
+hipError_t launch_label_stats(const LabelStatsArgs &a, hipStream_t s);
+
 }  // namespace clvr

@@ -236,6 +236,43 @@ class MaskCombineDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
 
 
+class RegionStats(C.Structure):
+    _fields_ = [
+        ("count", C.c_uint64), ("sum", C.c_int64), ("sum_sq", C.c_uint64),
+        ("vmin", C.c_int32), ("vmax", C.c_int32),
+        ("sum_pos", C.c_uint64 * 3),
+        ("bbox_lo", C.c_uint32 * 3), ("bbox_hi", C.c_uint32 * 3),
+        ("faces", C.c_uint32 * 3), ("border_faces", C.c_uint32 * 3),
+    ]
+
+    def as_dict(self):
+        return {"count": int(self.count), "sum": int(self.sum), "sum_sq": int(self.sum_sq), "vmin": int(self.vmin), "vmax": int(self.vmax),
+                "sum_pos": tuple(int(v) for v in self.sum_pos), "bbox_lo": tuple(self.bbox_lo), "bbox_hi": tuple(self.bbox_hi),
+                "faces": tuple(self.faces), "border_faces": tuple(self.border_faces)}
+
+
+# the same record as a numpy dtype (scene.REGION_STATS_DTYPE): what Context.label_statistics' table holds
+REGION_STATS_DTYPE = np.dtype([("count", np.uint64), ("sum", np.int64), ("sum_sq", np.uint64), ("vmin", np.int32), ("vmax", np.int32),
+                               ("sum_pos", np.uint64, (3,)), ("bbox_lo", np.uint32, (3,)), ("bbox_hi", np.uint32, (3,)),
+                               ("faces", np.uint32, (3,)), ("border_faces", np.uint32, (3,))])
+assert REGION_STATS_DTYPE.itemsize == C.sizeof(RegionStats) == 104
+LABEL_STATS_MAX_CAPACITY = 1 << 24
+
+
+class MaskStatsResult(C.Structure):
+    _fields_ = [("stats", RegionStats), ("hist_below", C.c_uint64), ("hist_above", C.c_uint64)]
+
+
+class MaskStatsDesc(C.Structure):
+    _fields_ = [("volume", C.c_void_p), ("mask", C.c_void_p), ("hist", C.c_void_p), ("hist_lo", C.c_int32), ("bin_width", C.c_int32),
+                ("n_bins", C.c_int32), ("flags", C.c_int32), ("result", C.POINTER(MaskStatsResult))]
+
+
+class LabelStatsDesc(C.Structure):
+    _fields_ = [("volume", C.c_void_p), ("labels", C.c_void_p), ("stats", C.c_void_p), ("capacity", C.c_uint64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -282,6 +319,8 @@ _PROTOTYPES = [
     ("clwh_mask_distance", C.c_int, [C.c_void_p, C.POINTER(DistanceDesc)]),
     ("clwh_mask_morph", C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
+    ("clwh_mask_statistics", C.c_int, [C.c_void_p, C.POINTER(MaskStatsDesc)]),
+    ("clwh_label_statistics", C.c_int, [C.c_void_p, C.POINTER(LabelStatsDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -866,6 +905,55 @@ class Context:
             out.release()
         _check(status, "clwh_mask_combine")
         return out
+
+    def mask_statistics_raw(self, volume: Mem, mask: Mem, hist: Mem = None, hist_lo=0, bin_width=0, n_bins=0, flags=0, result=True):
+        """one clwh_mask_statistics call: (status, MaskStatsResult); nothing is raised.  result=False passes a NULL result."""
+        d, res = MaskStatsDesc(), MaskStatsResult()
+        d.volume, d.mask, d.hist = _handle(volume), _handle(mask), _handle(hist)
+        d.hist_lo, d.bin_width, d.n_bins, d.flags = int(hist_lo), int(bin_width), int(n_bins), int(flags)
+        if result:
+            d.result = C.pointer(res)
+        return lib().clwh_mask_statistics(self.h, C.byref(d)), res
+
+    def mask_statistics(self, volume: Mem, mask: Mem, hist=None):
+        """the exact record of the region of `volume` (S16) whose bits are set in `mask` (grow's layout, whoever made it): (RegionStats,
+        histogram or None, below, above).  hist = (lo, width, n): n bins of `width` values from `lo` on, as a uint64 numpy array, with
+        the counts of the region's voxels under and over the range.  scene.region_measures turns the record into volume, mean,
+        centroid and area.  The call waits for the device."""
+        table = None
+        try:
+            if hist is not None:
+                lo, width, n = (int(v) for v in hist)
+                table = self.buffer(8 * max(n, 1), np.uint64, (max(n, 1),))
+                status, res = self.mask_statistics_raw(volume, mask, table, lo, width, n)
+            else:
+                status, res = self.mask_statistics_raw(volume, mask)
+            _check(status, "clwh_mask_statistics")
+            counts = table.pull()[:int(hist[2])].copy() if table is not None else None
+            return res.stats, counts, int(res.hist_below), int(res.hist_above)
+        finally:
+            if table is not None:
+                table.release()
+
+    def label_statistics_raw(self, volume: Mem, labels: Mem, stats: Mem, capacity, flags=0):
+        """one clwh_label_statistics call: its status; nothing is raised"""
+        d = LabelStatsDesc()
+        d.volume, d.labels, d.stats = _handle(volume), _handle(labels), _handle(stats)
+        d.capacity, d.flags = int(capacity), int(flags)
+        return lib().clwh_label_statistics(self.h, C.byref(d))
+
+    def label_statistics(self, volume: Mem, labels: Mem, capacity, stats: Mem = None) -> Mem:
+        """one record per rank 1 .. capacity of `labels` (uint32 [z][y][x]: clwh_segment_label's, or any words) over `volume`: the
+        device table of `capacity` records, allocated when none is given; stats.pull() is a structured array (REGION_STATS_DTYPE),
+        record k for rank k + 1, zero for a rank no voxel has.  Ordered on the context's stream; does not wait."""
+        own = stats is None
+        if own:
+            stats = self.buffer(104 * max(int(capacity), 1), REGION_STATS_DTYPE, (max(int(capacity), 1),))
+        status = self.label_statistics_raw(volume, labels, stats, capacity)
+        if status != OK and own:
+            stats.release()
+        _check(status, "clwh_label_statistics")
+        return stats
 
     def scene_info(self):
         """(id, bytes, holders) of the derived scene data this context renders from"""

@@ -745,6 +745,86 @@ typedef struct clwh_mask_combine_desc {
 } clwh_mask_combine_desc;
 int clwh_mask_combine(clwh_ctx *ctx, const clwh_mask_combine_desc *desc);
 
+/* ---- measuring a region (not in the reference): once a mask has been grown, dilated, closed, intersected or selected from a
+ * labelling, "how many voxels is this now, what is its mean density, where is it, how large is its surface" -- on the device, as exact
+ * integers.  A region is a set R of voxels of the volume V[z][y][x] (an S16 3-D image with one channel; the dims come from it).  The
+ * record of R, every field an exact integer:
+ *   count, sum (of V over R), sum_sq (of V * V), vmin, vmax (0 when count == 0);
+ *   sum_pos[c] = the sum of p.c over R, the centroid's numerators (voxel centres are at p + 0.5);
+ *   bbox_lo, bbox_hi (hi exclusive; all zero when count == 0);
+ *   faces[c] = the number of pairs (p, p + e_c), both inside the volume, of which exactly one is in R;
+ *   border_faces[c] = #{p in R : p.c == 0} + #{p in R : p.c == dim_c - 1}, so a voxel with dim_c == 1 counts twice.
+ * The empty region has the all-zero record.  faces and border_faces are kept apart for the reason clwh_mask_morph gives: the outside of
+ * the volume is not clear, so whether the face a scan box cuts through a structure counts as surface is the caller's choice.  The face
+ * area over-estimates a smooth surface (by about 1.5 times for a sphere: it measures the staircase); clwh_mesh_isosurface is the other
+ * measure.
+ * Limits.  Those of clwh_labels_to_mask: no dim of 0, dims within the projections' rule, X * Y * Z <= 2^31 - 1.  Under them every
+ * field fits: count < 2^31, |sum| <= 2^15 * count < 2^46, sum_sq <= 2^30 * count < 2^61, sum_pos[c] <= (dim_c - 1) * count
+ * < 2^47 while no dim exceeds 2^16 (and below 2^62 for any dims the limits allow), faces[c] < X * Y * Z < 2^31, border_faces[c] <=
+ * 2 * count < 2^32. */
+typedef struct clwh_region_stats {   /* 104 bytes */
+  uint64_t count;
+  int64_t sum;                       /* of V over the region */
+  uint64_t sum_sq;                   /* of V * V */
+  int32_t vmin, vmax;                /* 0 when count == 0 */
+  uint64_t sum_pos[3];               /* of p.x, p.y, p.z */
+  uint32_t bbox_lo[3], bbox_hi[3];   /* hi exclusive; all zero when count == 0 */
+  uint32_t faces[3];
+  uint32_t border_faces[3];
+} clwh_region_stats;
+
+/* clwh_mask_statistics: the record of R = the set bits of `mask` (clwh_segment_grow's mask layout; read only; bits at x >= X and the
+ * padding words are ignored whatever they hold), and optionally the histogram of V over R: `hist`, a plain device buffer, 8-byte
+ * aligned, of uint64[n_bins]; bin b counts the region's voxels with hist_lo + b * bin_width <= V < hist_lo + (b + 1) * bin_width
+ * (in 64-bit arithmetic), -32768 <= hist_lo <= 32767, bin_width >= 1, 1 <= n_bins <= 65536; all n_bins words are written and nothing
+ * behind them; result->hist_below and hist_above count the region's voxels under and over the range (both 0 without `hist`), so that
+ * sum(hist) + hist_below + hist_above == count.  Without `hist`, n_bins must be 0 (hist_lo and bin_width are then ignored).
+ * SYNCHRONOUS, like clwh_segment_grow: ordered on the context's stream, returns with *result (HOST, required) and hist written.  The
+ * volume is read directly; no derived data is built or invalidated.  One pass over mask and volume; the scratch (one record) is kept
+ * with the context.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a NULL or wrong-kind volume; a mask that
+ * breaks grow's rules (NULL, an image, not 8-byte aligned); flags other than 0; a hist that is an image or not 8-byte aligned; with a
+ * hist, n_bins outside 1 .. 65536, bin_width < 1 or hist_lo outside [-32768, 32767]; without one, n_bins != 0; dims that break the
+ * limits.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than its layout, a hist smaller than 8 * n_bins bytes.  CLWH_ERR_OUT_OF_MEMORY:
+ * scratch that cannot be allocated.  Nothing is written on any of these. */
+typedef struct clwh_mask_stats_result {
+  clwh_region_stats stats;
+  uint64_t hist_below, hist_above;
+} clwh_mask_stats_result;
+typedef struct clwh_mask_stats_desc {
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  clwh_mem *mask;             /* plain device buffer in the mask layout; read only */
+  clwh_mem *hist;             /* optional plain device buffer of uint64[n_bins] */
+  int32_t hist_lo;            /* -32768 .. 32767 */
+  int32_t bin_width;          /* >= 1 */
+  int32_t n_bins;             /* 1 .. 65536; 0 without hist */
+  int32_t flags;              /* 0 */
+  clwh_mask_stats_result *result;  /* host; required */
+} clwh_mask_stats_desc;
+int clwh_mask_statistics(clwh_ctx *ctx, const clwh_mask_stats_desc *desc);
+
+/* clwh_label_statistics: one record per rank.  `labels`: uint32 [z][y][x], a plain device buffer, 4-byte aligned, of at least
+ * 4 * X * Y * Z bytes: what clwh_segment_label wrote, or ANY words the caller made.  `stats`: a plain device buffer, 8-byte aligned, of
+ * clwh_region_stats[capacity], 1 <= capacity <= 2^24.  Record k is the record of R_k = { p : labels(p) == k + 1 }; ALL capacity records
+ * are written, absent ranks get the all-zero record, and nothing behind them is touched.  Label 0 and labels above capacity belong to
+ * no region; for the faces of their neighbours they still count as "not in R_k".  Nothing assumes that a region is connected or that
+ * different ranks do not touch: a face between ranks a != b counts for both.  "Which of these 40 pieces is calcified, and where is
+ * each" is this call after clwh_segment_label.
+ * Asynchronous and ordered on the context's stream, like clwh_labels_to_mask; no host result, no scratch.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a NULL or wrong-kind volume; NULL labels, labels
+ * that are an image or not 4-byte aligned; NULL stats, stats that are an image or not 8-byte aligned; capacity outside 1 .. 2^24; flags
+ * other than 0; dims that break the limits.  CLWH_ERR_SIZE_MISMATCH: labels smaller than 4 * X * Y * Z bytes, stats smaller than
+ * 104 * capacity bytes.  Nothing is written on any of these. */
+typedef struct clwh_label_stats_desc {
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  clwh_mem *labels;           /* plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *stats;            /* plain device buffer of clwh_region_stats[capacity] */
+  uint64_t capacity;          /* 1 .. 2^24 */
+  int32_t flags;              /* 0 */
+  int32_t reserved;           /* ignored */
+} clwh_label_stats_desc;
+int clwh_label_statistics(clwh_ctx *ctx, const clwh_label_stats_desc *desc);
+
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
  * per layer.  `sdf` is an S8 3-D image of the volume's dims.  n_launches (optional) receives the
