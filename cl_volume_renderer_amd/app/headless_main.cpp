@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -28,6 +28,11 @@
 // min, max, sum_pos, bbox, faces, border_faces) of the mask that is applied, after any morphology and before the volume is changed:
 // {"measure": {...}}; for --components {"measure_components": [...]}, the records (renderer::measure_labels) of the selected ranks,
 // rank 1 first, at most 256 of them, and with a morphology item also "measure": the record of the morphed mask.
+// show[=fill|outline|both] (default both), an item of --grow and of --components: the volume is NOT rewritten; the region is drawn over
+// every frame of the chosen view instead (renderer::overlay_slice with --slice's plane, renderer::overlay_camera with the camera of
+// --projection, --composite and --isosurface): half-transparent colour, an outline, or both.  --components colours every selected
+// component by its rank (with a morphology item: the morphed mask, in one colour).  The JSON lines say "mode": "show" and
+// "overlay": "fill" | "outline" | "both".  show excludes keep, remove and fill=, and needs one of those four views.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -67,6 +72,16 @@ int main(int argc_in, char const *argv_in[]) {
   int morph_op = -1;  // clwh_morph_op of the dilate= | erode= | open= | close= item, or -1
   float morph_radius = 0.0f;
   bool measure = false;  // the measure item
+  int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
+  bool rewrites = false; // a keep, remove or fill= item
+  // whether `v` is the show item; *ok is cleared if its style is unknown
+  const auto show_item = [&](const std::string &v, bool *ok) {
+    if (v != "show" && v.rfind("show=", 0) != 0) return false;
+    const std::string style = v == "show" ? "both" : v.substr(5);
+    show = style == "fill" ? CLWH_OVERLAY_FILL : style == "outline" ? CLWH_OVERLAY_OUTLINE : CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE;
+    *ok = *ok && (style == "fill" || style == "outline" || style == "both");
+    return true;
+  };
   // whether `v` is that item; *ok is cleared if its radius is not a number >= 0
   const auto morph_item = [&](const std::string &v, bool *ok) {
     static const char *const names[4] = {"dilate=", "erode=", "open=", "close="};
@@ -82,8 +97,8 @@ int main(int argc_in, char const *argv_in[]) {
     }
     return false;
   };
-  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V])";
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -169,9 +184,12 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (morph_item(v, &ok)) {
         } else if (v == "measure") {
           measure = true;
+        } else if (show_item(v, &ok)) {
         } else if (v == "keep" || v == "remove") {
           grow_remove = v == "remove";
+          rewrites = true;
         } else if (v.rfind("fill=", 0) == 0) {
+          rewrites = true;
           const long n = std::strtol(v.c_str() + 5, &end, 10);
           ok = ok && v.size() > 5 && *end == '\0' && n >= -32768 && n <= 32767;
           grow_fill = (int)n;
@@ -179,7 +197,7 @@ int main(int argc_in, char const *argv_in[]) {
           ok = false;
         }
       }
-      if (!ok || field < 5 || grow_lo > grow_hi) {
+      if (!ok || field < 5 || grow_lo > grow_hi || (show >= 0 && rewrites)) {
         std::cout << "Unknown option '" << a << "' " << kGrowUsage << "\n";
         return 1;
       }
@@ -206,9 +224,12 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (morph_item(v, &ok)) {
         } else if (v == "measure") {
           measure = true;
+        } else if (show_item(v, &ok)) {
         } else if (v == "keep" || v == "remove") {
           comps_remove = v == "remove";
+          rewrites = true;
         } else if (v.rfind("fill=", 0) == 0) {
+          rewrites = true;
           const long n = std::strtol(v.c_str() + 5, &end, 10);
           ok = ok && v.size() > 5 && *end == '\0' && n >= -32768 && n <= 32767;
           comps_fill = (int)n;
@@ -222,7 +243,7 @@ int main(int argc_in, char const *argv_in[]) {
           ok = false;
         }
       }
-      if (!ok || field < 2 || comps_lo > comps_hi || (comps_largest >= 0 && comps_min >= 0)) {
+      if (!ok || field < 2 || comps_lo > comps_hi || (comps_largest >= 0 && comps_min >= 0) || (show >= 0 && rewrites)) {
         std::cout << "Unknown option '" << a << "' " << kCompsUsage << "\n";
         return 1;
       }
@@ -269,6 +290,10 @@ int main(int argc_in, char const *argv_in[]) {
     std::cout << "--grow and --components exclude each other\n";
     return 1;
   }
+  if (show >= 0 && projection < 0 && composite < 0 && !isosurface && slice < 0) {
+    std::cout << "show needs --projection, --composite, --isosurface or --slice " << (grow ? kGrowUsage : kCompsUsage) << "\n";
+    return 1;
+  }
   if (mesh && (projection >= 0 || composite >= 0 || isosurface || slice >= 0)) {
     std::cout << "--mesh excludes --projection, --composite, --isosurface and --slice\n";
     return 1;
@@ -288,7 +313,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -317,6 +342,11 @@ int main(int argc_in, char const *argv_in[]) {
   env_map emap(ctx, em);
   emitter->image_set(&rv, &emap);
 
+  int show_source = renderer::OVERLAY_REGION_MASK;  // what the show item draws
+  renderer::overlay_style show_style;
+  if (show >= 0) show_style.flags = show;
+  static const char *const kShowNames[4] = {"", "fill", "outline", "both"};
+
   if (grow) {  // first: everything below sees the masked volume
     const auto &size = rv.get_volume_size();
     for (int q = 0; q < 3; ++q)
@@ -330,10 +360,10 @@ int main(int argc_in, char const *argv_in[]) {
     if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
     clwh_mask_stats_result measured{};
     if (measure) measured = r.measure_mask(none);  // of the volume as loaded: before the mask changes it
-    r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
+    if (show < 0) r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
-                grow_seed[0], grow_seed[1], grow_seed[2], grow_lo, grow_hi, (grow_flags & CLWH_GROW_26) ? 26 : 6, grow_remove ? "remove" : "keep",
+                grow_seed[0], grow_seed[1], grow_seed[2], grow_lo, grow_hi, (grow_flags & CLWH_GROW_26) ? 26 : 6, show >= 0 ? "show" : grow_remove ? "remove" : "keep",
                 grow_fill, (unsigned long long)g.count, g.bbox_lo[0], g.bbox_lo[1], g.bbox_lo[2], g.bbox_hi[0], g.bbox_hi[1], g.bbox_hi[2],
                 g.count ? (double)g.sum / (double)g.count : 0.0, g.vmin, g.vmax);
     if (morph_op >= 0)
@@ -370,10 +400,14 @@ int main(int argc_in, char const *argv_in[]) {
     clwh_mask_stats_result measured_mask{};
     if (measure && keep > 0) measured = r.measure_labels(none, (unsigned)std::min<uint64_t>(keep, 256));  // before the mask changes the volume
     if (measure && morph_op >= 0) measured_mask = r.measure_mask(none);  // the morphed mask is no longer the union of the ranks
-    r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
+    if (show < 0) r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
+    if (show >= 0 && morph_op < 0 && keep > 0) {  // the labelling itself: a colour per rank (else the mask, which may be empty or morphed)
+      show_source = renderer::OVERLAY_LABELS;
+      show_style.id_hi = (uint32_t)keep;
+    }
     std::printf("{\"components\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"n_components\": %llu, \"n_voxels\": %llu, "
                 "\"selected\": [%u, %llu], \"largest\": [",
-                comps_lo, comps_hi, (comps_flags & CLWH_LABEL_26) ? 26 : 6, comps_remove ? "remove" : "keep", comps_fill,
+                comps_lo, comps_hi, (comps_flags & CLWH_LABEL_26) ? 26 : 6, show >= 0 ? "show" : comps_remove ? "remove" : "keep", comps_fill,
                 (unsigned long long)c.n_components, (unsigned long long)c.n_voxels, keep > 0 ? 1u : 0u, (unsigned long long)keep);
     for (size_t k = 0; k < c.top.size(); ++k) {
       const clwh_label_component &t = c.top[k];
@@ -449,6 +483,10 @@ int main(int argc_in, char const *argv_in[]) {
       frame = static_cast<const unsigned char *>(r.render_projection(state, projection, 0.0f, 4000.0f));
     else
       frame = static_cast<const unsigned char *>(emitter->render_frame(state, changed));
+    if (show >= 0 && slice >= 0)
+      frame = static_cast<const unsigned char *>(r.overlay_slice(state, show_source, slice, slice_position, slice_slab, 0.5f, show_style));
+    else if (show >= 0)
+      frame = static_cast<const unsigned char *>(r.overlay_camera(state, show_source, 0.5f, show_style));
   }
   const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
@@ -466,13 +504,14 @@ int main(int argc_in, char const *argv_in[]) {
   }
   static const char *const kProjectionNames[] = {"max", "min", "mean"};
   static const char *const kSliceNames[] = {"axial", "coronal", "sagittal"};
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s%s}\n",
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s%s%s%s%s}\n",
               frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
               projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "",
               composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "",
               isosurface ? (", \"isosurface\": " + std::to_string(iso_value) + ", \"below\": " + (iso_below ? "true" : "false")).c_str() : "",
               slice >= 0 ? (std::string(", \"slice\": \"") + kSliceNames[slice] + "\", \"position\": " + std::to_string(slice_position) +
-                            ", \"slab\": " + std::to_string(slice_slab) + ", \"mode\": \"" + kProjectionNames[slice_mode] + "\"").c_str() : "");
+                            ", \"slab\": " + std::to_string(slice_slab) + ", \"mode\": \"" + kProjectionNames[slice_mode] + "\"").c_str() : "",
+              show >= 0 ? ", \"overlay\": \"" : "", show >= 0 ? kShowNames[show] : "", show >= 0 ? "\"" : "");
   for (tf_selection *s : selection) delete s;
   return 0;
 }

@@ -184,6 +184,36 @@ void clvr_host_measure_labels(clvr_host *h, unsigned capacity, void *out) {
   const std::vector<clwh_region_stats> table = h->rend.measure_labels(h->state, capacity);
   std::memcpy(out, table.data(), table.size() * sizeof(clwh_region_stats));
 }
+// renderer::overlay_slice over the frame clvr_host_render_slice wrote, with the same region and plane: source 0 the region mask, 1 the
+// held mask, 2 the last labelling; the RGBA8 frame (SCREEN_WIDTH x SCREEN_HEIGHT)
+const void *clvr_host_overlay_slice(clvr_host *h, int width, int height, int source, int orientation, float position, int slab_samples,
+                                    float step, int flags, unsigned fill_alpha, unsigned outline_alpha, unsigned id_lo, unsigned id_hi) {
+  h->state.width = width;
+  h->state.height = height;
+  renderer::overlay_style style;
+  style.flags = flags;
+  style.fill_alpha = fill_alpha;
+  style.outline_alpha = outline_alpha;
+  style.id_lo = id_lo;
+  style.id_hi = id_hi;
+  return h->rend.overlay_slice(h->state, source, orientation, position, slab_samples, step, style);
+}
+// renderer::overlay_camera over the frame a camera view wrote, from the same camera arguments as clvr_host_render_projection
+const void *clvr_host_overlay_camera(clvr_host *h, const float pos[3], const float look[2], int width, int height, int source, float step,
+                                     int flags, unsigned fill_alpha, unsigned outline_alpha, unsigned id_lo, unsigned id_hi) {
+  h->state.position = Position3D(pos[0], pos[1], pos[2]);
+  h->state.direction_look[0] = look[0];
+  h->state.direction_look[1] = look[1];
+  h->state.width = width;
+  h->state.height = height;
+  renderer::overlay_style style;
+  style.flags = flags;
+  style.fill_alpha = fill_alpha;
+  style.outline_alpha = outline_alpha;
+  style.id_lo = id_lo;
+  style.id_hi = id_hi;
+  return h->rend.overlay_camera(h->state, source, step, style);
+}
 // tf_composite_lut for a list of rectangles {min_v, max_v, min_g, max_g, r, g, b, a} into out[lut_len][4] (no device involved)
 void clvr_host_tf_composite_lut(const float *rects, int n, int lut_first, int lut_len, float opacity, float *out) {
   std::vector<tf_selection *> sel;

@@ -26,6 +26,7 @@ renderer::renderer(clw_context &c)
       region_mask(ctx, std::vector<uint32_t>(2)),
       held_mask(ctx, std::vector<uint32_t>(2)),
       region_labels(ctx, std::vector<uint32_t>(1)),
+      overlay_palette(ctx, std::vector<uint32_t>(overlay_colours()), true),
       sdf(ctx) {}
 
 void renderer::image_set(const reference_volume *rv, const env_map *map) {
@@ -205,6 +206,75 @@ void *renderer::render_slice(struct ui_state &state, int orientation, float posi
   d.window_center = center;
   d.window_width = width;
   clw_fail_hard_on_error(clwh_render_slice(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
+const std::vector<uint32_t> &renderer::overlay_colours() {
+  static const uint8_t rgb[20][3] = {{230, 25, 75},   {60, 180, 75},   {255, 225, 25}, {0, 130, 200},   {245, 130, 48},
+                                     {145, 30, 180},  {70, 240, 240},  {240, 50, 230}, {210, 245, 60},  {255, 140, 170},
+                                     {0, 128, 128},   {220, 190, 255}, {170, 110, 40}, {255, 250, 200}, {128, 0, 0},
+                                     {170, 255, 195}, {128, 128, 0},   {200, 160, 120}, {0, 0, 128},    {128, 128, 128}};
+  static const std::vector<uint32_t> words = [] {
+    std::vector<uint32_t> w;
+    for (const auto &c : rgb) w.push_back((uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | 255u << 24);
+    return w;
+  }();
+  return words;
+}
+
+// what the two overlay descriptors share: the frame and the launched region, the chosen region buffer, the palette and the style
+template <class Desc>
+void renderer::fill_overlay(Desc &d, const struct ui_state &state, int source, const overlay_style &style) {
+  const auto &size = volume->get_volume_size();
+  const size_t mask_words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];
+  const clw_vector<uint32_t> *buffer = nullptr;
+  if (source == OVERLAY_REGION_MASK && region_mask.size() == mask_words) buffer = &region_mask;
+  if (source == OVERLAY_HELD_MASK && held_mask.size() == mask_words) buffer = &held_mask;
+  if (source == OVERLAY_LABELS && region_labels.size() == (size_t)size[0] * size[1] * size[2]) buffer = &region_labels;
+  if (!buffer) clw_fail_hard_on_error(source < OVERLAY_REGION_MASK || source > OVERLAY_LABELS ? CLWH_ERR_INVALID_VALUE : CLWH_ERR_SIZE_MISMATCH);  // nothing grown, held or labelled
+  d.frame = frame.get_device_reference();
+  d.width = (uint32_t)state.width;
+  d.height = (uint32_t)state.height;
+  d.region.buffer = buffer->get_device_reference();
+  d.region.kind = source == OVERLAY_LABELS ? CLWH_REGION_LABELS : CLWH_REGION_MASK;
+  for (int q = 0; q < 3; ++q) d.region.dims[q] = (uint32_t)size[q];
+  d.region.id_lo = style.id_lo;
+  d.region.id_hi = style.id_hi;
+  d.paint.palette = overlay_palette.get_device_reference();
+  d.paint.n_colours = (uint32_t)overlay_palette.size();
+  d.paint.flags = style.flags;
+  d.paint.fill_alpha = style.fill_alpha;
+  d.paint.outline_alpha = style.outline_alpha;
+}
+
+void *renderer::overlay_slice(struct ui_state &state, int source, int orientation, float position, int slab_samples, float step,
+                              const overlay_style &style) {
+  if (orientation < SLICE_AXIAL || orientation > SLICE_SAGITTAL || state.width < 1 || state.height < 1) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  clwh_overlay_slice_desc d{};
+  fill_overlay(d, state, source, style);
+  const auto &size = volume->get_volume_size();
+  const size_t dims[3] = {size[0], size[1], size[2]};
+  slice_plane(dims, orientation, position, state.width, state.height, slab_samples, step, d.origin, d.du, d.dv, d.normal);
+  d.slab_samples = slab_samples;
+  d.step = step;
+  clw_fail_hard_on_error(clwh_overlay_slice(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
+void *renderer::overlay_camera(struct ui_state &state, int source, float step, const overlay_style &style) {
+  clwh_overlay_camera_desc d{};
+  fill_overlay(d, state, source, style);
+  Position3D vec(state.direction_look[0], state.direction_look[1], 0.0, {1.0, 0.0, 0.0});
+  for (int q = 0; q < 3; ++q) {
+    d.cam_pos[q] = (float)state.position.val[q];
+    d.cam_dir[q] = (float)vec.val[q];
+  }
+  d.step = step;
+  d.t_near = 0.0f;
+  d.t_far = INFINITY;
+  clw_fail_hard_on_error(clwh_overlay_camera(ctx.get_handle(), &d));
   frame.pull();
   return &frame[0];
 }

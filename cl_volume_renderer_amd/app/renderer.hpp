@@ -24,6 +24,13 @@ struct mesh_data {
 // not be written
 bool write_ply(const std::string &path, const mesh_data &mesh);
 
+// how renderer::overlay_slice and overlay_camera draw a region
+struct overlay_style {
+  int flags = CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE;  // | CLWH_OVERLAY_DENSE
+  uint32_t fill_alpha = 96, outline_alpha = 255;
+  uint32_t id_lo = 1, id_hi = 0xFFFFFFFFu;  // the ranks drawn
+};
+
 class renderer : public frame_emitter {
  public:
   explicit renderer(clw_context &ctx);
@@ -138,6 +145,21 @@ class renderer : public frame_emitter {
                                       std::vector<uint64_t> *hist = nullptr);
   std::vector<clwh_region_stats> measure_labels(struct ui_state &state, unsigned capacity);
 
+  // not in the reference: the region drawn over the frame the last view wrote (clwh_overlay_slice / clwh_overlay_camera): coloured,
+  // half-transparent areas with an outline, in place of rewriting the volume with apply_mask.  `source`: the region mask (grow_region,
+  // select_components, morph_mask, combine_masks), hold_mask's copy of it, or the last labelling, whose rank r gets colour
+  // overlay_colours()[(r - 1) % 20].  overlay_slice takes render_slice's orientation, position, slab and step and draws with the
+  // same plane; overlay_camera draws with the camera of `state`, the one of render_projection, render_composite, render_isosurface
+  // and the path-traced frame.  The region is seen through whatever the view shows in front of it.  Both pull the frame and return
+  // its host copy.
+  enum overlay_source { OVERLAY_REGION_MASK = 0, OVERLAY_HELD_MASK = 1, OVERLAY_LABELS = 2 };
+  typedef ::overlay_style overlay_style;
+  void *overlay_slice(struct ui_state &state, int source, int orientation, float position, int slab_samples = 1, float step = 0.5f,
+                      const overlay_style &style = overlay_style());
+  void *overlay_camera(struct ui_state &state, int source, float step = 0.5f, const overlay_style &style = overlay_style());
+  // the table of scene.overlay_palette: 20 well-separated opaque colours as packed RGBA8 words
+  static const std::vector<uint32_t> &overlay_colours();
+
   // not in the reference: read-only access for tests and headless tools
   clw_vector<unsigned short> &voxel_cache() { return buffer_volume; }
   signed_distance_field &distance_field() { return sdf; }
@@ -153,6 +175,9 @@ class renderer : public frame_emitter {
   clw_vector<uint32_t> region_mask;          // grow_region's mask on the device (never pulled: the host side only sizes it)
   clw_vector<uint32_t> held_mask;            // hold_mask's copy of region_mask (never pulled)
   clw_vector<uint32_t> region_labels;        // label_components' ranks on the device, one word per voxel (never pulled)
+  clw_vector<uint32_t> overlay_palette;      // overlay_colours() on the device, pushed once, by the constructor
+  template <class Desc>
+  void fill_overlay(Desc &d, const struct ui_state &state, int source, const overlay_style &style);
   const reference_volume *volume = nullptr;  // borrowed
   const env_map *emap = nullptr;             // borrowed
   signed_distance_field sdf;

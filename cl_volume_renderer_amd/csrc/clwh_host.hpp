@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces and slices; clwh_mesh.hip: the
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
 // clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
@@ -243,6 +243,12 @@ struct RegionStatsScratch {
   DeviceBuffer result;
 };
 
+// clwh_overlay_slice's and clwh_overlay_camera's scratch: {ID, K} per pixel of the region and its one-pixel halo, and the occupancy words of
+// the region's bricks and cells.  Every call rewrites what it reads: only the allocations are kept.
+struct OverlayScratch {
+  DeviceBuffer pixel_ids, occupancy;
+};
+
 // intensity projections and compositing: the volume in brick order + the per-brick {min, max} table (one allocation, per context,
 // shared by clwh_render_projection and clwh_render_composite), and the key of the content it was built from (device pointer, shared
 // content version, dims).  Beside it the derived data of compositing's colour/opacity table: the prefix count of entries with
@@ -298,6 +304,7 @@ struct clwh_ctx {
   clvr::LabelScratch label;
   clvr::DistanceScratch distance;
   clvr::RegionStatsScratch region_stats;
+  clvr::OverlayScratch overlay;
   clvr::ProjectionData proj;
   clvr::DeviceBuffer bilateral_weights;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)
   // derived packed volume: hit records (8 B per voxel of the brick grid), the step bytes (1 B), the per-brick minima (4 B per

@@ -511,4 +511,32 @@ hipError_t launch_stats_finish(clwh_region_stats *stats, uint32_t n, hipStream_t
 hipError_t launch_mask_stats(const MaskStatsArgs &a, hipStream_t s);
 hipError_t launch_label_stats(const LabelStatsArgs &a, hipStream_t s);
 
+// ---- overlays of a mask or a labelling on a slice's or a camera view's frame (overlay_kernels.hip; host side clwh_views.hip).  The walk
+// needs of `vol` only the dims and the brick and cell counts; its pointers stay nullptr.
+struct OverlayArgs {
+  ViewVolume vol;
+  ViewFrame fr;
+  ViewCamera cam;              // the camera call's rays
+  float origin[3], du[3], dv[3], normal[3];  // the plane call's
+  float step;                  // of either ray kind
+  int32_t slab_samples;        // the plane call's cap of the sample indices
+  int32_t kind;                // clwh_region_kind
+  const unsigned long long *mask;  // CLWH_REGION_MASK: grow's bit rows
+  const uint32_t *labels;      // CLWH_REGION_LABELS: [z][y][x]
+  int32_t W64;
+  uint32_t id_lo, id_hi;
+  const uint32_t *occ_bricks, *occ_cells;  // 1: holds a nonzero filtered id; nullptr when the walk is dense (always for the plane)
+  uint2 *pixel_ids;            // scratch: {ID, K} per pixel of the padded grid (launch_w + 2) x (launch_h + 2), pixel (-1, -1) first
+  const uint32_t *palette;     // n_colours packed RGBA8 words
+  uint32_t n_colours;
+  int32_t flags;               // clwh_overlay_flags
+  uint32_t fill_alpha, outline_alpha;
+  uint32_t *ids;               // optional, row-major launch_w x launch_h
+  float *t_first;              // optional, same
+};
+// `cells` (n_cells words) is cleared, then every word of `bricks` (NBX * NBY * NBZ) and of `cells` is written
+hipError_t launch_region_occupancy(const OverlayArgs &a, uint32_t *bricks, uint32_t *cells, size_t n_cells, hipStream_t s);
+// k_region_ids into a.pixel_ids, then k_overlay_blend
+hipError_t launch_overlay(const OverlayArgs &a, bool camera, bool skip, hipStream_t s);
+
 }  // namespace clvr

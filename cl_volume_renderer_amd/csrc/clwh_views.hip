@@ -2,6 +2,8 @@
 // (compositing through a colour/opacity table), clwh_render_isosurface (the isosurface of the trilinear field) and clwh_render_slice
 // (its oblique slices and slabs).  All read the same bricked copy of the volume (ensure_projection_data), as does the mesher
 // (clwh_mesh.hip).  The kernels are in projection_kernels.hip, composite_kernels.hip, isosurface_kernels.hip and slice_kernels.hip.
+// Behind them clwh_overlay_slice and clwh_overlay_camera, which draw a mask or a labelling over a frame one of them has written, with
+// the slice's or the projection's rays (overlay_kernels.hip); they read no volume.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -73,12 +75,12 @@ static bool view_region_ok(const clwh_mem *frame, uint32_t width, uint32_t heigh
 static bool holds(const clwh_mem *m, size_t bytes) { return !m || m->bytes >= bytes; }
 
 // distance from the camera to the farthest corner of the volume's box (infinite for an infinite camera)
-static double farthest_corner(const clwh_mem *volume, const float cam_pos[3]) {
+static double farthest_corner(const size_t dims[3], const float cam_pos[3]) {
   double far = 0.0;
   for (int c = 0; c < 8; ++c) {
     double s2 = 0.0;
     for (int q = 0; q < 3; ++q) {
-      const double corner = (c >> q) & 1 ? (double)volume->dims[q] : 0.0;
+      const double corner = (c >> q) & 1 ? (double)dims[q] : 0.0;
       s2 += (corner - (double)cam_pos[q]) * (corner - (double)cam_pos[q]);
     }
     far = std::max(far, std::sqrt(s2));
@@ -89,11 +91,11 @@ static double farthest_corner(const clwh_mem *volume, const float cam_pos[3]) {
 // far / step < 2^29 (|d| = 1 within float rounding), which bounds the kernels' 32-bit sample indices (ViewCamera::k_cap); false for an
 // infinite camera.  std::max in farthest_corner drops a NaN distance, so a NaN camera position passes that test: the compositor and
 // the isosurface refuse it by name (finite_camera), the projections accept it and find no kept sample (include/clwh.h).
-static bool view_march_ok(const clwh_mem *volume, const float cam_pos[3], float step, float t_near, float t_far, bool finite_camera) {
+static bool view_march_ok(const size_t dims[3], const float cam_pos[3], float step, float t_near, float t_far, bool finite_camera) {
   if (!(std::isfinite(step) && step > 0.0f)) return false;
   if (!(t_near <= t_far) || t_near == INFINITY) return false;  // (false for NaN)
   if (finite_camera && !(std::isfinite(cam_pos[0]) && std::isfinite(cam_pos[1]) && std::isfinite(cam_pos[2]))) return false;
-  return farthest_corner(volume, cam_pos) / (double)step < 536870912.0;
+  return farthest_corner(dims, cam_pos) / (double)step < 536870912.0;
 }
 
 static ViewFrame view_frame(const clwh_mem *frame, uint32_t width, uint32_t height) {
@@ -127,7 +129,7 @@ extern "C" int clwh_render_projection(clwh_ctx *ctx, const clwh_projection_desc 
   if (d->mode != CLWH_PROJ_MAX && d->mode != CLWH_PROJ_MIN && d->mode != CLWH_PROJ_MEAN) return CLWH_ERR_INVALID_VALUE;
   if ((d->flags & ~CLWH_PROJ_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
   if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
-  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/false)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume->dims, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/false)) return CLWH_ERR_INVALID_VALUE;
   if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
   const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
   if (!holds(d->values, out_bytes) || !holds(d->t_extreme, out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
@@ -171,7 +173,7 @@ extern "C" int clwh_render_composite(clwh_ctx *ctx, const clwh_composite_desc *d
   if (!(d->alpha_stop > 0.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN; +inf never stops early)
   const bool shade = (d->flags & CLWH_COMP_SHADE) != 0;
   if (shade && !(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;
-  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume->dims, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
   if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
   if (d->lut->bytes < (size_t)d->lut_len * 16u) return CLWH_ERR_SIZE_MISMATCH;
   const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
@@ -203,7 +205,7 @@ extern "C" int clwh_render_isosurface(clwh_ctx *ctx, const clwh_isosurface_desc 
   if (d->refine < 0 || d->refine > 24) return CLWH_ERR_INVALID_VALUE;
   if (!(d->ambient >= 0.0f && d->ambient <= 1.0f)) return CLWH_ERR_INVALID_VALUE;  // (false for NaN)
   if (!(std::isfinite(d->color[0]) && std::isfinite(d->color[1]) && std::isfinite(d->color[2]))) return CLWH_ERR_INVALID_VALUE;
-  if (!view_march_ok(d->volume, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_march_ok(d->volume->dims, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
   if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
   const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
   if (!holds(d->t_hit, out_bytes) || !holds(d->normal, 4u * out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
@@ -270,4 +272,114 @@ extern "C" int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *d) {
   a.t_extreme = optional_output<float>(d->t_extreme);
   HIP_TRY(launch_slice(a, d->mode, dense, ctx->stream));
   return CLWH_OK;
+}
+
+// ---- overlays of a mask or a labelling on a frame one of the views above has written (overlay_kernels.hip)
+static_assert(sizeof(clwh_overlay_region) == 32 && sizeof(clwh_overlay_paint) == 40 && sizeof(clwh_overlay_slice_desc) == 144 &&
+                  sizeof(clwh_overlay_camera_desc) == 128, "the overlay descriptors' layout (ffi.py states it again)");
+
+// (value) what both overlay calls demand of the frame, the region and the paint
+static bool overlay_values_ok(const clwh_mem *frame, const clwh_overlay_region &r, const clwh_overlay_paint &p) {
+  if (!is_image(frame, 2, 4, CLWH_ELEM_U8)) return false;
+  if (r.kind != CLWH_REGION_MASK && r.kind != CLWH_REGION_LABELS) return false;
+  if (!is_plain_buffer(r.buffer) || ((uintptr_t)r.buffer->dptr & (r.kind == CLWH_REGION_MASK ? 7u : 3u)) != 0u) return false;
+  if (!is_plain_buffer(p.palette) || ((uintptr_t)p.palette->dptr & 3u) != 0u) return false;
+  if ((p.ids && !is_plain_buffer(p.ids)) || (p.t_first && !is_plain_buffer(p.t_first))) return false;
+  if ((p.flags & ~(CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE | CLWH_OVERLAY_DENSE)) != 0) return false;
+  if (r.id_lo == 0u || r.id_lo > r.id_hi) return false;
+  if (p.n_colours < 1u || p.n_colours > 65536u || p.fill_alpha > 255u || p.outline_alpha > 255u) return false;
+  // clwh_labels_to_mask's limits: X * Y * Z <= 2^31 - 1, by division (the product may not fit)
+  const uint64_t X = r.dims[0], Y = r.dims[1], Z = r.dims[2];
+  if (X == 0 || Y == 0 || Z == 0 || X > 0x7FFFFFFFu || Y > 0x7FFFFFFFu || Z > 0x7FFFFFFFu) return false;
+  return X * Y <= 0x7FFFFFFFull && Z <= 0x7FFFFFFFull / (X * Y);
+}
+// (size) the region's buffer holds its layout, the palette its colours, the outputs the launched region
+static bool overlay_sizes_ok(const clwh_overlay_region &r, const clwh_overlay_paint &p, uint32_t width, uint32_t height) {
+  const uint64_t X = r.dims[0], Y = r.dims[1], Z = r.dims[2];
+  if (r.kind == CLWH_REGION_MASK ? r.buffer->bytes / (((X + 63u) / 64u) * 8u) < Y * Z : r.buffer->bytes / 4u < X * Y * Z) return false;
+  if (p.palette->bytes < (size_t)p.n_colours * 4u) return false;
+  const size_t out_bytes = (size_t)width * height * 4u;
+  return holds(p.ids, out_bytes) && holds(p.t_first, out_bytes);
+}
+
+// what the two calls share once their checks have passed: a.cam or the plane and a.step are set
+static int overlay_run(clwh_ctx *ctx, OverlayArgs &a, const clwh_mem *frame, const clwh_overlay_region &r, const clwh_overlay_paint &p,
+                       uint32_t width, uint32_t height, bool camera) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  ViewVolume &v = a.vol;
+  v.X = (int32_t)r.dims[0]; v.Y = (int32_t)r.dims[1]; v.Z = (int32_t)r.dims[2];
+  v.NBX = (v.X + 7) / 8; v.NBY = (v.Y + 7) / 8; v.NBZ = (v.Z + 7) / 8;
+  v.CNX = (v.NBX + 3) / 4; v.CNY = (v.NBY + 3) / 4;
+  a.fr = view_frame(frame, width, height);
+  a.kind = r.kind;
+  if (r.kind == CLWH_REGION_MASK) a.mask = (const unsigned long long *)r.buffer->dptr;
+  else a.labels = (const uint32_t *)r.buffer->dptr;
+  a.W64 = (v.X + 63) / 64;
+  a.id_lo = r.id_lo;
+  a.id_hi = r.id_hi;
+  a.palette = (const uint32_t *)p.palette->dptr;
+  a.n_colours = p.n_colours;
+  a.flags = p.flags;
+  a.fill_alpha = p.fill_alpha;
+  a.outline_alpha = p.outline_alpha;
+  a.ids = optional_output<uint32_t>(p.ids);
+  a.t_first = optional_output<float>(p.t_first);
+  OverlayScratch &s = ctx->overlay;
+  CLWH_TRY(s.pixel_ids.reserve(ctx->stream, ((size_t)width + 2u) * ((size_t)height + 2u) * sizeof(uint2)));
+  a.pixel_ids = s.pixel_ids.as<uint2>();
+  // the camera's rays step over empty bricks; the plane's walk densely: a slab is short, and the table, which has to be built per call
+  // (a caller's buffer has no content version), cost more than it saved in every slab timed
+  const bool skip = camera && (p.flags & CLWH_OVERLAY_DENSE) == 0;
+  if (skip) {
+    const size_t n_bricks = (size_t)v.NBX * v.NBY * v.NBZ, n_cells = (size_t)v.CNX * v.CNY * ((v.NBZ + 3) / 4);
+    CLWH_TRY(s.occupancy.reserve(ctx->stream, (n_bricks + n_cells) * sizeof(uint32_t)));
+    uint32_t *bricks = s.occupancy.as<uint32_t>();
+    HIP_TRY(launch_region_occupancy(a, bricks, bricks + n_bricks, n_cells, ctx->stream));
+    a.occ_bricks = bricks;
+    a.occ_cells = bricks + n_bricks;
+  }
+  HIP_TRY(launch_overlay(a, camera, skip, ctx->stream));
+  return CLWH_OK;
+}
+
+extern "C" int clwh_overlay_slice(clwh_ctx *ctx, const clwh_overlay_slice_desc *d) {
+  if (!ctx || !d || !overlay_values_ok(d->frame, d->region, d->paint)) return CLWH_ERR_INVALID_VALUE;
+  if (d->slab_samples < 1 || d->slab_samples > 8192) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  for (int q = 0; q < 3; ++q) {
+    if (!(std::isfinite(d->origin[q]) && std::isfinite(d->du[q]) && std::isfinite(d->dv[q]) && std::isfinite(d->normal[q]))) return CLWH_ERR_INVALID_VALUE;
+    // clwh_render_slice's reach with the halo's pixels -1, width and height: below 2^30 every coordinate converts to int32
+    const double reach = std::fabs((double)d->origin[q]) + (double)d->width * std::fabs((double)d->du[q]) +
+                         (double)d->height * std::fabs((double)d->dv[q]) +
+                         (double)(d->slab_samples - 1) * (double)d->step * std::fabs((double)d->normal[q]);
+    if (!(reach < 1073741824.0)) return CLWH_ERR_INVALID_VALUE;
+  }
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (!overlay_sizes_ok(d->region, d->paint, d->width, d->height)) return CLWH_ERR_SIZE_MISMATCH;
+
+  OverlayArgs a;
+  std::memset(&a, 0, sizeof a);
+  for (int q = 0; q < 3; ++q) {
+    a.origin[q] = d->origin[q];
+    a.du[q] = d->du[q];
+    a.dv[q] = d->dv[q];
+    a.normal[q] = d->normal[q];
+  }
+  a.step = d->step;
+  a.slab_samples = d->slab_samples;
+  return overlay_run(ctx, a, d->frame, d->region, d->paint, d->width, d->height, /*camera=*/false);
+}
+
+extern "C" int clwh_overlay_camera(clwh_ctx *ctx, const clwh_overlay_camera_desc *d) {
+  if (!ctx || !d || !overlay_values_ok(d->frame, d->region, d->paint)) return CLWH_ERR_INVALID_VALUE;
+  const size_t dims[3] = {d->region.dims[0], d->region.dims[1], d->region.dims[2]};
+  if (!view_march_ok(dims, d->cam_pos, d->step, d->t_near, d->t_far, /*finite_camera=*/true)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  if (!overlay_sizes_ok(d->region, d->paint, d->width, d->height)) return CLWH_ERR_SIZE_MISMATCH;
+
+  OverlayArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.cam = view_camera(d->cam_pos, d->cam_dir, d->step, d->t_near, d->t_far);
+  a.step = d->step;
+  return overlay_run(ctx, a, d->frame, d->region, d->paint, d->width, d->height, /*camera=*/true);
 }

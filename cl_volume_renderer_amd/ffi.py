@@ -33,6 +33,8 @@ DIST_TO_CLEAR = 1
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
+REGION_MASK, REGION_LABELS = 0, 1
+OVERLAY_FILL, OVERLAY_OUTLINE, OVERLAY_DENSE = 1, 2, 4
 SHADE_LIGHT, SHADE_AO = 0, 1
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
@@ -273,6 +275,33 @@ class LabelStatsDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class OverlayRegion(C.Structure):
+    _fields_ = [("buffer", C.c_void_p), ("kind", C.c_int32), ("dims", C.c_uint32 * 3), ("id_lo", C.c_uint32), ("id_hi", C.c_uint32)]
+
+
+class OverlayPaint(C.Structure):
+    _fields_ = [("palette", C.c_void_p), ("n_colours", C.c_uint32), ("flags", C.c_int32), ("fill_alpha", C.c_uint32),
+                ("outline_alpha", C.c_uint32), ("ids", C.c_void_p), ("t_first", C.c_void_p)]
+
+
+class OverlaySliceDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("region", OverlayRegion), ("paint", OverlayPaint),
+        ("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("normal", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("slab_samples", C.c_int32), ("step", C.c_float),
+    ]
+
+
+class OverlayCameraDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("region", OverlayRegion), ("paint", OverlayPaint),
+        ("cam_pos", C.c_float * 3), ("cam_dir", C.c_float * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("step", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/clwh.h declares: (name, restype, argtypes)
 _SIZE3 = C.POINTER(C.c_size_t)
 _PROTOTYPES = [
@@ -321,6 +350,8 @@ _PROTOTYPES = [
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
     ("clwh_mask_statistics", C.c_int, [C.c_void_p, C.POINTER(MaskStatsDesc)]),
     ("clwh_label_statistics", C.c_int, [C.c_void_p, C.POINTER(LabelStatsDesc)]),
+    ("clwh_overlay_slice", C.c_int, [C.c_void_p, C.POINTER(OverlaySliceDesc)]),
+    ("clwh_overlay_camera", C.c_int, [C.c_void_p, C.POINTER(OverlayCameraDesc)]),
     ("clwh_sdf_build", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_buffer_reset", C.c_int, [C.c_void_p, C.c_void_p]),
     ("clwh_cache_exchange_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -394,6 +425,20 @@ def accum_len(w, h, world=1) -> int:
 def _handle(mem):
     """the handle of an optional Mem"""
     return mem.h if mem is not None else None
+
+
+def _fill_overlay(d, frame, source, kind, dims, palette, width, height, n_colours, flags, fill_alpha, outline_alpha, id_range, ids, t_first):
+    """what the two overlay descriptors share"""
+    d.frame = _handle(frame)
+    d.region.buffer, d.region.kind = _handle(source), int(kind)
+    for k in range(3):
+        d.region.dims[k] = int(dims[k])
+    d.region.id_lo, d.region.id_hi = int(id_range[0]), int(id_range[1])
+    d.paint.palette = _handle(palette)
+    d.paint.n_colours = int(n_colours if n_colours is not None else (palette.nbytes // 4 if palette is not None else 0))
+    d.paint.flags, d.paint.fill_alpha, d.paint.outline_alpha = int(flags), int(fill_alpha), int(outline_alpha)
+    d.paint.ids, d.paint.t_first = _handle(ids), _handle(t_first)
+    d.width, d.height = int(width), int(height)
 
 
 def _fill_view(d, frame, volume, cam_pos, cam_dir, width, height):
@@ -650,6 +695,39 @@ class Context:
         d.values = _handle(values)
         d.t_extreme = _handle(t_extreme)
         _check(lib().clwh_render_slice(self.h, C.byref(d)), "clwh_render_slice")
+
+    def overlay_slice_raw(self, frame: Mem, source: Mem, kind, dims, palette: Mem, origin, du, dv, normal, width, height, slab_samples=1,
+                          step=0.5, flags=OVERLAY_FILL | OVERLAY_OUTLINE, fill_alpha=96, outline_alpha=255, id_range=(1, 0xFFFFFFFF),
+                          n_colours=None, ids: Mem = None, t_first: Mem = None):
+        """one clwh_overlay_slice call: its status; nothing is raised.  The region `source` (kind REGION_MASK: grow's mask layout,
+        REGION_LABELS: uint32[Z][Y][X]; dims = (X, Y, Z)) drawn over `frame` with the rays of render_slice's plane; palette: packed
+        RGBA8 words (n_colours defaults to the whole buffer).  ids (uint32) / t_first (float32): optional [height][width] buffers."""
+        d = OverlaySliceDesc()
+        _fill_overlay(d, frame, source, kind, dims, palette, width, height, n_colours, flags, fill_alpha, outline_alpha, id_range, ids, t_first)
+        for k in range(3):
+            d.origin[k], d.du[k], d.dv[k], d.normal[k] = float(origin[k]), float(du[k]), float(dv[k]), float(normal[k])
+        d.slab_samples, d.step = int(slab_samples), float(step)
+        return lib().clwh_overlay_slice(self.h, C.byref(d))
+
+    def overlay_slice(self, *args, **kw):
+        """overlay_slice_raw, raising on a status other than OK"""
+        _check(self.overlay_slice_raw(*args, **kw), "clwh_overlay_slice")
+
+    def overlay_camera_raw(self, frame: Mem, source: Mem, kind, dims, palette: Mem, cam_pos, cam_dir, width, height, step=0.5,
+                           t_near=0.0, t_far=float("inf"), flags=OVERLAY_FILL | OVERLAY_OUTLINE, fill_alpha=96, outline_alpha=255,
+                           id_range=(1, 0xFFFFFFFF), n_colours=None, ids: Mem = None, t_first: Mem = None):
+        """one clwh_overlay_camera call: its status; nothing is raised.  As overlay_slice_raw with render_projection's camera rays:
+        the first voxel of the region along each ray, whatever the volume shows in front of it."""
+        d = OverlayCameraDesc()
+        _fill_overlay(d, frame, source, kind, dims, palette, width, height, n_colours, flags, fill_alpha, outline_alpha, id_range, ids, t_first)
+        for k in range(3):
+            d.cam_pos[k], d.cam_dir[k] = float(cam_pos[k]), float(cam_dir[k])
+        d.step, d.t_near, d.t_far = float(step), float(t_near), float(t_far)
+        return lib().clwh_overlay_camera(self.h, C.byref(d))
+
+    def overlay_camera(self, *args, **kw):
+        """overlay_camera_raw, raising on a status other than OK"""
+        _check(self.overlay_camera_raw(*args, **kw), "clwh_overlay_camera")
 
     def mesh_isosurface_raw(self, volume: Mem, iso, flags=0, box=None, positions: Mem = None, normals: Mem = None, keys: Mem = None,
                             triangles: Mem = None, vertex_capacity=0, triangle_capacity=0):

@@ -825,6 +825,94 @@ typedef struct clwh_label_stats_desc {
 } clwh_label_stats_desc;
 int clwh_label_statistics(clwh_ctx *ctx, const clwh_label_stats_desc *desc);
 
+/* ---- overlays (not in the reference): a mask or a labelling drawn as coloured, half-transparent areas with an outline over the frame
+ * a view has just written -- on a slice (clwh_overlay_slice) or in a camera view (clwh_overlay_camera) -- and the id under every
+ * pixel (picking).  A view over buffers the library already produces: no volume is read, rewritten or rebuilt.  Integers and float
+ * comparisons only: defined bit for bit.
+ * Region.  `region.buffer` is a plain device buffer for dims = X, Y, Z, of one of two kinds:
+ *   CLWH_REGION_MASK    clwh_segment_grow's mask layout (8-byte aligned); word(v) = 1 where the bit of voxel v is set, else 0.  Bits
+ *                       at x >= X and the padding words are ignored, whatever they hold.
+ *   CLWH_REGION_LABELS  uint32 [z][y][x] (4-byte aligned): what clwh_segment_label wrote, or ANY words of the caller's, words
+ *                       >= 2^31 included; word(v) = the word.
+ * With the filter 1 <= id_lo <= id_hi, id(v) = word(v) if id_lo <= word(v) <= id_hi, else 0.  Limits as clwh_labels_to_mask's: no dim
+ * of 0, dims within the projections' rule, X * Y * Z <= 2^31 - 1.
+ * Rays.  A ray and its kept samples are defined for EVERY integer pixel (x, y), also outside the launched region:
+ *   clwh_overlay_slice   clwh_render_slice's: o = (origin + (float)x * du) + (float)y * dv, p_k = o + normal * ((float)k * step) for
+ *                        0 <= k < slab_samples (1 .. 8192), kept iff 0 <= p_k.c < dim_c on all three axes.
+ *   clwh_overlay_camera  clwh_render_projection's: generate_ray with the frame IMAGE's dims as totals, o = cam_pos (finite, as
+ *                        clwh_render_composite demands), p_k = o + d * ((float)k * step), kept iff t_near <= t_k <= t_far and inside.
+ * A kept sample lies in voxel v = ((int)p.x, (int)p.y, (int)p.z).  ID(x, y) = id(v) of the smallest kept k whose id is not 0, K(x, y)
+ * that k; ID = 0 if there is no kept sample or every kept sample has id 0.
+ * Outputs, written for the pixels of the launched region only.  ids (optional): uint32[height][width] = ID.  t_first (optional):
+ * float32[height][width] = (float)K * step, 0x7FC00000 where ID == 0.
+ * Frame.  `palette`: a plain device buffer (4-byte aligned) of n_colours (1 .. 65536) packed RGBA8 words, bytes in the frame's
+ * order; the colour of a pixel is (r, g, b, A) = palette[(ID - 1) % n_colours].  A pixel with ID != 0 is an OUTLINE pixel iff one of
+ * ID(x - 1, y), ID(x + 1, y), ID(x, y - 1), ID(x, y + 1) differs from ID(x, y) -- by the ray formula also at x = -1, x = width,
+ * y = -1, y = height, so the edge of the launched region is no boundary and tiling a frame into regions changes no byte; a neighbour
+ * without a kept sample has ID 0, so a structure cut by the volume's face is outlined there.  The overlay alpha a of a pixel, all
+ * divisions integer: with CLWH_OVERLAY_OUTLINE on an outline pixel a = (A * outline_alpha + 127) / 255; else with CLWH_OVERLAY_FILL
+ * on a pixel with ID != 0 a = (A * fill_alpha + 127) / 255; else the pixel is not touched.  Then for c in r, g, b
+ * out.c = (in.c * (255 - a) + col.c * a + 127) / 255 and out.alpha = in.alpha + ((255 - in.alpha) * a + 127) / 255; a == 0 leaves
+ * the same bytes.  With neither flag the frame is not written at all: the call only produces ids and t_first.  Pixels outside the
+ * region are never touched.
+ * Skipping.  CLWH_OVERLAY_DENSE reads every kept sample up to the first hit.  Without it an 8^3 brick or a cell of 4^3 bricks may be
+ * stepped over unread iff no voxel in it has a nonzero id: the table that says so is built per call from the region (the caller's
+ * buffers carry no content version).  Same bytes as the dense walk, by the contract.  As built, clwh_overlay_camera skips and
+ * clwh_overlay_slice walks densely (a slab is too short for the table to pay: DESIGN.md); the flag is accepted by both.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a NULL or wrong-kind frame; a NULL region
+ * buffer or palette, one that is an image or misaligned (8 bytes for a mask, 4 for labels and the palette); ids or t_first that are
+ * images; an unknown kind or unknown flag bits; id_lo == 0 or id_lo > id_hi; n_colours outside 1 .. 65536; fill_alpha or
+ * outline_alpha above 255; dims beyond the limits; for the slice call clwh_render_slice's conditions on slab_samples, step, origin,
+ * du, dv and normal, its 2^30 bound taken with width and height in place of width - 1 and height - 1 (the halo is evaluated); for
+ * the camera call clwh_render_composite's conditions on step, t_near, t_far and cam_pos.  CLWH_ERR_BAD_NDRANGE: the region rules of the
+ * projections.  CLWH_ERR_SIZE_MISMATCH: a region buffer smaller than its layout, a palette smaller than 4 * n_colours bytes, ids or
+ * t_first smaller than 4 * width * height bytes.  Nothing is written on any of these.
+ * Asynchronous and ordered on the context's stream; no derived data of any volume is built or invalidated.  The scratch (8 bytes per
+ * pixel of the region and its halo, 4 bytes per brick and per cell) is kept with the context and holds nothing between calls.  No
+ * host wait except when the scratch grows: a call with a larger region or more bricks than any before it on the context allocates,
+ * and waits for the stream's work on the smaller scratch before it frees that (like grow's scratch). */
+enum clwh_region_kind { CLWH_REGION_MASK = 0, CLWH_REGION_LABELS = 1 };
+enum clwh_overlay_flags {
+  CLWH_OVERLAY_FILL = 1,     /* blend the colour over every pixel with ID != 0 */
+  CLWH_OVERLAY_OUTLINE = 2,  /* ... and with outline_alpha over the outline pixels */
+  CLWH_OVERLAY_DENSE = 4     /* no brick skipping: same result by contract; for tests and timing */
+};
+typedef struct clwh_overlay_region {
+  clwh_mem *buffer;           /* plain device buffer of the given kind */
+  int32_t kind;               /* clwh_region_kind */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t id_lo, id_hi;      /* both ends included; 1 <= id_lo <= id_hi */
+} clwh_overlay_region;
+typedef struct clwh_overlay_paint {
+  clwh_mem *palette;          /* plain device buffer of n_colours RGBA8 words */
+  uint32_t n_colours;         /* 1 .. 65536 */
+  int32_t flags;              /* clwh_overlay_flags */
+  uint32_t fill_alpha, outline_alpha;  /* 0 .. 255 */
+  clwh_mem *ids;              /* optional uint32[height][width] */
+  clwh_mem *t_first;          /* optional float32[height][width] */
+} clwh_overlay_paint;
+typedef struct clwh_overlay_slice_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image, drawn onto */
+  clwh_overlay_region region;
+  clwh_overlay_paint paint;
+  float origin[3], du[3], dv[3], normal[3];  /* as clwh_slice_desc */
+  uint32_t width, height;     /* launched region: multiples of 8, <= frame dims, <= 65535 */
+  int32_t slab_samples;       /* 1 .. 8192 */
+  float step;                 /* > 0, finite */
+} clwh_overlay_slice_desc;
+typedef struct clwh_overlay_camera_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image, drawn onto; its dims are generate_ray's totals */
+  clwh_overlay_region region;
+  clwh_overlay_paint paint;
+  float cam_pos[3], cam_dir[3];
+  uint32_t width, height;
+  float step;                 /* h > 0, finite */
+  float t_near, t_far;        /* 0 and +INFINITY = whole volume */
+  int32_t reserved;           /* ignored */
+} clwh_overlay_camera_desc;
+int clwh_overlay_slice(clwh_ctx *ctx, const clwh_overlay_slice_desc *desc);
+int clwh_overlay_camera(clwh_ctx *ctx, const clwh_overlay_camera_desc *desc);
+
 /* clwh_sdf_build replaces the host loop of signed_distance_field::signed_distance_field
  * (app/signed_distance_field.cpp:7-35): base image + all propagation layers, no host round trip
  * per layer.  `sdf` is an S8 3-D image of the volume's dims.  n_launches (optional) receives the
