@@ -113,6 +113,26 @@ __device__ __forceinline__ bool start_certificate(uint32_t mask, f3 d, float dmi
   const float dsum = d.x + d.y + d.z;
   return ((mask >> octant) & 1u) != 0u && dmin >= dmin_needed && dsum == dsum;
 }
+// Hull certificates: direction k of the support table (k_hull_*, scene_kernels.hip), the centre of cell (k % 64, k / 64) of an octahedral
+// grid.  The unnormalised components are multiples of 1/64 below 2 and the sum of their squares a multiple of 2^-12 below 4: every
+// operation before the reciprocal square root is exact in binary32 whether or not it is contracted, so the table's builder, k_primary
+// and k_bounce get the same bits (v_rsq_f32 leaves the length within 2^-22 of 1: kHullSlack).
+__device__ __forceinline__ f3 hull_direction(unsigned k) {
+  static_assert(kHullGrid == 64, "cell centres are odd multiples of 1/64");
+  const float u = (float)(2 * (int)(k & 63u) - 63) * 0.015625f, v = (float)(2 * (int)((k >> 6) & 63u) - 63) * 0.015625f;
+  const float z = (1.0f - fabsf(u)) - fabsf(v);
+  const float x = z >= 0.0f ? u : copysignf(1.0f - fabsf(v), u), y = z >= 0.0f ? v : copysignf(1.0f - fabsf(u), v);
+  const float r = __builtin_amdgcn_rsqf((x * x + y * y) + z * z);
+  return f3{x * r, y * r, z * r};
+}
+// `code`: 1 + the index of a plane the first leg's start point lies in front of (k_primary), 0: none; `d` the leg's direction, `delta0`
+// hull_cert_delta0 (clwh_internal.hpp).  The far-face crawl and NaN directions as in certify_exit.
+__device__ __forceinline__ bool hull_certificate(uint32_t code, f3 d, float delta0) {
+  const f3 n = hull_direction(code - 1u);
+  const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+  const float dsum = d.x + d.y + d.z;
+  return code != 0u && dot3(d, n) >= delta0 && dmin >= 0.0009765625f && dsum == dsum;
+}
 __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
   int away;
   return certify_exit(a, p, d, budget, away);
@@ -163,6 +183,7 @@ template <> struct BounceStatsT<false> {
   __device__ void fresh_items(int, int) {}
   __device__ void swap_point() {}
   __device__ void start_cert(bool, bool) {}
+  __device__ void hull_cert(bool, bool, bool) {}
   __device__ void march_end(uint32_t *, int) {}
   template <bool TWO_RAYS> __device__ void flush(uint32_t *) {}
 };
@@ -212,9 +233,19 @@ template <> struct BounceStatsT<true> {
     start_tried += (uint32_t)__popcll(__ballot(tried)); start_granted += (uint32_t)__popcll(__ballot(granted));
     start_open = start_open || granted;
   }
+  // hull certificates, verified the same way; `both`: the octant proof grants the leg as well
+  uint32_t hull_tried = 0, hull_granted = 0, hull_both = 0;
+  bool hull_open = false;
+  __device__ __forceinline__ void hull_cert(bool tried, bool granted, bool both) {
+    hull_tried += (uint32_t)__popcll(__ballot(tried)); hull_granted += (uint32_t)__popcll(__ballot(granted));
+    hull_both += (uint32_t)__popcll(__ballot(both));
+    hull_open = hull_open || granted;
+  }
   __device__ __forceinline__ void march_end(uint32_t *counters, int ev) {
     if (start_open && ev != EV_EXIT) atomicAdd(&counters[CTR_START_WRONG], 1u);
+    if (hull_open && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_WRONG], 1u);
     start_open = false;
+    hull_open = false;
   }
   // lane 0 of a wave that ends
   template <bool TWO_RAYS> __device__ __forceinline__ void flush(uint32_t *counters) {
@@ -226,6 +257,7 @@ template <> struct BounceStatsT<true> {
     atomicAdd(&counters[CTR_CERT_PHASES], cert_phases); atomicAdd(&counters[CTR_CERT_LANES], cert_lanes);
     atomicAdd(&counters[CTR_CERT_GRANTED], cert_granted); atomicAdd(&counters[CTR_STEP_IDLE], step_idle);
     atomicAdd(&counters[CTR_START_TRIED], start_tried); atomicAdd(&counters[CTR_START_GRANTED], start_granted);
+    atomicAdd(&counters[CTR_HULL_TRIED], hull_tried); atomicAdd(&counters[CTR_HULL_GRANTED], hull_granted); atomicAdd(&counters[CTR_HULL_BOTH], hull_both);
   }
 };
 using BounceStats = BounceStatsT<kBounceStats>;

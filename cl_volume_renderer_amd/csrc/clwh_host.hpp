@@ -97,7 +97,7 @@ struct JitTf {
   hipFunction_t classify = nullptr;
 };
 
-// ---- derived scene data (step bytes + hit records + per-brick minima + exit-certificate table + start-certificate table), ONE copy per device however many
+// ---- derived scene data (step bytes + hit records + per-brick minima + exit-certificate table + start-certificate table + hull-certificate table), ONE copy per device however many
 // contexts (frame lanes, callers) render the same (volume content, SDF content, transfer function): contexts hold it by
 // shared_ptr and find it in a process-wide registry (clwh_render.hip); the memory goes when the last context lets go of it.
 struct PackedScene {
@@ -109,6 +109,7 @@ struct PackedScene {
   std::string tf_identity;   // opaque (hiprtc) transfer functions: the source text -- two sources may share a palette
   int32_t macro_shift = 0;
   bool start_table = false;  // the allocation ends with the start-certificate table (one byte per voxel)
+  bool hull_table = false;   // ... followed by the hull-certificate table and its scratch
   int32_t dims[3] = {0, 0, 0};  // of the volume (the macro table's place in `data` follows from them)
   uint64_t generation = 0;   // process-wide unique id of this content (part of the primary-hit key)
   Event ready;               // recorded on the building stream after the last build kernel; adopters make their stream wait for it
@@ -138,6 +139,7 @@ struct Tuning {
   int32_t unit_group = 1, unit_affinity = 0, unit_queues = 8;
   int32_t cert_hint = 1;       // CLWH_TUNE_CERT_HINT=0: a refused march asks again at its next long step, whatever the refusing entry says
   int32_t start_cert = 1;      // CLWH_TUNE_START_CERT=0: no start-certificate table (a byte per voxel), first legs march from their first step
+  int32_t hull_cert = 1;       // CLWH_TUNE_HULL_CERT=0: no hull-certificate table, no plane search in k_primary, no test in k_bounce
   int32_t cert_min_step = -1;  // CLWH_TUNE_CERT: 0 = exit certificates off; -1 = by volume size (12 at 512^3, 24 at 1024^3, 48 at 2048^3:
                                // the best of the sweeps in profiles/r02_sweep_k_bounce_lds_state.txt)
   uint32_t bounce_max_blocks = 2048;  // CLWH_TUNE_BLOCKS
@@ -167,6 +169,7 @@ struct PrimaryHits {
   } key{};
   bool valid = false;  // cleared by clwh_ctx_invalidate_derived (scene or camera)
   DeviceBuffer pix_slot, hits;
+  DeviceBuffer hull_codes;    // a word per hit: its hull-certificate plane (k_primary), when the scene has the table
   uint32_t n_hits = 0;
   bool n_hits_known = false;  // false: the count of this camera's hits is only on the device so far
   // the count travels to the host behind the camera's k_primary without anybody waiting for it: a 4-byte copy into page-locked

@@ -59,6 +59,7 @@ enum : uint32_t {
   CTR_CERT_PHASES = CTR_EV_KIND + 4, CTR_CERT_LANES, CTR_CERT_GRANTED,
   CTR_SWAPS, CTR_STEP_IDLE,  // k_bounce2 only: swap points; k_bounce only: idle lanes, summed over the step iterations
   CTR_START_TRIED, CTR_START_GRANTED, CTR_START_WRONG,  // k_bounce only: start certificates (first legs of long launches); wrong: see BounceStats
+  CTR_HULL_TRIED, CTR_HULL_GRANTED, CTR_HULL_BOTH, CTR_HULL_WRONG,  // k_bounce only: hull certificates; both: legs either proof grants
   CTR_STATS_END,
   CTR_QUEUE_STRIDE = 32,  // head of unit queue q: slot CTR_QUEUE_STRIDE * (q + 1), every head on its own 128-byte line
 };
@@ -80,6 +81,12 @@ struct RenderArgs {
   // volume corner of octant o may be an event.  k_primary copies the byte of a hit's start voxel into the hit record; nullptr: not built
   const uint8_t *start_free;
   float start_cert_dmin;   // a first leg is granted its certificate only if min |direction component| is at least this (start_cert_dmin below)
+  // hull certificates (k_hull_* in scene_kernels.hip): kHullPlanes entries {n_k, h_k}, every corner of every event voxel has n_k . c <= h_k.
+  // k_primary stores per hit (hull_codes, beside the hit records) 1 + the index of a plane the hit's start point lies in front of,
+  // 0: none; nullptr: not built
+  const float4 *hull;
+  uint32_t *hull_codes;
+  float hull_delta0;       // a first leg with such a plane is granted if direction . n_k is at least this (hull_cert_delta0 below)
   int32_t NBX, NBY;
   const uint32_t *env;     // RGBA8 packed, row-major
   int32_t env_w, env_h;
@@ -174,7 +181,8 @@ inline int macro_cell_shift(int X, int Y, int Z, int forced) {
 }
 hipError_t launch_macro_table(const uint32_t *brick_min, int NBX, int NBY, int NBZ, uint8_t *macro, int X, int Y, int Z, int shift, hipStream_t s);
 // The start-certificate table of scene_kernels.hip: `regular` (one word) and `table` (X * Y * Z bytes) are written.
-hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s);
+// `ends` (optional): Y * Z int2, a row's first and last event voxel (X, -1: none) for the hull table
+hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int2 *ends, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s);
 // The largest step value the start certificate's bound counts on: the SDF build's layer count, min(127, largest dimension / 2)
 // (signed_distance_field.cpp), at which its values saturate.
 inline int start_cert_cap(int X, int Y, int Z) {
@@ -211,6 +219,40 @@ inline float start_cert_dmin(int X, int Y, int Z) {
   }
   return 2.0f;
 }
+// ---- hull certificates: the support table of the event voxels over a fixed set of directions (k_hull_*, scene_kernels.hip)
+constexpr int kHullGrid = 64;                           // the directions: the cell centres of an octahedral grid of 64 x 64 (hull_direction, bounce_device.hpp)
+constexpr int kHullPlanes = kHullGrid * kHullGrid;
+// Every stored h_k is the binary32 maximum of n_k . c over the corners plus this slack.  It covers, with room to spare: the roundings
+// of that maximum and of k_primary's n_k . P (each below 2^-10 for coordinates up to kHullMaxDim), the march's own roundings (70
+// additions, half an ulp of a coordinate below 2^11 each, on three axes: below 2^-5), and n_k being 2^-22 off unit length.  So a
+// start point with n_k . P - h_k >= 0 in binary32 is, in the reals, more than 2^-5 in front of the plane: the bound's m0 is 0.
+constexpr float kHullSlack = 0.0625f;
+constexpr int kHullMaxDim = 2048;                       // no table for a longer volume
+// The smallest direction . n_k (a multiple of 1/64) with which a first leg that starts in front of plane k (margin m0 = 0 after the
+// slack) is PROVEN to leave the volume within its 70 steps.  Every event voxel lies behind the plane; after a path t the position is at
+// least t * delta0 in front of it (the direction is constant, the roundings are in the slack), hence at least that far, Euclidean, from
+// every point of every event voxel, and its voxel at least floor(t * delta0 / sqrt(3)) - 2 voxels (Chebyshev) from every event voxel.
+// By the regularity of the step bytes (k_start_regular; the table is only built from bytes that pass) the step taken there is at least
+// min(cap, that distance) and never below 1: no voxel in front of the plane is an event.  The bound grows with t and the real steps
+// are no shorter, so the real path is at least the recurrence's after every step; once t exceeds sqrt(3) * (largest dimension + 1) the
+// largest direction component has carried its coordinate out of the volume.  70 - 5 steps: certify_exit's reserve.  2 = none qualifies.
+inline float hull_cert_delta0(int X, int Y, int Z) {
+  const double longest = (double)(X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z));
+  const double reach = 1.7320508075688772 * (longest + 1.0), cap = (double)start_cert_cap(X, Y, Z);
+  for (int k = 1; k <= 64; ++k) {
+    const double delta0 = (double)k / 64.0;
+    double t = 0.0;
+    for (int step = 0; step < 70 - 5 && t <= reach; ++step) {
+      const double m = (double)(long long)(t * delta0 / 1.7320508075688772) - 2.0;
+      const double bound = m > cap ? cap : m;
+      t += bound < 1.0 ? 1.0 : bound;
+    }
+    if (t > reach) return (float)delta0;
+  }
+  return 2.0f;
+}
+// `ends`: scratch of Y * Z int2 (k_start_rows leaves a row's first and last event voxel there); `hull`: kHullPlanes float4
+hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, int X, int Y, int Z, hipStream_t s);
 constexpr uint64_t kStartTableBudget = 2ull << 30;  // bytes (= voxels): larger volumes get no start certificates
 hipError_t launch_primary(const RenderArgs &a, hipStream_t s);
 hipError_t launch_bounce(const RenderArgs &a, hipStream_t s);

@@ -26,8 +26,9 @@ PackedScene::~PackedScene() {
 // layout of a PackedScene's allocation
 struct PackedLayout {
   int X, Y, Z, NBX, NBY, NBZ, mshift, MNX, MNY, MNZ;
-  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, off_start, bytes;
+  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, off_start, off_hull_ends, off_hull, bytes;
   bool start_table;  // the start-certificate table is part of the allocation
+  bool hull_table;   // ... and behind it the hull-certificate table with its scratch (the rows' first and last event voxels)
 };
 // Start certificates (k_start_*, scene_kernels.hip) are built for tables the step byte decides alone (no rule reads `gradient`), under
 // which the border texel is no event (the other exit certificates are off there too), for volumes whose table fits the budget (and the
@@ -36,7 +37,13 @@ static bool wants_start_table(const Tuning &t, const TfDev &tf, const clwh_mem *
   return t.start_cert != 0 && tf.uses_gradient == 0 && tf.border_class == 0 && fits_grid_yz(volume) &&
          (uint64_t)volume->dims[0] * volume->dims[1] * volume->dims[2] <= kStartTableBudget;
 }
-static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift, bool start_table) {
+// Hull certificates (k_hull_*) are built where start certificates are (the same proof obligations), for volumes of at most
+// kHullMaxDim voxels along every axis, unless CLWH_TUNE_HULL_CERT=0.
+static bool wants_hull_table(const Tuning &t, const TfDev &tf, const clwh_mem *volume) {
+  return t.hull_cert != 0 && wants_start_table(t, tf, volume) && volume->dims[0] <= (size_t)kHullMaxDim && volume->dims[1] <= (size_t)kHullMaxDim &&
+         volume->dims[2] <= (size_t)kHullMaxDim;
+}
+static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift, bool start_table, bool hull_table) {
   PackedLayout L;
   L.X = (int)volume->dims[0]; L.Y = (int)volume->dims[1]; L.Z = (int)volume->dims[2];
   L.NBX = (L.X + 7) / 8; L.NBY = (L.Y + 7) / 8; L.NBZ = (L.Z + 7) / 8;
@@ -52,13 +59,17 @@ static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift
   L.off_start = (L.off_macro + (size_t)L.MNX * L.MNY * L.MNZ * 8u + 15u) & ~(size_t)15u;  // eight octant entries per cell
   // the start-certificate table: 16 bytes for the `regular` word, then one byte per voxel, x fastest
   L.start_table = start_table;
-  L.bytes = L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u);
+  L.off_hull_ends = (L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u) + 15u) & ~(size_t)15u;
+  L.hull_table = hull_table;
+  L.off_hull = L.off_hull_ends + (hull_table ? (size_t)L.Y * L.Z * sizeof(int2) : 0u);  // (a multiple of 8; float4 loads need 16)
+  L.off_hull = (L.off_hull + 15u) & ~(size_t)15u;
+  L.bytes = hull_table ? L.off_hull + (size_t)kHullPlanes * sizeof(float4) : L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u);
   return L;
 }
 
 static bool packed_matches(const PackedScene &p, int device, const PackedLayout &L, const clwh_mem *volume, const clwh_mem *sdf,
                            const TfDev &tf, const std::string &tf_identity) {
-  return !p.stale && p.device == device && p.data.bytes == L.bytes && p.macro_shift == L.mshift && p.start_table == L.start_table && p.vol == volume->dptr &&
+  return !p.stale && p.device == device && p.data.bytes == L.bytes && p.macro_shift == L.mshift && p.start_table == L.start_table && p.hull_table == L.hull_table && p.vol == volume->dptr &&
          p.sdf == sdf->dptr && p.vol_ver == volume->version() && p.sdf_ver == sdf->version() &&
          !std::memcmp(&p.tf, &tf, sizeof tf) && p.tf_identity == tf_identity;
 }
@@ -121,7 +132,10 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
   }));
   if (L.start_table)
     CLWH_TRY(timed(ctx, CLWH_TIMER_REPACK, [&] {
-      return launch_start_table(r.stepb, data + L.off_start + 16u, reinterpret_cast<uint32_t *>(data + L.off_start), L.X, L.Y, L.Z, L.NBX, L.NBY, L.NBZ, ctx->stream);
+      int2 *ends = L.hull_table ? reinterpret_cast<int2 *>(data + L.off_hull_ends) : nullptr;
+      const hipError_t e = launch_start_table(r.stepb, data + L.off_start + 16u, reinterpret_cast<uint32_t *>(data + L.off_start), ends, L.X, L.Y, L.Z, L.NBX, L.NBY, L.NBZ, ctx->stream);
+      if (e != hipSuccess || !L.hull_table) return e;
+      return launch_hull_table(ends, reinterpret_cast<const uint32_t *>(data + L.off_start), reinterpret_cast<float4 *>(data + L.off_hull), L.X, L.Y, L.Z, ctx->stream);
     }));
   HIP_TRY(hipEventRecord(entry->ready.ev, ctx->stream));
   ctx->scene = entry;
@@ -135,6 +149,7 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
     entry->tf_identity = tf_identity;
     entry->macro_shift = L.mshift;
     entry->start_table = L.start_table;
+    entry->hull_table = L.hull_table;
     entry->dims[0] = L.X; entry->dims[1] = L.Y; entry->dims[2] = L.Z;
     entry->generation = ++g_packed_generation;
     entry->stale = false;
@@ -248,6 +263,7 @@ static int describe_launch(const clwh_ctx *ctx, const clwh_render_desc *d, Rende
   a.unit_queues = t.unit_queues;
   a.cert_hint = t.cert_hint;
   a.start_cert_dmin = start_cert_dmin(a.X, a.Y, a.Z);
+  a.hull_delta0 = hull_cert_delta0(a.X, a.Y, a.Z);
   return CLWH_OK;
 }
 
@@ -257,7 +273,7 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   const uint8_t *cls_in = nullptr;
   CLWH_TRY(kernel_tf(k, d->volume, a.tf, &cls_in));
   a.tf.literal_gradient_taps = ctx->tune.literal_gradient;
-  const PackedLayout L = packed_layout(d->volume, ctx->tune.macro_shift, wants_start_table(ctx->tune, a.tf, d->volume));
+  const PackedLayout L = packed_layout(d->volume, ctx->tune.macro_shift, wants_start_table(ctx->tune, a.tf, d->volume), wants_hull_table(ctx->tune, a.tf, d->volume));
   CLWH_TRY(ensure_packed(ctx, L, d->volume, d->sdf, a.tf, cls_in, k->jit ? k->jit->source : std::string()));
   const uint8_t *packed = ctx->scene->data.as<uint8_t>();
   a.grec = reinterpret_cast<const uint2 *>(packed);
@@ -268,6 +284,7 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   a.sdf_lin = (const int8_t *)d->sdf->dptr;
   a.macro = packed + L.off_macro;
   a.start_free = L.start_table ? packed + L.off_start + 16u : nullptr;
+  a.hull = L.hull_table ? reinterpret_cast<const float4 *>(packed + L.off_hull) : nullptr;
   a.macro_shift = L.mshift;
   a.MNX = L.MNX; a.MNY = L.MNY; a.MNZ = L.MNZ;
   // An exit certificate proves "this march leaves the volume without a Hit"; a position with a coordinate == dimension or NaN
@@ -287,6 +304,7 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
   const size_t slots = pixel_slots(a);
   CLWH_TRY(p.pix_slot.reserve(ctx->stream, slots * sizeof(uint32_t)));
   CLWH_TRY(p.hits.reserve(ctx->stream, slots * sizeof(HitRec)));
+  if (a.hull) CLWH_TRY(p.hull_codes.reserve(ctx->stream, slots * sizeof(uint32_t)));
   CLWH_TRY(s.counters.reserve(ctx->stream, PassScratch::kCounters * sizeof(uint32_t)));
   bool fresh_flags = false;
   CLWH_TRY(s.sticky_flags.reserve(ctx->stream, 64, &fresh_flags));
@@ -294,6 +312,7 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
   a.sticky_flags = s.sticky_flags.as<uint32_t>();
   a.pix_slot = p.pix_slot.as<uint32_t>();
   a.hits = p.hits.as<HitRec>();
+  a.hull_codes = a.hull ? p.hull_codes.as<uint32_t>() : nullptr;
   a.counters = s.counters.as<uint32_t>();
 
   PrimaryHits::Key key;
@@ -425,6 +444,9 @@ static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
   std::fprintf(stderr, "[bounce stats] lane_steps=%u event_lanes=%u start certificates (%s) tried/granted/wrong=%u/%u/%u dmin=%.6f\n", h[CTR_STEP_LANES],
                h[CTR_EVENT_LANES], (CLVR_BOUNCE_STATS + 0) == 2 ? "taken" : "verified: marched literally", h[CTR_START_TRIED], h[CTR_START_GRANTED],
                h[CTR_START_WRONG], (double)a.start_cert_dmin);
+  std::fprintf(stderr, "[bounce stats] hull certificates tried/granted/wrong=%u/%u/%u, of the granted the octant proof grants %u; either proof grants %u first legs; delta0=%.6f\n",
+               h[CTR_HULL_TRIED], h[CTR_HULL_GRANTED], h[CTR_HULL_WRONG], h[CTR_HULL_BOTH], h[CTR_START_GRANTED] + h[CTR_HULL_GRANTED] - h[CTR_HULL_BOTH],
+               (double)a.hull_delta0);
   return CLWH_OK;
 }
 #endif
@@ -577,7 +599,7 @@ static PackedLayout scene_layout(clwh_ctx *ctx) {
   std::lock_guard<std::mutex> lock(g_scenes_mutex);
   clwh_mem shape{};
   for (int q = 0; q < 3; ++q) shape.dims[q] = (size_t)ctx->scene->dims[q];
-  return packed_layout(&shape, ctx->scene->macro_shift, ctx->scene->start_table);
+  return packed_layout(&shape, ctx->scene->macro_shift, ctx->scene->start_table, ctx->scene->hull_table);
 }
 
 int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
@@ -611,6 +633,44 @@ int clwh_debug_start_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int
 int clwh_debug_start_cert_dmin(int32_t X, int32_t Y, int32_t Z, float *dmin_out) {
   if (!dmin_out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
   *dmin_out = start_cert_dmin(X, Y, Z);
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
+  const PackedLayout L = scene_layout(ctx);
+  info_out[0] = kHullGrid; info_out[1] = kHullPlanes; info_out[2] = 0; info_out[3] = L.hull_table ? 1 : 0;
+  if (!host_out || !L.hull_table) return CLWH_OK;  // the size alone; or there is no table
+  const size_t bytes = (size_t)kHullPlanes * sizeof(float4);
+  if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + L.off_hull, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_cert_bound(int32_t X, int32_t Y, int32_t Z, float out[2]) {
+  if (!out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
+  out[0] = hull_cert_delta0(X, Y, Z);
+  out[1] = kHullSlack;
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_codes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out) {
+  if (!ctx || !n_hits_out) return CLWH_ERR_INVALID_VALUE;
+  PrimaryHits &p = ctx->primary;
+  if (!p.valid || !p.hits.ptr || !ctx->pass.counters.ptr) return CLWH_ERR_BAD_ARGS;  // no camera rendered yet
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(n_hits_out, ctx->pass.counters.as<uint32_t>() + CTR_HITS, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!host_out) return CLWH_OK;  // the count alone
+  const bool built = ctx->scene && ctx->scene->hull_table && p.hull_codes.ptr;
+  const size_t bytes = (size_t)*n_hits_out * sizeof(uint32_t);
+  if (capacity < bytes || (built && p.hull_codes.bytes < bytes)) return CLWH_ERR_SIZE_MISMATCH;
+  if (!built) { std::memset(host_out, 0, bytes); return CLWH_OK; }  // no table: no hit has a plane
+  HIP_TRY(hipMemcpyAsync(host_out, p.hull_codes.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return CLWH_OK;
 }
 

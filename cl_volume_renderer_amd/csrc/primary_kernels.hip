@@ -53,6 +53,15 @@ __global__ __launch_bounds__(64) void k_primary(const RenderArgs a) {
     base = __shfl(base, leader);
   }
 
+  // the coarse grid of the hull-certificate search below, once per wave that has a hit (the block is one wave)
+  constexpr int kHullCoarse = kHullGrid / 4;
+  __shared__ float4 hull_coarse[kHullCoarse * kHullCoarse];
+  if (a.hull != nullptr && hit_mask != 0ull) {
+    for (int c = (int)lane; c < kHullCoarse * kHullCoarse; c += 64)
+      hull_coarse[c] = a.hull[((c / kHullCoarse) * 4 + 2) * kHullGrid + (c % kHullCoarse) * 4 + 2];
+    __syncthreads();
+  }
+
   int64_t raw_entry = -1;
   if (hit) {
     const uint32_t h = base + prefix_count(hit_mask);
@@ -75,6 +84,38 @@ __global__ __launch_bounds__(64) void k_primary(const RenderArgs a) {
       const f3 p = (current_ray.origin + current_ray.direction) + normal * 2.0f;
       if (__float_as_uint(p.x) < __float_as_uint(dx) && __float_as_uint(p.y) < __float_as_uint(dy) && __float_as_uint(p.z) < __float_as_uint(dz))
         start_free = a.start_free[((size_t)(int)p.z * (size_t)a.Y + (size_t)(int)p.y) * (size_t)a.X + (size_t)(int)p.x];
+    }
+    // hull certificate (k_hull_*, scene_kernels.hip): a plane of the support table with the same P in front of it, by the largest margin
+    // m = n_k . P - h_k the search finds -- every 4th cell of the octahedral grid in both directions first (the wave's copy in LDS,
+    // above), then the 7 x 7 cells around the best of those.  The margin is concave in an unnormalised normal, so the second look
+    // rarely misses the best plane, and any plane with m >= 0 is a valid one.  (The hit's own normal is a poor guide: central
+    // differences on a voxelised surface are a dozen degrees off, and a plane that far from the tangent stands voxels behind P.)
+    // The code lives beside the hit record, not in it.
+    if (a.hull) {
+      const f3 p = (current_ray.origin + current_ray.direction) + normal * 2.0f;
+      float best = -INFINITY;  // (a NaN in P: every comparison fails, no plane)
+      int bc = 0;
+#pragma unroll 4
+      for (int c = 0; c < kHullCoarse * kHullCoarse; ++c) {
+        const float4 e = hull_coarse[c];
+        const float m = ((e.x * p.x + e.y * p.y) + e.z * p.z) - e.w;
+        if (m > best) { best = m; bc = c; }
+      }
+      int bi = (bc % kHullCoarse) * 4 + 2, bj = (bc / kHullCoarse) * 4 + 2;
+      uint32_t code = 0u;
+      float margin = best;
+      const int i0 = bi, j0 = bj;
+#pragma unroll 1
+      for (int dj = -3; dj <= 3; ++dj)  // (rolled: unrolled, the forty-nine gathers cost the kernel three of its eight waves)
+        for (int di = -3; di <= 3; ++di) {
+          const int i = min(max(i0 + di, 0), kHullGrid - 1), j = min(max(j0 + dj, 0), kHullGrid - 1);
+          const float4 e = a.hull[j * kHullGrid + i];
+          const float m = ((e.x * p.x + e.y * p.y) + e.z * p.z) - e.w;
+          if (m >= margin) { margin = m; bi = i; bj = j; }
+        }
+      // bits 0-12: 1 + the plane's index; bits 16-31: the margin in 1/256 voxels, rounded down (k_bounce needs its sign only)
+      if (margin >= 0.0f) code = ((uint32_t)(bj * kHullGrid + bi) + 1u) | ((uint32_t)fminf(floorf(margin * 256.0f), 65535.0f) << 16);
+      a.hull_codes[h] = code;
     }
     q3.x = x | (y << 16); q3.y = pslot; q3.z = start_free; q3.w = 0u;
     uint4 *dst = reinterpret_cast<uint4 *>(&a.hits[h]);

@@ -9,12 +9,15 @@
 //   k_repack   (when volume / SDF / TF changed)  bricked step bytes + hit records (packed_volume.hpp);      scene_kernels.hip
 //                                                k_macro_*: the exit-certificate table
 //                                                k_start_*: the start-certificate table (a byte per voxel)
+//                                                k_hull_*: the hull-certificate table (support of the event voxels in 4096 directions)
 //   k_primary  (when the camera changed)         one lane per pixel: ray, box entry, primary march;         primary_kernels.hip
 //                                                hits are compacted into 64-byte records with a
 //                                                wave ballot + prefix (one atomic per wave);
 //                                                misses keep their environment colour
 //                                                a hit carries the start-certificate byte of the voxel
 //                                                its distribution rays start from
+//                                                and, beside its record, the plane of the hull table that
+//                                                start point lies furthest in front of
 //   k_bounce   (every launch, 1..64 seeds)       persistent waves pull (hit, seed) items from eight         this file
 //                                                work queues; each lane runs the sample's two               (k_bounce2, two rays per
 //                                                distribution rays as a small state machine; idle           lane: bounce_two_rays.hpp)
@@ -83,14 +86,15 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   enum : int { C_START_X, C_START_Y, C_START_Z,  // hit origin + hit direction: where both distribution rays start from
                C_NORMAL_X, C_NORMAL_Y, C_NORMAL_Z,
                C_ENTRY_LO,
-               C_ENTRY_HI,  // bits 0-23: the entry's (a stored entry is -1, -2 or below 2^34: bit 23 is its sign); bits 24-31: the hit's start-certificate byte
+               C_ENTRY_HI,  // bits 0-7: the entry's (a stored entry is -1, -2 or below 2^34: bit 7 is its sign); bits 8-20: the hit's hull-certificate code;
+                            // bits 24-31: the hit's start-certificate byte
                C_PIXEL, C_HIT, C_SEED,
                C_FIX,  // (fix + 2) << 2 | npend; fix: fix-up record of the sample (-1: none, -2: dropped, the buffer overflowed),
                        // npend: pending environment terms written to it
                C_BV_R, C_BV_G, C_BV_B, C_FIELDS };
   __shared__ uint32_t cold[C_FIELDS][kBounceThreads];
 #define COLD(f) cold[f][threadIdx.x]
-#define COLD_ENTRY_HI() ((uint32_t)((int32_t)(COLD(C_ENTRY_HI) << 8) >> 8))
+#define COLD_ENTRY_HI() ((uint32_t)((int32_t)(COLD(C_ENTRY_HI) << 24) >> 24))
   // path state; energies and colour carry over from distribution ray 1 into ray 2 (SURVEY "hard parts")
   Ray ray{{0, 0, 0}, {0, 0, 0}};
   float atten = 0.0f, r_energy = 0.0f, g_energy = 0.0f, b_energy = 0.0f;
@@ -111,6 +115,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   const int cert_at = a.cert_min_step != 0 ? a.cert_min_step : kCertNever;
   // first legs ask the hit's start-certificate byte: long launches only (launch_bounce); tables with `gradient` rules have no such table
   const bool start_cert = !USE_GRAD && a.cert_min_step != 0;
+  const bool hull_cert = start_cert && a.hull_codes != nullptr;  // ... and the hit's hull-certificate code
   bool exhausted = false;  // wave-uniform: the queue has no more items
   BounceStats stats;
 
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             if (granted) {
               COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
               COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
-              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = (q2.w & 0x00FFFFFFu) | (q3.z << 24);
+              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = (q2.w & 0xFFu) | (hull_cert ? (a.hull_codes[h] & 0x1FFFu) << 8 : 0u) | (q3.z << 24);
               COLD(C_PIXEL) = q3.x;
               COLD(C_HIT) = h;
               COLD(C_SEED) = (uint32_t)a.seeds[s];
@@ -382,6 +387,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
 
     // ---- event phase, opening half: the bounce is one shared block, then the march's first SDF read ---------
     bool sc_tried = false, sc_granted = false;  // this lane's first leg asked for / holds a start certificate
+    bool hc_tried = false, hc_granted = false;  // ... a hull certificate
     if (st >= ST_EVENT) {
       const int ev = st - ST_EVENT;
       bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
@@ -441,13 +447,23 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             // component with which it provably leaves within its 70 steps.  Like every exit certificate it ends the march at once:
             // only the direction is used from here on, and not one step byte is fetched.
             sc_tried = true;
-            sc_granted = start_certificate(COLD(C_ENTRY_HI) >> 24, nr.direction, a.start_cert_dmin);
+            const uint32_t word = COLD(C_ENTRY_HI);
+            sc_granted = start_certificate(word >> 24, nr.direction, a.start_cert_dmin);
+            // Hull certificate.  k_primary has found a plane {x : n_k . x = h_k} with every corner of every event voxel behind it and
+            // the start point in front of it (k_hull_*, scene_kernels.hip); a leg with direction . n_k >= hull_cert_delta0
+            // (clwh_internal.hpp: the proof) moves away from every event voxel linearly with its path, the steps grow with that
+            // distance, and it provably leaves within its 70 steps.  The proof that fits a leg leaving a convex surface, where the
+            // octant's box nearly always holds the object.
+            if (hull_cert) {
+              hc_tried = (word & 0x001FFF00u) != 0u;
+              hc_granted = hull_certificate((word >> 8) & 0x1FFFu, nr.direction, a.hull_delta0);
+            }
           }
         }
         ray = nr;
       }
 
-      if (sc_granted && !kStartCertVerify) {
+      if ((sc_granted || hc_granted) && !kStartCertVerify) {
         st = ST_EVENT + EV_EXIT;  // the next closing half takes it from here
       } else {
         // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
@@ -457,6 +473,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
       }
     }
     stats.start_cert(sc_tried, sc_granted);
+    stats.hull_cert(hc_tried, hc_granted, hc_granted && sc_granted);
   }
 #undef COLD_ENTRY_HI
 #undef COLD

@@ -1,5 +1,5 @@
-// scene_kernels.hip -- what the `render` pass derives from the scene: step bytes and hit records (k_repack), the exit-certificate table (k_macro_*), the start-certificate table (k_start_*)
-#include "render_device.hpp"
+// scene_kernels.hip -- what the `render` pass derives from the scene: step bytes and hit records (k_repack), the exit-certificate table (k_macro_*), the start-certificate table (k_start_*), the hull-certificate table (k_hull_*)
+#include "bounce_device.hpp"
 
 namespace clvr {
 
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_start_regular(const uint8_t *__restrict
 }
 // x: a wave per row finds the row's first and last event voxel; bits of the octants that head for x = X - 1 (even o) are set behind the
 // last one, those of the octants that head for x = 0 before the first.  A block takes the 4 x 4 rows of a row of sub-bricks.
-__global__ __launch_bounds__(256) void k_start_rows(const uint8_t *__restrict__ stepb, uint8_t *__restrict__ table, int X, int Y, int Z, int NBX, int NBY) {
+__global__ __launch_bounds__(256) void k_start_rows(const uint8_t *__restrict__ stepb, uint8_t *__restrict__ table, int2 *__restrict__ ends, int X, int Y, int Z, int NBX, int NBY) {
   const int lane = (int)(threadIdx.x & 63u), y = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (y >= Y) return;
   for (int k = 0; k < 4; ++k) {
@@ -322,6 +322,7 @@ __global__ __launch_bounds__(256) void k_start_rows(const uint8_t *__restrict__ 
     }
     uint8_t *row = table + ((size_t)z * (size_t)Y + (size_t)y) * (size_t)X;
     for (int x = lane; x < X; x += 64) row[x] = (uint8_t)((x > last ? 0x55u : 0u) | (x < first ? 0xAAu : 0u));
+    if (ends != nullptr && lane == 0) ends[(size_t)z * (size_t)Y + (size_t)y] = make_int2(first, last);  // for k_hull_support
   }
 }
 // y (axis 1) and z (axis 2): one thread per line, neighbouring threads neighbouring x.  A bit survives only if it is set in every voxel
@@ -347,13 +348,58 @@ __global__ __launch_bounds__(256) void k_start_scan(uint8_t *__restrict__ table,
     line[(size_t)i * stride] = (uint8_t)(((v & up) | (run & ~up)) & keep);
   }
 }
-hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s) {
+hipError_t launch_start_table(const uint8_t *stepb, uint8_t *table, uint32_t *regular, int2 *ends, int X, int Y, int Z, int NBX, int NBY, int NBZ, hipStream_t s) {
   hipError_t e = hipMemsetAsync(regular, 1, sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_start_regular, dim3((unsigned)(NBX * NBY * NBZ)), dim3(256), 0, s, stepb, X, Y, Z, NBX, NBY, (unsigned)start_cert_cap(X, Y, Z), regular);
-  hipLaunchKernelGGL(k_start_rows, dim3(((unsigned)Y + 3u) / 4u, ((unsigned)Z + 3u) / 4u), dim3(256), 0, s, stepb, table, X, Y, Z, NBX, NBY);
+  hipLaunchKernelGGL(k_start_rows, dim3(((unsigned)Y + 3u) / 4u, ((unsigned)Z + 3u) / 4u), dim3(256), 0, s, stepb, table, ends, X, Y, Z, NBX, NBY);
   hipLaunchKernelGGL(k_start_scan, dim3(((unsigned)X + 255u) / 256u, (unsigned)Z), dim3(256), 0, s, table, X, Y, Z, 1, (const uint32_t *)nullptr);
   hipLaunchKernelGGL(k_start_scan, dim3(((unsigned)X + 255u) / 256u, (unsigned)Y), dim3(256), 0, s, table, X, Y, Z, 2, (const uint32_t *)regular);
+  return hipGetLastError();
+}
+
+// ---- hull certificates: the support table of the event voxels (k_primary picks a plane per hit, k_bounce ends a first leg that heads
+// away from it: render_kernels.hip).  Entry k = {n_k, h_k}: n_k = hull_direction(k), h_k an upper bound of n_k . c over the eight
+// corners c of every event voxel (step byte bit 7).  Along a row of voxels n_k . c is largest at the row's first or its last event
+// voxel, which k_start_rows has found already: a thread takes one direction over kHullRows rows, an ordered-integer atomic maximum
+// joins the row groups, and k_hull_finish adds the corner term and the slack (clwh_internal.hpp).  Step bytes that are not `regular`
+// (k_start_regular), or without any event, leave h_k = +inf: no point is in front of such a plane.
+constexpr int kHullRows = 512;
+__device__ __forceinline__ uint32_t ordered_bits(float v) {
+  const uint32_t b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__global__ __launch_bounds__(256) void k_hull_support(const int2 *__restrict__ ends, int Y, int n_rows, uint32_t *__restrict__ best_out) {
+  const unsigned k = blockIdx.x * 256u + threadIdx.x;
+  const f3 n = hull_direction(k);
+  const int r0 = (int)blockIdx.y * kHullRows, r1 = min(r0 + kHullRows, n_rows);
+  float best = -INFINITY;
+  for (int r = r0; r < r1; ++r) {  // (wave-uniform: the row's ends arrive by scalar loads)
+    const int2 e = ends[r];
+    if (e.y < 0) continue;
+    const float yz = n.y * (float)(r % Y) + n.z * (float)(r / Y);
+    best = fmaxf(best, yz + fmaxf(n.x * (float)e.x, n.x * (float)e.y));
+  }
+  if (best > -INFINITY) atomicMax(&best_out[4u * k + 3u], ordered_bits(best));  // the entry's fourth word
+}
+__global__ __launch_bounds__(256) void k_hull_finish(const uint32_t *__restrict__ regular, float4 *__restrict__ hull) {
+  const unsigned k = blockIdx.x * 256u + threadIdx.x;
+  const f3 n = hull_direction(k);
+  const uint32_t o = reinterpret_cast<const uint32_t *>(hull)[4u * k + 3u];  // k_hull_support's maximum, 0: no event voxel
+  const uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+  float h = INFINITY;
+  if (o != 0u && *regular != 0u) h = (__uint_as_float(b) + ((fmaxf(n.x, 0.0f) + fmaxf(n.y, 0.0f)) + fmaxf(n.z, 0.0f))) + kHullSlack;
+  hull[k] = make_float4(n.x, n.y, n.z, h);
+}
+hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, int X, int Y, int Z, hipStream_t s) {
+  (void)X;
+  const hipError_t e = hipMemsetAsync(hull, 0, (size_t)kHullPlanes * sizeof(float4), s);
+  if (e != hipSuccess) return e;
+  const int n_rows = Y * Z;  // (below 2^31: kHullMaxDim)
+  // the running maxima sit in the entries' fourth words (stride 4 words)
+  hipLaunchKernelGGL(k_hull_support, dim3((unsigned)kHullPlanes / 256u, ((unsigned)n_rows + (unsigned)kHullRows - 1u) / (unsigned)kHullRows), dim3(256), 0, s, ends, Y, n_rows,
+                     reinterpret_cast<uint32_t *>(hull));
+  hipLaunchKernelGGL(k_hull_finish, dim3((unsigned)kHullPlanes / 256u), dim3(256), 0, s, regular, hull);
   return hipGetLastError();
 }
 

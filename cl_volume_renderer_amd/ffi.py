@@ -364,6 +364,9 @@ _PROTOTYPES = [
     ("clwh_debug_start_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_start_cert_dmin", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     ("clwh_debug_hit_records", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    ("clwh_debug_hull_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("clwh_debug_hull_cert_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    ("clwh_debug_hull_codes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("clwh_strerror", C.c_char_p, [C.c_int]),
     ("clwh_last_hip_error", C.c_int, []),
     ("clwh_version", C.c_char_p, []),
@@ -405,6 +408,14 @@ def parse_tf(source: str) -> Tf:
     tf = Tf()
     _check(lib().clwh_tf_parse(source.encode(), C.byref(tf)), "clwh_tf_parse")
     return tf
+
+
+def hull_cert_bound(X: int, Y: int, Z: int):
+    """(delta0, slack): the smallest direction . n_k a hull certificate needs in an X x Y x Z volume (2.0: never granted), and the slack
+    every entry of the hull table includes"""
+    v = (C.c_float * 2)()
+    _check(lib().clwh_debug_hull_cert_bound(X, Y, Z, v), "clwh_debug_hull_cert_bound")
+    return float(v[0]), float(v[1])
 
 
 def start_cert_dmin(X: int, Y: int, Z: int) -> float:
@@ -1058,6 +1069,26 @@ class Context:
         out = np.empty((info[2], info[1], info[0]), np.uint8)
         _check(lib().clwh_debug_start_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_start_table")
         return out
+
+    def hull_table(self):
+        """the hull-certificate table of the scene data this context rendered from last: float32 [planes][4] = unit normal n_k, h_k
+        (every corner c of every event voxel has n_k . c <= h_k); None when it was not built"""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_hull_table(self.h, None, C.c_uint64(0), info), "clwh_debug_hull_table")
+        if not info[3]:
+            return None
+        out = np.empty((info[1], 4), np.float32)
+        _check(lib().clwh_debug_hull_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_hull_table")
+        return out
+
+    def hull_codes(self):
+        """per hit of the camera this context rendered last (hit_records' order): uint32, 0 = no plane, else 1 + plane index in bits
+        0-12 and the margin in 1/256 voxels (rounded down) in bits 16-31 (clwh_debug_hull_codes)"""
+        n = C.c_uint32(0)
+        _check(lib().clwh_debug_hull_codes(self.h, None, C.c_uint64(0), C.byref(n)), "clwh_debug_hull_codes")
+        out = np.empty(int(n.value), np.uint32)
+        _check(lib().clwh_debug_hull_codes(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), C.byref(n)), "clwh_debug_hull_codes")
+        return out[:int(n.value)]
 
     def hit_records(self):
         """the hit records of the camera this context rendered last: uint32 [n_hits][16] (clwh_debug_hit_records)"""

@@ -1000,6 +1000,19 @@ int clwh_debug_start_cert_dmin(int32_t X, int32_t Y, int32_t Z, float *dmin_out)
  * 64 bytes per hit: float origin[3], direction[3], normal[3]; uint32 colour; int64 cache entry; uint32 x | y << 16, pixel slot,
  * start-certificate byte, 0.  CLWH_ERR_BAD_ARGS: no camera yet */
 int clwh_debug_hit_records(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out);
+/* the hull-certificate table of the derived scene data the context rendered from last: info_out = {cells of the
+ * octahedral grid along one axis, planes, 0, 1 if the table was built else 0}; host_out (may be null: the shape alone) receives four
+ * floats per plane k = j * grid + i: the unit normal n_k (the octahedral decode of the centre of cell (i, j)) and h_k, above the largest
+ * n_k . c over the eight corners c of every event voxel by the slack clwh_debug_hull_cert_bound names, within 2^-9; +inf: no plane.
+ * Nothing is written when the table was not built.  CLWH_ERR_BAD_ARGS: the context holds no scene data */
+int clwh_debug_hull_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
+/* out[0]: the smallest direction . n_k with which a hull certificate is granted in a volume of X x Y x Z voxels (a multiple of 1/64;
+ * 2: never); out[1]: the slack every h_k of the table includes */
+int clwh_debug_hull_cert_bound(int32_t X, int32_t Y, int32_t Z, float out[2]);
+/* per hit of the camera the context rendered last (the order of clwh_debug_hit_records), one uint32: 0 = no plane of the hull table has
+ * the hit's start point P = (origin + direction) + 2 normal in front of it (or there is no table); else bits 0-12 = 1 + the plane's
+ * index, bits 16-31 = n_k . P - h_k in 1/256 voxels, rounded down, saturating.  CLWH_ERR_BAD_ARGS: no camera yet */
+int clwh_debug_hull_codes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out);
 const char *clwh_strerror(int status);
 int clwh_last_hip_error(void);
 const char *clwh_version(void);
