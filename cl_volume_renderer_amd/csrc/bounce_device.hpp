@@ -125,14 +125,7 @@ __device__ __forceinline__ f3 hull_direction(unsigned k) {
   const float r = __builtin_amdgcn_rsqf((x * x + y * y) + z * z);
   return f3{x * r, y * r, z * r};
 }
-// `code`: 1 + the index of a plane the first leg's start point lies in front of (k_primary), 0: none; `d` the leg's direction, `delta0`
-// hull_cert_delta0 (clwh_internal.hpp).  The far-face crawl and NaN directions as in certify_exit.
-__device__ __forceinline__ bool hull_certificate(uint32_t code, f3 d, float delta0) {
-  const f3 n = hull_direction(code - 1u);
-  const float dmin = fminf(fminf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
-  const float dsum = d.x + d.y + d.z;
-  return code != 0u && dot3(d, n) >= delta0 && dmin >= 0.0009765625f && dsum == dsum;
-}
+// (the test itself: k_bounce's opening half.  The far-face crawl and NaN directions as in certify_exit.)
 __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
   int away;
   return certify_exit(a, p, d, budget, away);
@@ -184,6 +177,8 @@ template <> struct BounceStatsT<false> {
   __device__ void swap_point() {}
   __device__ void start_cert(bool, bool) {}
   __device__ void hull_cert(bool, bool, bool) {}
+  __device__ void hull_more(bool, bool, bool, bool) {}
+  __device__ void hull_fired(bool, bool) {}
   __device__ void march_end(uint32_t *, int) {}
   template <bool TWO_RAYS> __device__ void flush(uint32_t *) {}
 };
@@ -241,11 +236,26 @@ template <> struct BounceStatsT<true> {
     hull_both += (uint32_t)__popcll(__ballot(both));
     hull_open = hull_open || granted;
   }
+  // item 13's classes, verified the same way: 0 first legs granted after a few literal steps, 1 rebounds granted at once, 2 rebounds
+  // granted after a few literal steps; per class tried (deferred: armed) and granted (deferred: got in front within kHullDeferSteps)
+  uint32_t more_tried[3] = {0, 0, 0}, more_granted[3] = {0, 0, 0};
+  int more_open = -1;  // this lane's current march holds a certificate of that class
+  __device__ __forceinline__ void hull_more(bool rebound_tried, bool rebound_granted, bool armed, bool first_leg) {
+    more_tried[0] += (uint32_t)__popcll(__ballot(armed && first_leg)); more_tried[2] += (uint32_t)__popcll(__ballot(armed && !first_leg));
+    more_tried[1] += (uint32_t)__popcll(__ballot(rebound_tried)); more_granted[1] += (uint32_t)__popcll(__ballot(rebound_granted));
+    if (rebound_granted) more_open = 1;
+  }
+  __device__ __forceinline__ void hull_fired(bool fired, bool first_leg) {
+    more_granted[0] += (uint32_t)__popcll(__ballot(fired && first_leg)); more_granted[2] += (uint32_t)__popcll(__ballot(fired && !first_leg));
+    if (fired) more_open = first_leg ? 0 : 2;
+  }
   __device__ __forceinline__ void march_end(uint32_t *counters, int ev) {
     if (start_open && ev != EV_EXIT) atomicAdd(&counters[CTR_START_WRONG], 1u);
     if (hull_open && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_WRONG], 1u);
+    if (more_open >= 0 && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_DEFER + 3 * more_open + 2], 1u);
     start_open = false;
     hull_open = false;
+    more_open = -1;
   }
   // lane 0 of a wave that ends
   template <bool TWO_RAYS> __device__ __forceinline__ void flush(uint32_t *counters) {
@@ -258,6 +268,7 @@ template <> struct BounceStatsT<true> {
     atomicAdd(&counters[CTR_CERT_GRANTED], cert_granted); atomicAdd(&counters[CTR_STEP_IDLE], step_idle);
     atomicAdd(&counters[CTR_START_TRIED], start_tried); atomicAdd(&counters[CTR_START_GRANTED], start_granted);
     atomicAdd(&counters[CTR_HULL_TRIED], hull_tried); atomicAdd(&counters[CTR_HULL_GRANTED], hull_granted); atomicAdd(&counters[CTR_HULL_BOTH], hull_both);
+    for (int k = 0; k < 3; ++k) { atomicAdd(&counters[CTR_HULL_DEFER + 3 * k], more_tried[k]); atomicAdd(&counters[CTR_HULL_DEFER + 3 * k + 1], more_granted[k]); }
   }
 };
 using BounceStats = BounceStatsT<kBounceStats>;

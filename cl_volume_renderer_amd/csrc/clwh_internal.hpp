@@ -62,6 +62,9 @@ enum : uint32_t {
   CTR_HULL_TRIED, CTR_HULL_GRANTED, CTR_HULL_BOTH, CTR_HULL_WRONG,  // k_bounce only: hull certificates; both: legs either proof grants
   CTR_STATS_END,
   CTR_QUEUE_STRIDE = 32,  // head of unit queue q: slot CTR_QUEUE_STRIDE * (q + 1), every head on its own 128-byte line
+  // k_bounce only, behind the last queue head: tried / granted / wrong of the hull certificates item 13 added, three slots per class --
+  // first legs granted after a few literal steps, rebounds granted at once, rebounds granted after a few literal steps
+  CTR_HULL_DEFER = CTR_QUEUE_STRIDE * 9, CTR_HULL_DEFER_END = CTR_HULL_DEFER + 9,
 };
 struct RenderArgs {
   int32_t X, Y, Z;
@@ -87,6 +90,10 @@ struct RenderArgs {
   const float4 *hull;
   uint32_t *hull_codes;
   float hull_delta0;       // a first leg with such a plane is granted if direction . n_k is at least this (hull_cert_delta0 below)
+  // ... and (hull_planes, a second word per hit) 1 + the index of the best plane the search found even when the start point lies up to
+  // kHullDeferDeficit BEHIND it, with the signed margin in bits 16-23 (k_primary; clwh_debug_hull_planes); nullptr: CLWH_TUNE_HULL_DEFER=0, or no table
+  uint32_t *hull_planes;
+  float hull_defer_delta0;  // a march that gets in front of such a plane within kHullDeferSteps steps is granted there if direction . n_k is at least this
   int32_t NBX, NBY;
   const uint32_t *env;     // RGBA8 packed, row-major
   int32_t env_w, env_h;
@@ -243,6 +250,48 @@ inline float hull_cert_delta0(int X, int Y, int Z) {
     const double delta0 = (double)k / 64.0;
     double t = 0.0;
     for (int step = 0; step < 70 - 5 && t <= reach; ++step) {
+      const double m = (double)(long long)(t * delta0 / 1.7320508075688772) - 2.0;
+      const double bound = m > cap ? cap : m;
+      t += bound < 1.0 ? 1.0 : bound;
+    }
+    if (t > reach) return (float)delta0;
+  }
+  return 2.0f;
+}
+// Deferred grants and rebounds.  The theorem above asks nothing of where a march comes from: a position in front of
+// plane k, a constant direction with d . n_k >= delta0, and `budget` steps left carry the march out of the volume if the recurrence gets
+// there in budget - 5 steps.  k_bounce applies it to every march of fresh budget 70 that starts from a bounce (never to the
+// continuation of a march that ran out of steps), first legs and rebounds from secondary hits alike:
+//   start   the march's first position, (hit position + incoming direction) + 2 * the bounce's normal, in binary32;
+//   P       the first legs' start point, rebuilt from the lane's copy of the hit with k_primary's own operations (origin + direction, then
+//           + normal * 2: the same bits);
+//   m_q     the margin k_primary stored for P against plane k, rounded DOWN to a multiple of 1 / kHullMarginScale (hull_planes);
+//   m       = m_q + n_k . (start - P), the march's own margin.  For a first leg start == P bit for bit and m == m_q.
+// (a) m >= 0 and d . n_k >= hull_cert_delta0: the theorem as it stands, granted before the first step.
+// (b) 0 < -m <= kHullDeferDeficit and d . n_k >= hull_defer_delta0: the lane marches literally and counts its path in the low field of
+//     `march` (one add of the step byte's value per step; the step itself is max(value, 0.5), so the count never exceeds the path).
+//     Once the count reaches ceil(-m / d . n_k) the position is start + t * d with t * (d . n_k) >= -m: in front of the plane.  If no
+//     event has ended the march and it has taken at most kHullDeferSteps steps, at least 70 - kHullDeferSteps are left, and the
+//     theorem holds with hull_defer_delta0, the same recurrence over 70 - 5 - kHullDeferSteps steps.  A lane that gets there later
+//     drops the claim and asks the macro-cell table like any other.
+// Rounding budget of m, in voxels, for coordinates up to kHullMaxDim = 2^11 (differences and partial sums below 2^13, half an ulp
+// at most 2^-12): m_q is rounded down, which only errs to the safe side; P is bit-identical to k_primary's, whose own n_k . P and the
+// table's maximum are in kHullSlack already (2 x 2^-10); the three subtractions start - P (3 x 2^-12, times |n| <= 1), three
+// products, two additions and the addition of m_q (6 x 2^-12): below 2^-9 + 2^-10 in all.  ceil(-m / d . n_k) is taken from a reciprocal
+// good to 2^-22 and widened by 2^-19: it never falls below the quotient.  kHullSlack = 2^-4 has to hold 2 x 2^-10 (support and n_k . P),
+// 2^-5 (the march's 70 additions -- a deferred grant's literal steps are among them), 2^-10 (|n_k| off by 2^-22 at 2^12) and now 3 x 2^-10:
+// 2^-5 + 6 x 2^-10 < 0.038 of 0.0625.  It fits; the slack is not touched and no guard is subtracted.
+// The direction guards are item 12's: no NaN, min |component| >= 2^-10.  A NaN in start or P makes m a NaN, which fails both tests.
+constexpr int kHullDeferSteps = 3;            // J: the most literal steps a march may have taken when a deferred grant fires
+constexpr float kHullDeferDeficit = 1.5f;     // D: planes further than this in front of the start point are not worth waiting for
+constexpr int kHullMarginScale = 16;          // the stored margin's grid: 1/16 voxel, eight bits signed (-8 .. +7.9375, clamped)
+inline float hull_defer_delta0(int X, int Y, int Z) {
+  const double longest = (double)(X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z));
+  const double reach = 1.7320508075688772 * (longest + 1.0), cap = (double)start_cert_cap(X, Y, Z);
+  for (int k = 1; k <= 64; ++k) {
+    const double delta0 = (double)k / 64.0;
+    double t = 0.0;
+    for (int step = 0; step < 70 - 5 - kHullDeferSteps && t <= reach; ++step) {
       const double m = (double)(long long)(t * delta0 / 1.7320508075688772) - 2.0;
       const double bound = m > cap ? cap : m;
       t += bound < 1.0 ? 1.0 : bound;

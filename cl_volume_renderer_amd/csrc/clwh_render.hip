@@ -264,6 +264,7 @@ static int describe_launch(const clwh_ctx *ctx, const clwh_render_desc *d, Rende
   a.cert_hint = t.cert_hint;
   a.start_cert_dmin = start_cert_dmin(a.X, a.Y, a.Z);
   a.hull_delta0 = hull_cert_delta0(a.X, a.Y, a.Z);
+  a.hull_defer_delta0 = hull_defer_delta0(a.X, a.Y, a.Z);
   return CLWH_OK;
 }
 
@@ -305,6 +306,8 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
   CLWH_TRY(p.pix_slot.reserve(ctx->stream, slots * sizeof(uint32_t)));
   CLWH_TRY(p.hits.reserve(ctx->stream, slots * sizeof(HitRec)));
   if (a.hull) CLWH_TRY(p.hull_codes.reserve(ctx->stream, slots * sizeof(uint32_t)));
+  const bool defer = a.hull && ctx->tune.hull_defer != 0;
+  if (defer) CLWH_TRY(p.hull_planes.reserve(ctx->stream, slots * sizeof(uint32_t)));
   CLWH_TRY(s.counters.reserve(ctx->stream, PassScratch::kCounters * sizeof(uint32_t)));
   bool fresh_flags = false;
   CLWH_TRY(s.sticky_flags.reserve(ctx->stream, 64, &fresh_flags));
@@ -313,6 +316,7 @@ static int ensure_primary_hits(clwh_ctx *ctx, const clwh_render_desc *d, RenderA
   a.pix_slot = p.pix_slot.as<uint32_t>();
   a.hits = p.hits.as<HitRec>();
   a.hull_codes = a.hull ? p.hull_codes.as<uint32_t>() : nullptr;
+  a.hull_planes = defer ? p.hull_planes.as<uint32_t>() : nullptr;
   a.counters = s.counters.as<uint32_t>();
 
   PrimaryHits::Key key;
@@ -429,7 +433,7 @@ static int plan_voxel_grants(clwh_ctx *ctx, RenderArgs &a) {
 
 #ifdef CLVR_BOUNCE_STATS  // experiment builds only (CLVR_EXTRA_HIPCC_FLAGS=-DCLVR_BOUNCE_STATS): scheduling statistics of the launch
 static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
-  uint32_t h[CTR_STATS_END];
+  uint32_t h[CTR_HULL_DEFER_END];
   HIP_TRY(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   auto per = [&](int sum, int n) { return h[n] ? (double)h[sum] / h[n] : 0.0; };
@@ -447,6 +451,10 @@ static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
   std::fprintf(stderr, "[bounce stats] hull certificates tried/granted/wrong=%u/%u/%u, of the granted the octant proof grants %u; either proof grants %u first legs; delta0=%.6f\n",
                h[CTR_HULL_TRIED], h[CTR_HULL_GRANTED], h[CTR_HULL_WRONG], h[CTR_HULL_BOTH], h[CTR_START_GRANTED] + h[CTR_HULL_GRANTED] - h[CTR_HULL_BOTH],
                (double)a.hull_delta0);
+  const uint32_t *m = h + CTR_HULL_DEFER;
+  std::fprintf(stderr, "[bounce stats] hull certificates tried/granted/wrong: first legs deferred=%u/%u/%u rebounds at once=%u/%u/%u rebounds deferred=%u/%u/%u; "
+               "J=%d D=%.4g defer_delta0=%.6f; look-ups=%u\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], kHullDeferSteps, (double)kHullDeferDeficit,
+               (double)a.hull_defer_delta0, h[CTR_CERT_LANES] - ((CLVR_BOUNCE_STATS + 0) == 2 ? m[1] + m[7] : 0u));
   return CLWH_OK;
 }
 #endif
@@ -654,6 +662,32 @@ int clwh_debug_hull_cert_bound(int32_t X, int32_t Y, int32_t Z, float out[2]) {
   if (!out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
   out[0] = hull_cert_delta0(X, Y, Z);
   out[1] = kHullSlack;
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_defer_bound(int32_t X, int32_t Y, int32_t Z, float out[4]) {
+  if (!out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
+  out[0] = hull_defer_delta0(X, Y, Z);
+  out[1] = (float)kHullDeferSteps;
+  out[2] = kHullDeferDeficit;
+  out[3] = (float)kHullMarginScale;
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_planes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out) {
+  if (!ctx || !n_hits_out) return CLWH_ERR_INVALID_VALUE;
+  PrimaryHits &p = ctx->primary;
+  if (!p.valid || !p.hits.ptr || !ctx->pass.counters.ptr) return CLWH_ERR_BAD_ARGS;  // no camera rendered yet
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(n_hits_out, ctx->pass.counters.as<uint32_t>() + CTR_HITS, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (!host_out) return CLWH_OK;  // the count alone
+  const bool built = ctx->scene && ctx->scene->hull_table && ctx->tune.hull_defer != 0 && p.hull_planes.ptr;
+  const size_t bytes = (size_t)*n_hits_out * sizeof(uint32_t);
+  if (capacity < bytes || (built && p.hull_planes.bytes < bytes)) return CLWH_ERR_SIZE_MISMATCH;
+  if (!built) { std::memset(host_out, 0, bytes); return CLWH_OK;}  // no table, or CLWH_TUNE_HULL_DEFER=0: no hit has the word
+  HIP_TRY(hipMemcpyAsync(host_out, p.hull_planes.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return CLWH_OK;
 }
 

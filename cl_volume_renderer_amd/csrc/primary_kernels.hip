@@ -116,6 +116,17 @@ __global__ __launch_bounds__(64) void k_primary(const RenderArgs a) {
       // bits 0-12: 1 + the plane's index; bits 16-31: the margin in 1/256 voxels, rounded down (k_bounce needs its sign only)
       if (margin >= 0.0f) code = ((uint32_t)(bj * kHullGrid + bi) + 1u) | ((uint32_t)fminf(floorf(margin * 256.0f), 65535.0f) << 16);
       a.hull_codes[h] = code;
+      // the second word: the same plane even when P lies up to kHullDeferDeficit behind it, with the signed margin
+      // rounded down on a grid of 1 / kHullMarginScale (k_bounce grants a march once it has got in front); 0: a NaN in P (margin stays
+      // -inf: the comparison fails), or no plane that near
+      if (a.hull_planes) {
+        uint32_t word = 0u;
+        if (margin >= -kHullDeferDeficit) {
+          const int q = (int)fminf(floorf(margin * (float)kHullMarginScale), 127.0f);  // (at least -kHullDeferDeficit * kHullMarginScale >= -128)
+          word = ((uint32_t)(bj * kHullGrid + bi) + 1u) | (((uint32_t)q & 0xFFu) << 16);
+        }
+        a.hull_planes[h] = word;
+      }
     }
     q3.x = x | (y << 16); q3.y = pslot; q3.z = start_free; q3.w = 0u;
     uint4 *dst = reinterpret_cast<uint4 *>(&a.hits[h]);

@@ -17,7 +17,7 @@
 //                                                a hit carries the start-certificate byte of the voxel
 //                                                its distribution rays start from
 //                                                and, beside its record, the plane of the hull table that
-//                                                start point lies furthest in front of
+//                                                start point lies furthest in front of (or least behind)
 //   k_bounce   (every launch, 1..64 seeds)       persistent waves pull (hit, seed) items from eight         this file
 //                                                work queues; each lane runs the sample's two               (k_bounce2, two rays per
 //                                                distribution rays as a small state machine; idle           lane: bounce_two_rays.hpp)
@@ -87,14 +87,16 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
                C_NORMAL_X, C_NORMAL_Y, C_NORMAL_Z,
                C_ENTRY_LO,
                C_ENTRY_HI,  // bits 0-7: the entry's (a stored entry is -1, -2 or below 2^34: bit 7 is its sign); bits 8-20: the hit's hull-certificate code;
-                            // bits 24-31: the hit's start-certificate byte
+                            // bits 24-31: the hit's start-certificate byte.  With deferred hull grants (hull_defer below: the scene has a hull
+                            // table, so no axis is longer than 2^11 and an entry is -1, -2 or below 2^33) the entry's keep bits 0-2, bit 2 its
+                            // sign; the code moves to bits 3-15 and bits 16-23 hold the signed margin of the hit's plane in 1/16 voxels
                C_PIXEL, C_HIT, C_SEED,
                C_FIX,  // (fix + 2) << 2 | npend; fix: fix-up record of the sample (-1: none, -2: dropped, the buffer overflowed),
                        // npend: pending environment terms written to it
                C_BV_R, C_BV_G, C_BV_B, C_FIELDS };
   __shared__ uint32_t cold[C_FIELDS][kBounceThreads];
 #define COLD(f) cold[f][threadIdx.x]
-#define COLD_ENTRY_HI() ((uint32_t)((int32_t)(COLD(C_ENTRY_HI) << 24) >> 24))
+#define COLD_ENTRY_HI() ((uint32_t)((int32_t)(COLD(C_ENTRY_HI) << (32 - entry_hi_bits)) >> (32 - entry_hi_bits)))
   // path state; energies and colour carry over from distribution ray 1 into ray 2 (SURVEY "hard parts")
   Ray ray{{0, 0, 0}, {0, 0, 0}};
   float atten = 0.0f, r_energy = 0.0f, g_energy = 0.0f, b_energy = 0.0f;
@@ -107,8 +109,10 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // before its next certificate look-up can succeed, see certify_exit): one add per step moves both, `no steps left` is one
   // unsigned compare, and the march may ask again once bit 23 is set.  (The distance is at most 126 cells, a march covers at most
   // 70 x 127 voxels: neither field reaches its neighbour.)
+  // Bit 31, kArmed: the march waits for a deferred hull grant (opening half); its low field then counts down the path after which
+  // its position is in front of the hit's plane, and the certificate phase grants it without a look-up.
   uint32_t march = 0u;
-  constexpr uint32_t kOneStep = 1u << 24, kCertReady = 1u << 23;
+  constexpr uint32_t kOneStep = 1u << 24, kCertReady = 1u << 23, kArmed = 1u << 31;
   const bool cert_hint = a.cert_hint != 0;
   const int cert_min_lanes = a.cert_min_lanes;
   // a lane asks for an exit certificate when its next step is at least this long (wave-uniform)
@@ -116,6 +120,10 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // first legs ask the hit's start-certificate byte: long launches only (launch_bounce); tables with `gradient` rules have no such table
   const bool start_cert = !USE_GRAD && a.cert_min_step != 0;
   const bool hull_cert = start_cert && a.hull_codes != nullptr;  // ... and the hit's hull-certificate code
+  // ... and marches that start behind the hit's plane, or from a secondary hit, ask it too (CLWH_TUNE_HULL_DEFER=0: no)
+  const bool hull_defer = hull_cert && a.hull_planes != nullptr;
+  const int entry_hi_bits = hull_defer ? 3 : 8;  // C_ENTRY_HI's layout (wave-uniform)
+  const uint32_t *hull_words = hull_defer ? a.hull_planes : a.hull_codes;  // the word per hit the refill reads
   bool exhausted = false;  // wave-uniform: the queue has no more items
   BounceStats stats;
 
@@ -143,8 +151,10 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
               const unsigned q = vol.template step_marched<SMALL>(ray.origin.x, ray.origin.y, ray.origin.z);
               sd = (int)(q & 0x7Fu);
               if (q & 0x80u) st = ST_EVENT + EV_HIT_COLOR_PENDING;
-              else if (march < kOneStep) st = ST_EVENT + EV_NONE;
-              else if (sd >= cert_at && (march & kCertReady)) st = ST_CERT;  // far from every surface: can the rest of this march be proven to exit?
+              else if ((march & ~kArmed) < kOneStep) st = ST_EVENT + EV_NONE;
+              // far from every surface: can the rest of this march be proven to exit?  (An armed lane asks as soon as it has covered its
+              // path, however short its next step: its flag is larger than every threshold.)
+              else if (((march & kArmed) | (uint32_t)sd) >= (uint32_t)cert_at && (march & kCertReady)) st = ST_CERT;
             } else {
               st = ST_EVENT + EV_CHECK;
             }
@@ -170,9 +180,17 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         const int n_cert = __popcll(__ballot(st == ST_CERT));
         if (n_cert != 0 && (n_cert >= cert_min_lanes || __popcll(__ballot(st == ST_MARCH)) < a.step_min_lanes)) {
           stats.cert_begin(st, n_cert);
+          // deferred hull grant: the lane has covered the path that puts it in front of its hit's plane; with at most kHullDeferSteps
+          // steps taken the theorem holds from here (hull_defer_delta0, clwh_internal.hpp) -- no look-up.  Later than that it is a march
+          // like any other.
+          const bool fired = !USE_GRAD && st == ST_CERT && (march & kArmed) != 0u && (march & ~kArmed) >= (uint32_t)(70 - kHullDeferSteps) * kOneStep;
+          stats.hull_fired(fired, i == 8);
           if (st == ST_CERT) {
+            if (!USE_GRAD) march &= ~kArmed;  // (no lane of a USE_GRAD instance is ever armed)
             int away;
-            if (certify_exit(a, ray.origin, ray.direction, (int)(march >> 24), away)) {
+            if (fired && !kStartCertVerify) {
+              st = ST_EVENT + EV_EXIT;
+            } else if (certify_exit(a, ray.origin, ray.direction, (int)(march >> 24), away)) {
               st = ST_EVENT + EV_EXIT;  // the march WOULD end in Exit_volume; only its direction matters from here on
             } else {
               // it tries again at its next step that is long enough (trying less often -- only once the step has doubled, or grown by
@@ -208,7 +226,7 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             ev = pending ? EV_HIT_COLOR_PENDING : EV_HIT;
             break;
           }
-          if (march < kOneStep) { ev = EV_NONE; break; }
+          if ((march & ~kArmed) < kOneStep) { ev = EV_NONE; break; }
           ray.origin = ray.origin + ray.direction * fmaxf((float)next_sd, 0.5f);
           march -= kOneStep;
         }
@@ -359,7 +377,9 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             if (granted) {
               COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
               COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
-              COLD(C_ENTRY_LO) = q2.z; COLD(C_ENTRY_HI) = (q2.w & 0xFFu) | (hull_cert ? (a.hull_codes[h] & 0x1FFFu) << 8 : 0u) | (q3.z << 24);
+              COLD(C_ENTRY_LO) = q2.z;
+              const uint32_t plane = hull_cert ? hull_words[h] : 0u;  // (one layout or the other: wave-uniform masks and shift)
+              COLD(C_ENTRY_HI) = (q2.w & ((1u << entry_hi_bits) - 1u)) | ((plane & 0x1FFFu) << entry_hi_bits) | (plane & (hull_defer ? 0x00FF0000u : 0u)) | (q3.z << 24);
               COLD(C_PIXEL) = q3.x;
               COLD(C_HIT) = h;
               COLD(C_SEED) = (uint32_t)a.seeds[s];
@@ -388,6 +408,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
     // ---- event phase, opening half: the bounce is one shared block, then the march's first SDF read ---------
     bool sc_tried = false, sc_granted = false;  // this lane's first leg asked for / holds a start certificate
     bool hc_tried = false, hc_granted = false;  // ... a hull certificate
+    bool rb_tried = false, rb_granted = false;  // this lane's rebound from a secondary hit asked for / holds a hull certificate
+    uint32_t armed_path = 0u;                   // != 0: this lane's march may be granted once it has covered this path (deferred grant)
     if (st >= ST_EVENT) {
       const int ev = st - ST_EVENT;
       bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
@@ -449,31 +471,50 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
             sc_tried = true;
             const uint32_t word = COLD(C_ENTRY_HI);
             sc_granted = start_certificate(word >> 24, nr.direction, a.start_cert_dmin);
-            // Hull certificate.  k_primary has found a plane {x : n_k . x = h_k} with every corner of every event voxel behind it and
-            // the start point in front of it (k_hull_*, scene_kernels.hip); a leg with direction . n_k >= hull_cert_delta0
-            // (clwh_internal.hpp: the proof) moves away from every event voxel linearly with its path, the steps grow with that
-            // distance, and it provably leaves within its 70 steps.  The proof that fits a leg leaving a convex surface, where the
-            // octant's box nearly always holds the object.
-            if (hull_cert) {
-              hc_tried = (word & 0x001FFF00u) != 0u;
-              hc_granted = hull_certificate((word >> 8) & 0x1FFFu, nr.direction, a.hull_delta0);
-            }
           }
+        }
+        // Hull certificate.  k_primary has found a plane {x : n_k . x = h_k} with every corner of every event voxel behind it
+        // (k_hull_*, scene_kernels.hip); a march that starts in front of it with direction . n_k >= hull_cert_delta0
+        // (clwh_internal.hpp: the proof) moves away from every event voxel linearly with its path, the steps grow with that
+        // distance, and it provably leaves within its 70 steps.  The proof that fits a leg leaving a convex surface, where the
+        // octant's box nearly always holds the object.  First legs start at the point P the plane was chosen for; with hull_defer a
+        // rebound from a secondary hit asks the same plane with its own margin, m_P + n_k . (start - P), and a march that starts up to
+        // kHullDeferDeficit behind the plane is armed: it is granted in the certificate phase once it has got in front.
+        if (hull_cert && (hull_defer || !from_hit)) {
+          const uint32_t word = COLD(C_ENTRY_HI);
+          const uint32_t code = (word >> entry_hi_bits) & 0x1FFFu;
+          const f3 n = hull_direction(code - 1u);
+          const float dn = dot3(nr.direction, n);
+          const f3 dir = nr.direction;
+          const bool dir_ok = fminf(fminf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z)) >= 0.0009765625f && (dir.x + dir.y) + dir.z == (dir.x + dir.y) + dir.z;
+          float m = hull_defer ? (float)((int32_t)(word << 8) >> 24) * (1.0f / (float)kHullMarginScale) : 0.0f;
+          if (from_hit) {
+            const f3 p = f3{__uint_as_float(COLD(C_START_X)), __uint_as_float(COLD(C_START_Y)), __uint_as_float(COLD(C_START_Z))} +
+                         f3{__uint_as_float(COLD(C_NORMAL_X)), __uint_as_float(COLD(C_NORMAL_Y)), __uint_as_float(COLD(C_NORMAL_Z))} * 2.0f;
+            m = m + dot3(n, f3{nr.origin.x - p.x, nr.origin.y - p.y, nr.origin.z - p.z});
+          }
+          const bool tried = code != 0u, granted = tried && dir_ok && m >= 0.0f && dn >= a.hull_delta0;
+          if (from_hit) { rb_tried = tried; rb_granted = granted; }
+          else { hc_tried = tried && m >= 0.0f; hc_granted = granted; }
+          if (tried && dir_ok && !sc_granted && m < 0.0f && m >= -kHullDeferDeficit && dn >= a.hull_defer_delta0)
+            armed_path = (uint32_t)ceilf(-m * __builtin_amdgcn_rcpf(dn) * (1.0f + 0x1p-19f));  // at least -m / dn, at most 8 x 64 + 1
         }
         ray = nr;
       }
 
-      if ((sc_granted || hc_granted) && !kStartCertVerify) {
+      if ((sc_granted || hc_granted || rb_granted) && !kStartCertVerify) {
         st = ST_EVENT + EV_EXIT;  // the next closing half takes it from here
       } else {
         // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
         sd = (int)(vol.template step_i<SMALL>(f2i(ray.origin.x), f2i(ray.origin.y), f2i(ray.origin.z)) & 0x7Fu);
         march = 70u * kOneStep + kCertReady;
+        if (armed_path != 0u) march = kArmed + 70u * kOneStep + kCertReady - armed_path;
         st = ST_MARCH;
       }
     }
     stats.start_cert(sc_tried, sc_granted);
     stats.hull_cert(hc_tried, hc_granted, hc_granted && sc_granted);
+    stats.hull_more(rb_tried, rb_granted, armed_path != 0u && st == ST_MARCH, i == 8);
   }
 #undef COLD_ENTRY_HI
 #undef COLD

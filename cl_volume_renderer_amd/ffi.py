@@ -367,6 +367,8 @@ _PROTOTYPES = [
     ("clwh_debug_hull_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_hull_cert_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     ("clwh_debug_hull_codes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    ("clwh_debug_hull_planes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    ("clwh_debug_hull_defer_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     ("clwh_strerror", C.c_char_p, [C.c_int]),
     ("clwh_last_hip_error", C.c_int, []),
     ("clwh_version", C.c_char_p, []),
@@ -416,6 +418,14 @@ def hull_cert_bound(X: int, Y: int, Z: int):
     v = (C.c_float * 2)()
     _check(lib().clwh_debug_hull_cert_bound(X, Y, Z, v), "clwh_debug_hull_cert_bound")
     return float(v[0]), float(v[1])
+
+
+def hull_defer_bound(X: int, Y: int, Z: int):
+    """(delta0, J, D, scale): the smallest direction . n_k with which a march that got in front of its plane within J literal steps is
+    granted in an X x Y x Z volume, the deficit limit D in voxels, and the grid of the stored margins (1 / scale voxels)"""
+    v = (C.c_float * 4)()
+    _check(lib().clwh_debug_hull_defer_bound(X, Y, Z, v), "clwh_debug_hull_defer_bound")
+    return float(v[0]), int(v[1]), float(v[2]), int(v[3])
 
 
 def start_cert_dmin(X: int, Y: int, Z: int) -> float:
@@ -1088,6 +1098,15 @@ class Context:
         _check(lib().clwh_debug_hull_codes(self.h, None, C.c_uint64(0), C.byref(n)), "clwh_debug_hull_codes")
         out = np.empty(int(n.value), np.uint32)
         _check(lib().clwh_debug_hull_codes(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), C.byref(n)), "clwh_debug_hull_codes")
+        return out[:int(n.value)]
+
+    def hull_planes(self):
+        """per hit, hull_codes' order: uint32, 0 = no plane within D voxels, else 1 + plane index in bits 0-12 and the signed margin in
+        1/16 voxels (rounded down, two's complement) in bits 16-23 (clwh_debug_hull_planes)"""
+        n = C.c_uint32(0)
+        _check(lib().clwh_debug_hull_planes(self.h, None, C.c_uint64(0), C.byref(n)), "clwh_debug_hull_planes")
+        out = np.empty(int(n.value), np.uint32)
+        _check(lib().clwh_debug_hull_planes(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), C.byref(n)), "clwh_debug_hull_planes")
         return out[:int(n.value)]
 
     def hit_records(self):

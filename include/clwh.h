@@ -1013,6 +1013,13 @@ int clwh_debug_hull_cert_bound(int32_t X, int32_t Y, int32_t Z, float out[2]);
  * the hit's start point P = (origin + direction) + 2 normal in front of it (or there is no table); else bits 0-12 = 1 + the plane's
  * index, bits 16-31 = n_k . P - h_k in 1/256 voxels, rounded down, saturating.  CLWH_ERR_BAD_ARGS: no camera yet */
 int clwh_debug_hull_codes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out);
+/* the second word per hit, same order: 0 = the start point has a NaN or no plane of the search lies within D
+ * voxels of it, else 1 + the plane's index in bits 0-12 and, in bits 16-23, the signed margin n_k . P - h_k in 1/scale voxels, rounded
+ * down, two's complement, clamped to 127.  All zero without a table or under CLWH_TUNE_HULL_DEFER=0. */
+int clwh_debug_hull_planes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uint32_t *n_hits_out);
+/* out = {the smallest direction . n_k with which a march that has got in front of its plane within J literal steps is granted in a
+ * volume of X x Y x Z voxels (2: never), J, D (voxels), scale} */
+int clwh_debug_hull_defer_bound(int32_t X, int32_t Y, int32_t Z, float out[4]);
 const char *clwh_strerror(int status);
 int clwh_last_hip_error(void);
 const char *clwh_version(void);
