@@ -325,6 +325,12 @@ hipError_t launch_ao(const RenderArgs &a, hipStream_t s);
 hipError_t launch_accum_resolve(const RenderArgs &a, const float4 *accum_all, hipStream_t s);
 hipError_t launch_accum_resolve_tiles(const RenderArgs &a, const float4 *accum, uint32_t *tiles_out, hipStream_t s);
 hipError_t launch_frame_from_tiles(const RenderArgs &a, const uint32_t *tiles_all, hipStream_t s);
+// clwh_debug_device_probe (probe_kernels.hip): words per record of probe `which` ({0, 0}: no such probe), and its launch
+struct ProbeShape {
+  uint32_t in_words, out_words;
+};
+ProbeShape probe_shape(int which);
+hipError_t launch_device_probe(int which, const uint32_t *in, uint64_t n, uint32_t *out, const uint32_t *aux, const int32_t params[4], hipStream_t s);
 // ---- fused SDF build: one breadth-first layer over the active 8x8x8 tiles (sdf_front_kernels.hip)
 struct SdfFrontArgs {
   int8_t *sdf;

@@ -602,6 +602,21 @@ int clwh_ctx_scene_info(clwh_ctx *ctx, uint64_t *scene_id, uint64_t *bytes, int3
   return CLWH_OK;
 }
 
+int clwh_debug_device_probe(clwh_ctx *ctx, int32_t which, clwh_mem *in, uint64_t n, clwh_mem *out, clwh_mem *aux, const int32_t params[4]) {
+  if (!ctx || !in || !out || !params) return CLWH_ERR_INVALID_VALUE;
+  const ProbeShape shape = probe_shape(which);
+  if (shape.in_words == 0u) return CLWH_ERR_INVALID_VALUE;
+  const bool env = which == CLWH_PROBE_ENV_EXACT || which == CLWH_PROBE_ENV_FAST;
+  if (env && (!aux || params[0] < 1 || params[1] < 1)) return CLWH_ERR_INVALID_VALUE;
+  if (n >= (1ull << 31) || in->bytes < n * shape.in_words * 4u || out->bytes < n * shape.out_words * 4u) return CLWH_ERR_SIZE_MISMATCH;
+  // the samplers clamp the texel they choose to [0, w) x [0, h): the image must hold that many words
+  if (env && aux->bytes < (uint64_t)params[0] * (uint64_t)params[1] * 4u) return CLWH_ERR_SIZE_MISMATCH;
+  if (n == 0) return CLWH_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(launch_device_probe(which, (const uint32_t *)in->dptr, n, (uint32_t *)out->dptr, env ? (const uint32_t *)aux->dptr : nullptr, params, ctx->stream));
+  return CLWH_OK;
+}
+
 // the layout of the context's derived scene data
 static PackedLayout scene_layout(clwh_ctx *ctx) {
   std::lock_guard<std::mutex> lock(g_scenes_mutex);

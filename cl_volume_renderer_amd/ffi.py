@@ -36,6 +36,10 @@ MASK_INVERT = 1
 REGION_MASK, REGION_LABELS = 0, 1
 OVERLAY_FILL, OVERLAY_OUTLINE, OVERLAY_DENSE = 1, 2, 4
 SHADE_LIGHT, SHADE_AO = 0, 1
+(PROBE_ARITH, PROBE_HASH, PROBE_HEMISPHERE, PROBE_RAY, PROBE_CUT, PROBE_ENV_EXACT, PROBE_ENV_FAST, PROBE_ENV_APPROX, PROBE_TONE,
+ PROBE_TAPS) = range(10)
+# clwh_debug_device_probe: (words per input record, words per output record) of each probe
+PROBE_WORDS = ((6, 12), (1, 1), (7, 6), (10, 3), (6, 4), (3, 1), (3, 2), (3, 2), (4, 1), (3, 3))
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
 TF_MAX_RULES = 16
@@ -360,6 +364,7 @@ _PROTOTYPES = [
     ("clwh_tf_parse", C.c_int, [C.c_char_p, C.POINTER(Tf)]),
     ("clwh_debug_float_conversions", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("clwh_debug_wave_min", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("clwh_debug_device_probe", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_debug_macro_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_start_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_start_cert_dmin", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
@@ -1059,6 +1064,23 @@ class Context:
         sid, nb, holders = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
         _check(lib().clwh_ctx_scene_info(self.h, C.byref(sid), C.byref(nb), C.byref(holders)), "clwh_ctx_scene_info")
         return int(sid.value), int(nb.value), int(holders.value)
+
+    def device_probe(self, which, records: np.ndarray, params=(0, 0, 0, 0), aux: np.ndarray = None) -> np.ndarray:
+        """clwh_debug_device_probe over `records` (uint32 [n][words in]; floats as their bits): uint32 [n][words out]"""
+        w_in, w_out = PROBE_WORDS[which]
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, w_in)
+        n = rec.shape[0]
+        m_in, m_out = self.buffer_from(rec if n else np.zeros(1, np.uint32)), self.buffer(max(n, 1) * w_out * 4, np.uint32)
+        m_aux = self.buffer_from(np.ascontiguousarray(aux, dtype=np.uint32)) if aux is not None else None
+        try:
+            _check(lib().clwh_debug_device_probe(self.h, which, m_in.h, C.c_uint64(n), m_out.h, m_aux.h if m_aux else None,
+                                                 (C.c_int32 * 4)(*[int(v) for v in params])), "clwh_debug_device_probe")
+            self.finish()
+            return m_out.pull().reshape(-1, w_out)[:n]
+        finally:
+            for m in (m_in, m_out, m_aux):
+                if m is not None:
+                    m.release()
 
     def macro_table(self):
         """the exit-certificate table of the scene data this context rendered from last: (uint8 [cz][cy][cx][octant], log2 of the

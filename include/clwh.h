@@ -982,6 +982,40 @@ int clwh_debug_float_conversions(clwh_ctx *ctx, clwh_mem *floats_in, uint64_t n,
 /* self-test of the wave-wide minimum k_repack takes over a sub-brick's 64 voxels for the exit-certificate table (cross-lane DPP
  * operations): n (a multiple of 64) values, one wave per 64; u32_out[0, n/64) = that minimum, [n/64, 2n/64) = the same by a shuffle loop */
 int clwh_debug_wave_min(clwh_ctx *ctx, clwh_mem *u32_in, uint64_t n, clwh_mem *u32_out);
+/* the render path's device functions one by one (csrc/device_math.hpp, render_device.hpp, env_fast.hpp), so that a test can say which
+ * function differs from the contract of DESIGN.md "Semantics" and at which input: one lane per record calls the function(s) `which`
+ * names, unchanged, on the record's words.  `in` holds n records of 32-bit words, `out` receives n records; floats travel as their bits.
+ *   which        in (words)                                     out (words)
+ *   ARITH        a.x a.y a.z b.x b.y b.z                        a.x / b.x, sqrtf(a.x), dot3(a, b), length3(a), normalize3(a) [3],
+ *                                                               cross3(a, b) [3], cl_min(a.x, b.x), cl_max(a.x, b.x)
+ *   HASH         seed                                           hash_u32(seed)
+ *   HEMISPHERE   gx gy normal[3] seed roughness                 hemisphere_reflective [3], hemisphere_direction [3]
+ *   RAY          origin[3] direction[3] x y x_total y_total     generate_ray(...).direction [3]
+ *   CUT          origin[3] direction[3]                         cut_box's flag, cut point [3]; box = (float)params[0..2]
+ *   ENV_EXACT    d[3]                                           sample_environment_map(aux, w, h, d); w = params[0], h = params[1]
+ *   ENV_FAST     d[3]                                           sample_environment_map_fast: decided (0 / 1), texel (0xFFFFFFFF when not)
+ *   ENV_APPROX   y x v                                          atan2_approx(y, x), asin_approx(v)
+ *   TONE         sr sg sb count                                 tone_map_rgba8
+ *   TAPS         p[3]                                           taps_are_voxel_neighbours(p), cache_entry_of(params[0], params[1], p) as
+ *                                                               int64: low word, high word
+ * `aux` is read by the two ENV probes only (null otherwise): an environment image of w * h words, row-major; a caller that stores
+ * j * w + i in texel (i, j) reads back the texel the sampler chose.  CLWH_ERR_INVALID_VALUE: a null ctx / in / out / params, an unknown
+ * `which`, an ENV probe without aux or with w < 1 or h < 1; CLWH_ERR_SIZE_MISMATCH: n >= 2^31, or `in`, `out` or `aux` shorter than
+ * the records (the image); n == 0 does nothing */
+enum clwh_probe {
+  CLWH_PROBE_ARITH = 0,
+  CLWH_PROBE_HASH = 1,
+  CLWH_PROBE_HEMISPHERE = 2,
+  CLWH_PROBE_RAY = 3,
+  CLWH_PROBE_CUT = 4,
+  CLWH_PROBE_ENV_EXACT = 5,
+  CLWH_PROBE_ENV_FAST = 6,
+  CLWH_PROBE_ENV_APPROX = 7,
+  CLWH_PROBE_TONE = 8,
+  CLWH_PROBE_TAPS = 9,
+  CLWH_PROBE_COUNT = 10
+};
+int clwh_debug_device_probe(clwh_ctx *ctx, int32_t which, clwh_mem *in, uint64_t n, clwh_mem *out, clwh_mem *aux, const int32_t params[4]);
 /* the exit-certificate table of the derived scene data the context rendered from last: info_out = {cells along x, y, z,
  * log2 of a cell's edge in voxels}; host_out (may be null: the shape alone) receives 8 bytes per cell, x fastest, byte o = the entry
  * of direction octant o = [d.x < 0] | [d.y < 0] << 1 | [d.z < 0] << 2: 1..127 = the box towards the octant's corner is free and this is

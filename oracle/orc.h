@@ -182,6 +182,33 @@ int orc_cut(int32_t X, int32_t Y, int32_t Z, const float origin[3], const float 
             float out_point[3]);
 void orc_env_texel(const float dir[3], int32_t env_w, int32_t env_h, int32_t out_ij[2]);
 int orc_tf_eval(const orc_tf *tf, int32_t value, int32_t gradient, int32_t color[4]);
+/* utility_sampling.cl:25-36 get_hemisphere_direction, and the `decider` both hemisphere functions compute */
+void orc_hemisphere_direction(const float normal[3], int32_t seed, uint32_t gx, uint32_t gy, float out[3]);
+float orc_hemisphere_decider(const float normal[3], int32_t seed, uint32_t gx, uint32_t gy);
+/* ray_marching.cl:82-99 on {sum r, sum g, sum b, count}: {r, g, b, 1} before write_imageui's saturation to 255 */
+void orc_tone_map(const uint32_t sums[4], uint32_t out[4]);
+
+/* the same probes over n records (vectors: 3 floats per record, packed); one call per input set */
+void orc_hash_n(const uint32_t *seed, int64_t n, uint32_t *out);
+void orc_hemisphere_reflective_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                                 const float *roughness, int64_t n, float *out);
+void orc_hemisphere_direction_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                                int64_t n, float *out);
+void orc_hemisphere_decider_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                              int64_t n, float *out);
+void orc_generate_ray_n(const float *cam_pos, const float *cam_dir, const int32_t *x, const int32_t *y,
+                        const int32_t *x_total, const int32_t *y_total, int64_t n, float *out_dir);
+/* plane_tests (may be null): bit 0 / 1 / 2 = the x / y / z plane's test of utility_ray.cl:52-64 succeeded */
+void orc_cut_n(int32_t X, int32_t Y, int32_t Z, const float *origin, const float *dir, int64_t n, int32_t *hit,
+               float *out_point, int32_t *plane_tests);
+void orc_env_texel_n(const float *dir, int64_t n, int32_t env_w, int32_t env_h, int32_t *out_ij);
+void orc_tone_map_n(const uint32_t *sums, int64_t n, uint32_t *out);
+/* the two steps where a second binary64 library may round differently, taken apart (tests/test_device_function_inputs_cpu.py):
+ * the binary64 angles / curve value before the rounding to binary32, and the texel / byte that follows from a given binary32 one */
+void orc_env_angles_n(const float *dir, int64_t n, double *theta, double *phi);
+void orc_env_texel_of_angles_n(const float *theta, const float *phi, int64_t n, int32_t w, int32_t h, int32_t *out_ij);
+void orc_tone_pow_n(const uint32_t *r, int64_t n, double *out);
+void orc_tone_byte_of_n(const float *p, int64_t n, uint32_t *out);
 
 #ifdef __cplusplus
 }

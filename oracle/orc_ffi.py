@@ -118,6 +118,27 @@ def lib():
         L.orc_env_texel.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.orc_tf_eval.restype = C.c_int
         L.orc_tf_eval.argtypes = [C.POINTER(Tf), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        L.orc_hemisphere_direction.restype = None
+        L.orc_hemisphere_direction.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        L.orc_hemisphere_decider.restype = C.c_float
+        L.orc_hemisphere_decider.argtypes = [C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.c_uint32]
+        L.orc_tone_map.restype = None
+        L.orc_tone_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        p, n64, i32 = C.c_void_p, C.c_int64, C.c_int32
+        for name, args in (("orc_hash_n", [p, n64, p]),
+                           ("orc_hemisphere_reflective_n", [p, p, p, p, p, n64, p]),
+                           ("orc_hemisphere_direction_n", [p, p, p, p, n64, p]),
+                           ("orc_hemisphere_decider_n", [p, p, p, p, n64, p]),
+                           ("orc_generate_ray_n", [p, p, p, p, p, p, n64, p]),
+                           ("orc_cut_n", [i32, i32, i32, p, p, n64, p, p, p]),
+                           ("orc_env_texel_n", [p, n64, i32, i32, p]),
+                           ("orc_tone_map_n", [p, n64, p]),
+                           ("orc_env_angles_n", [p, n64, p, p]),
+                           ("orc_env_texel_of_angles_n", [p, p, n64, i32, i32, p]),
+                           ("orc_tone_pow_n", [p, n64, p]),
+                           ("orc_tone_byte_of_n", [p, n64, p])):
+            f = getattr(L, name)
+            f.restype, f.argtypes = None, args
         _lib = L
     return _lib
 
@@ -323,6 +344,110 @@ class Scene:
 
     def counter_dict(self):
         return {k: int(v) for k, v in zip(COUNTER_NAMES, self.counters) if k != "reserved"}
+
+
+# -------------------------------------------------------------------------------------------------
+# the single-function probes over arrays (orc.h): one call per input set
+
+
+def _a(v, dtype, width=None):
+    a = np.ascontiguousarray(v, dtype=dtype)
+    return a if width is None else a.reshape(-1, width)
+
+
+def hash_n(seeds) -> np.ndarray:
+    s = _a(seeds, np.uint32)
+    out = np.empty_like(s)
+    lib().orc_hash_n(s.ctypes.data, s.size, out.ctypes.data)
+    return out
+
+
+def hemisphere_reflective_n(normal, seed, gx, gy, roughness) -> np.ndarray:
+    nrm, s, x, y, r = _a(normal, np.float32, 3), _a(seed, np.int32), _a(gx, np.uint32), _a(gy, np.uint32), _a(roughness, np.float32)
+    out = np.empty_like(nrm)
+    lib().orc_hemisphere_reflective_n(nrm.ctypes.data, s.ctypes.data, x.ctypes.data, y.ctypes.data, r.ctypes.data, len(nrm), out.ctypes.data)
+    return out
+
+
+def hemisphere_direction_n(normal, seed, gx, gy) -> np.ndarray:
+    nrm, s, x, y = _a(normal, np.float32, 3), _a(seed, np.int32), _a(gx, np.uint32), _a(gy, np.uint32)
+    out = np.empty_like(nrm)
+    lib().orc_hemisphere_direction_n(nrm.ctypes.data, s.ctypes.data, x.ctypes.data, y.ctypes.data, len(nrm), out.ctypes.data)
+    return out
+
+
+def hemisphere_decider_n(normal, seed, gx, gy) -> np.ndarray:
+    nrm, s, x, y = _a(normal, np.float32, 3), _a(seed, np.int32), _a(gx, np.uint32), _a(gy, np.uint32)
+    out = np.empty(len(nrm), np.float32)
+    lib().orc_hemisphere_decider_n(nrm.ctypes.data, s.ctypes.data, x.ctypes.data, y.ctypes.data, len(nrm), out.ctypes.data)
+    return out
+
+
+def generate_ray_n(cam_pos, cam_dir, x, y, x_total, y_total) -> np.ndarray:
+    p, d = _a(cam_pos, np.float32, 3), _a(cam_dir, np.float32, 3)
+    ints = [_a(v, np.int32) for v in (x, y, x_total, y_total)]
+    out = np.empty_like(d)
+    lib().orc_generate_ray_n(p.ctypes.data, d.ctypes.data, *[v.ctypes.data for v in ints], len(d), out.ctypes.data)
+    return out
+
+
+def cut_n(dims, origin, direction):
+    """(hit flags int32 [n], cut points float32 [n][3], plane tests int32 [n]: bit k = the plane test of axis k succeeded)"""
+    o, d = _a(origin, np.float32, 3), _a(direction, np.float32, 3)
+    hit, point, planes = np.empty(len(o), np.int32), np.empty_like(o), np.empty(len(o), np.int32)
+    lib().orc_cut_n(int(dims[0]), int(dims[1]), int(dims[2]), o.ctypes.data, d.ctypes.data, len(o), hit.ctypes.data, point.ctypes.data,
+                    planes.ctypes.data)
+    return hit, point, planes
+
+
+def env_texel_n(direction, w, h) -> np.ndarray:
+    d = _a(direction, np.float32, 3)
+    out = np.empty((len(d), 2), np.int32)
+    lib().orc_env_texel_n(d.ctypes.data, len(d), int(w), int(h), out.ctypes.data)
+    return out
+
+
+def env_angles_n(direction):
+    """binary64 (atan2(d.x, d.z), asin(-d.y)): what the contract rounds to binary32"""
+    d = _a(direction, np.float32, 3)
+    theta, phi = np.empty(len(d), np.float64), np.empty(len(d), np.float64)
+    lib().orc_env_angles_n(d.ctypes.data, len(d), theta.ctypes.data, phi.ctypes.data)
+    return theta, phi
+
+
+def env_texel_of_angles_n(theta, phi, w, h) -> np.ndarray:
+    t, p = _a(theta, np.float32), _a(phi, np.float32)
+    out = np.empty((t.size, 2), np.int32)
+    lib().orc_env_texel_of_angles_n(t.ctypes.data, p.ctypes.data, t.size, int(w), int(h), out.ctypes.data)
+    return out
+
+
+def tone_map_n(sums) -> np.ndarray:
+    """{r, g, b, 1} per record of {sum r, sum g, sum b, count}, before the frame write's saturation"""
+    s = _a(sums, np.uint32, 4)
+    out = np.empty_like(s)
+    lib().orc_tone_map_n(s.ctypes.data, len(s), out.ctypes.data)
+    return out
+
+
+def tone_rgba8_n(sums) -> np.ndarray:
+    """tone_map_n through write_imageui's saturation, packed r | g << 8 | b << 16 | a << 24"""
+    t = np.minimum(tone_map_n(sums), 255).astype(np.uint32)
+    return t[:, 0] | (t[:, 1] << 8) | (t[:, 2] << 16) | (t[:, 3] << 24)
+
+
+def tone_pow_n(r) -> np.ndarray:
+    v = _a(r, np.uint32)
+    out = np.empty(v.size, np.float64)
+    lib().orc_tone_pow_n(v.ctypes.data, v.size, out.ctypes.data)
+    return out
+
+
+def tone_byte_of_n(p) -> np.ndarray:
+    v = _a(p, np.float32)
+    out = np.empty(v.size, np.uint32)
+    lib().orc_tone_byte_of_n(v.ctypes.data, v.size, out.ctypes.data)
+    return out
 
 
 def algorithmic_bytes(counters: dict, samples: int) -> float:

@@ -916,3 +916,113 @@ void orc_camera_direction(double alpha, double beta, float out[3]) {
   out[1] = val[1] / flen;
   out[2] = val[2] / flen;
 }
+
+/* ---- single-function probes over arrays (tests/test_gpu_device_functions.py: one ctypes call per input set) ---- */
+void orc_hash_n(const uint32_t *seed, int64_t n, uint32_t *out) {
+  for (int64_t k = 0; k < n; ++k) out[k] = orc_hash(seed[k]);
+}
+
+void orc_hemisphere_reflective_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                                 const float *roughness, int64_t n, float *out) {
+  for (int64_t k = 0; k < n; ++k)
+    orc_hemisphere_reflective(normal + 3 * k, seed[k], gx[k], gy[k], roughness[k], out + 3 * k);
+}
+
+void orc_hemisphere_direction(const float normal[3], int32_t seed, uint32_t gx, uint32_t gy, float out[3]) {
+  f3 nrm = {normal[0], normal[1], normal[2]};
+  f3 r = hemisphere_direction(gx, gy, nrm, seed);
+  out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+
+void orc_hemisphere_direction_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                                int64_t n, float *out) {
+  for (int64_t k = 0; k < n; ++k) orc_hemisphere_direction(normal + 3 * k, seed[k], gx[k], gy[k], out + 3 * k);
+}
+
+/* the three numbers get_hemisphere_direction(_reflective) draws and their dot product with the normal */
+float orc_hemisphere_decider(const float normal[3], int32_t seed, uint32_t gx, uint32_t gy) {
+  uint32_t useed = (uint32_t)seed + (gx + 1u) * (gy + 1u);
+  int32_t rx = (int32_t)orc_hash(useed * 0x182205bdu);
+  int32_t ry = (int32_t)orc_hash(useed * 0xe8d052f3u);
+  int32_t rz = (int32_t)orc_hash(useed * 0xf1981dcfu);
+  f3 direction = {(float)((rx % 2048) - 1024), (float)((ry % 2048) - 1024), (float)((rz % 2048) - 1024)};
+  f3 nrm = {normal[0], normal[1], normal[2]};
+  return v_dot(direction, nrm);
+}
+
+void orc_hemisphere_decider_n(const float *normal, const int32_t *seed, const uint32_t *gx, const uint32_t *gy,
+                              int64_t n, float *out) {
+  for (int64_t k = 0; k < n; ++k) out[k] = orc_hemisphere_decider(normal + 3 * k, seed[k], gx[k], gy[k]);
+}
+
+void orc_generate_ray_n(const float *cam_pos, const float *cam_dir, const int32_t *x, const int32_t *y,
+                        const int32_t *x_total, const int32_t *y_total, int64_t n, float *out_dir) {
+  for (int64_t k = 0; k < n; ++k)
+    orc_generate_ray(cam_pos + 3 * k, cam_dir + 3 * k, x[k], y[k], x_total[k], y_total[k], out_dir + 3 * k);
+}
+
+/* plane_tests (optional): per record, bit 0 / 1 / 2 = the x / y / z plane's test succeeded (utility_ray.cl:52-64) */
+void orc_cut_n(int32_t X, int32_t Y, int32_t Z, const float *origin, const float *dir, int64_t n, int32_t *hit,
+               float *out_point, int32_t *plane_tests) {
+  const float dx = (float)X, dy = (float)Y, dz = (float)Z;
+  for (int64_t k = 0; k < n; ++k) {
+    hit[k] = orc_cut(X, Y, Z, origin + 3 * k, dir + 3 * k, out_point + 3 * k);
+    if (plane_tests) {
+      ray_t s = {{origin[3 * k], origin[3 * k + 1], origin[3 * k + 2]}, {dir[3 * k], dir[3 * k + 1], dir[3 * k + 2]}};
+      f3 xc = v_add(s.origin, v_scale(s.direction, minimum_cut(dx, s.origin.x, s.direction.x)));
+      f3 yc = v_add(s.origin, v_scale(s.direction, minimum_cut(dy, s.origin.y, s.direction.y)));
+      f3 zc = v_add(s.origin, v_scale(s.direction, minimum_cut(dz, s.origin.z, s.direction.z)));
+      plane_tests[k] = (limits(xc.y, dy) && limits(xc.z, dz) ? 1 : 0) | (limits(yc.x, dx) && limits(yc.z, dz) ? 2 : 0) |
+                       (limits(zc.x, dx) && limits(zc.y, dy) ? 4 : 0);
+    }
+  }
+}
+
+void orc_env_texel_n(const float *dir, int64_t n, int32_t env_w, int32_t env_h, int32_t *out_ij) {
+  for (int64_t k = 0; k < n; ++k) orc_env_texel(dir + 3 * k, env_w, env_h, out_ij + 2 * k);
+}
+
+/* the texel of utility_environment_map.cl:3-13 from given binary32 angles (what follows atan2 / asin) */
+void orc_env_texel_of_angles_n(const float *theta, const float *phi, int64_t n, int32_t w, int32_t h, int32_t *out_ij) {
+  for (int64_t k = 0; k < n; ++k) {
+    float u = theta[k] * 0.1591549431f, v = phi[k] * 0.318309886f;
+    u = u + 0.5f;
+    v = v + 0.5f;
+    int32_t i = f2i(floorf(u * (float)w)), j = f2i(floorf(v * (float)h));
+    if (i < 0) i = 0;
+    if (i > w - 1) i = w - 1;
+    if (j < 0) j = 0;
+    if (j > h - 1) j = h - 1;
+    out_ij[2 * k] = i; out_ij[2 * k + 1] = j;
+  }
+}
+
+/* the binary64 values the two angles are rounded from: atan2((double)d.x, (double)d.z), asin((double)-d.y) */
+void orc_env_angles_n(const float *dir, int64_t n, double *theta, double *phi) {
+  for (int64_t k = 0; k < n; ++k) {
+    theta[k] = atan2((double)dir[3 * k], (double)dir[3 * k + 2]);
+    phi[k] = asin((double)-dir[3 * k + 1]);
+  }
+}
+
+/* ray_marching.cl:82-99 on {sum r, sum g, sum b, count}: {r, g, b, 1} before write_imageui's saturation */
+void orc_tone_map(const uint32_t sums[4], uint32_t out[4]) {
+  u4 bv = {sums[0], sums[1], sums[2], sums[3]};
+  u4 r = tone_map(bv);
+  out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+}
+
+void orc_tone_map_n(const uint32_t *sums, int64_t n, uint32_t *out) {
+  for (int64_t k = 0; k < n; ++k) orc_tone_map(sums + 4 * k, out + 4 * k);
+}
+
+/* the tone curve's binary64 value for a channel mean r: pow((double)((float)r / 255.0f * 4.0f), (double)(1.0f / 1.77777777f)),
+ * and the byte of a given binary32 curve value: f2u(p * 255.0f) */
+void orc_tone_pow_n(const uint32_t *r, int64_t n, double *out) {
+  const float inv_gamma = 1.0f / 1.77777777f;
+  for (int64_t k = 0; k < n; ++k) out[k] = pow((double)((float)r[k] / 255.0f * 4.0f), (double)inv_gamma);
+}
+
+void orc_tone_byte_of_n(const float *p, int64_t n, uint32_t *out) {
+  for (int64_t k = 0; k < n; ++k) out[k] = f2u(p[k] * 255.0f);
+}

@@ -1,5 +1,7 @@
 // Host build of csrc/env_fast.hpp for tests/test_env_fast.py: the approximations use IEEE operations
 // only, so what is measured here on the CPU is what gfx950 computes.
+#include <string.h>
+
 #include "../../cl_volume_renderer_amd/csrc/env_fast.hpp"
 
 extern "C" {
@@ -12,6 +14,27 @@ int probe_env_texel_fast(float dx, float dy, float dz, int w, int h, int *ij) {
   ij[0] = i;
   ij[1] = j;
   return ok ? 1 : 0;
+}
+// the same over arrays: the approximations' bits, and (decided, i, j) per direction of 3 floats
+void probe_atan2_approx_n(const float *y, const float *x, long n, uint32_t *bits) {
+  for (long k = 0; k < n; ++k) {
+    const float r = clvr::atan2_approx(y[k], x[k]);
+    memcpy(&bits[k], &r, 4);
+  }
+}
+void probe_asin_approx_n(const float *v, long n, uint32_t *bits) {
+  for (long k = 0; k < n; ++k) {
+    const float r = clvr::asin_approx(v[k]);
+    memcpy(&bits[k], &r, 4);
+  }
+}
+void probe_env_texel_fast_n(const float *d, long n, int w, int h, int32_t *out) {
+  for (long k = 0; k < n; ++k) {
+    int32_t i = 0, j = 0;
+    out[3 * k] = clvr::env_texel_fast(d[3 * k], d[3 * k + 1], d[3 * k + 2], w, h, i, j) ? 1 : 0;
+    out[3 * k + 1] = i;
+    out[3 * k + 2] = j;
+  }
 }
 // worst absolute error of the two approximations against binary64 libm over n samples of a
 // deterministic low-discrepancy sweep (plus the caller's special values)

@@ -1,5 +1,6 @@
 """The certified fast path of the environment-map lookup (csrc/env_fast.hpp), measured on the CPU:
-its approximations use IEEE +,*,/,sqrt,fma only, so this host build computes what gfx950 computes.
+its approximations use IEEE +,*,/,sqrt,fma only, so this host build computes what gfx950 computes
+(tests/test_gpu_device_functions.py compares the two by bits on the device: test_env_approx, test_env_fast).
 
 1. the approximations' worst absolute error against binary64 libm stays well inside the bracket;
 2. whenever the fast path claims a texel, it is the texel of the exact contract (oracle)."""

@@ -391,3 +391,34 @@ def test_resolve_and_context_status(o):
     h = C.c_void_p()
     assert L.clwh_ctx_create(0, None) == INVALID_VALUE
     assert L.clwh_ctx_create(-1, C.byref(h)) == 2 and L.clwh_ctx_create(4096, C.byref(h)) == 2  # CLWH_ERR_NO_DEVICE
+
+
+def test_device_probe_status(o):
+    ctx, L = o.ctx, ffi.lib()
+    probe = L.clwh_debug_device_probe
+    p = (C.c_int32 * 4)(4, 4, 0, 0)
+    big, n1 = o.cache.h, C.c_uint64(1)
+    assert probe(None, ffi.PROBE_HASH, big, n1, big, None, p) == INVALID_VALUE
+    assert probe(ctx.h, ffi.PROBE_HASH, None, n1, big, None, p) == INVALID_VALUE
+    assert probe(ctx.h, ffi.PROBE_HASH, big, n1, None, None, p) == INVALID_VALUE
+    assert probe(ctx.h, ffi.PROBE_HASH, big, n1, big, None, None) == INVALID_VALUE
+    for which in (-1, len(ffi.PROBE_WORDS), 1 << 20):
+        assert probe(ctx.h, which, big, n1, big, None, p) == INVALID_VALUE
+    assert probe(ctx.h, -1, o.tiny.h, n1, o.tiny.h, None, p) == INVALID_VALUE          # the unknown probe comes before the sizes
+    for which, (w_in, w_out) in enumerate(ffi.PROBE_WORDS):
+        aux = big if which in (ffi.PROBE_ENV_EXACT, ffi.PROBE_ENV_FAST) else None
+        n_in, n_out = C.c_uint64(16 // (4 * w_in) + 1), C.c_uint64(16 // (4 * w_out) + 1)  # one record more than 16 bytes hold
+        assert probe(ctx.h, which, o.sixteen.h, n_in, big, aux, p) == SIZE_MISMATCH
+        assert probe(ctx.h, which, big, n_out, o.sixteen.h, aux, p) == SIZE_MISMATCH
+        assert probe(ctx.h, which, big, C.c_uint64(1 << 31), big, aux, p) == SIZE_MISMATCH
+        assert probe(ctx.h, which, o.tiny.h, C.c_uint64(0), o.tiny.h, aux, p) == ffi.OK    # valid: no record
+    for which in (ffi.PROBE_ENV_EXACT, ffi.PROBE_ENV_FAST):
+        assert probe(ctx.h, which, big, n1, big, None, p) == INVALID_VALUE                  # the image is missing
+        assert probe(ctx.h, which, big, n1, big, big, (C.c_int32 * 4)(0, 4, 0, 0)) == INVALID_VALUE
+        assert probe(ctx.h, which, big, n1, big, big, (C.c_int32 * 4)(4, -1, 0, 0)) == INVALID_VALUE
+        assert probe(ctx.h, which, big, n1, big, o.sixteen.h, (C.c_int32 * 4)(5, 1, 0, 0)) == SIZE_MISMATCH   # 5 texels in 16 bytes
+        assert probe(ctx.h, which, big, n1, big, o.sixteen.h, (C.c_int32 * 4)(32768, 32768, 0, 0)) == SIZE_MISMATCH
+        assert probe(ctx.h, which, o.tiny.h, n1, big, None, (C.c_int32 * 4)(0, 0, 0, 0)) == INVALID_VALUE     # before the sizes
+    assert probe(ctx.h, ffi.PROBE_ENV_EXACT, o.sixteen.h, n1, o.word.h, o.sixteen.h, (C.c_int32 * 4)(2, 2, 0, 0)) == ffi.OK  # valid
+    assert probe(ctx.h, ffi.PROBE_HASH, o.sixteen.h, n1, o.word.h, None, p) == ffi.OK   # valid: aux is not looked at
+    ctx.finish()
