@@ -639,6 +639,45 @@ int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int
   return CLWH_OK;
 }
 
+int clwh_debug_packed_scene(clwh_ctx *ctx, int32_t which, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (which != CLWH_SCENE_HIT_RECORDS && which != CLWH_SCENE_STEP_BYTES && which != CLWH_SCENE_BRICK_MIN) return CLWH_ERR_INVALID_VALUE;
+  if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
+  const PackedLayout L = scene_layout(ctx);
+  info_out[0] = L.NBX; info_out[1] = L.NBY; info_out[2] = L.NBZ; info_out[3] = 0;
+  if (!host_out) return CLWH_OK;  // the size alone
+  const size_t offset = which == CLWH_SCENE_HIT_RECORDS ? 0u : (which == CLWH_SCENE_STEP_BYTES ? L.off_stepb : L.off_brick_min);
+  const size_t bytes = which == CLWH_SCENE_HIT_RECORDS ? L.records * sizeof(uint2) : (which == CLWH_SCENE_STEP_BYTES ? L.records : L.n_bricks * sizeof(uint32_t));
+  if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + offset, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
+int clwh_debug_view_data(clwh_ctx *ctx, int32_t which, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (which != CLWH_VIEW_BRICKS && which != CLWH_VIEW_TABLE && which != CLWH_VIEW_DILATED && which != CLWH_VIEW_COARSE) return CLWH_ERR_INVALID_VALUE;
+  const ProjectionData &p = ctx->proj;
+  if (!p.valid) return CLWH_ERR_BAD_ARGS;  // no view rendered yet (or the derived data was dropped)
+  const size_t NBX = (p.dims[0] + 7) / 8, NBY = (p.dims[1] + 7) / 8, NBZ = (p.dims[2] + 7) / 8;
+  const size_t n_bricks = NBX * NBY * NBZ, n_cells = ((NBX + 3) / 4) * ((NBY + 3) / 4) * ((NBZ + 3) / 4);
+  info_out[0] = (int32_t)NBX; info_out[1] = (int32_t)NBY; info_out[2] = (int32_t)NBZ; info_out[3] = (int32_t)n_cells;
+  const bool second_level = which == CLWH_VIEW_DILATED || which == CLWH_VIEW_COARSE;
+  // the bricked copy alone (ensure_projection_data): the dilated and the coarse table do not exist, whatever the buffer holds
+  if (second_level && !p.dilated_valid) return CLWH_ERR_BAD_ARGS;
+  if (!host_out) return CLWH_OK;  // the size alone
+  const size_t off_table = n_bricks * 512u * sizeof(int16_t);
+  const DeviceBuffer &from = second_level ? p.dilated : p.data;
+  const size_t offset = which == CLWH_VIEW_TABLE ? off_table : (which == CLWH_VIEW_COARSE ? n_bricks * sizeof(uint32_t) : 0u);
+  const size_t bytes = which == CLWH_VIEW_BRICKS ? off_table : (which == CLWH_VIEW_COARSE ? n_cells : n_bricks) * sizeof(uint32_t);
+  if (capacity < bytes || from.bytes < offset + bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, from.as<uint8_t>() + offset, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
 int clwh_debug_start_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
   if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
   if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)

@@ -40,6 +40,8 @@ SHADE_LIGHT, SHADE_AO = 0, 1
  PROBE_TAPS) = range(10)
 # clwh_debug_device_probe: (words per input record, words per output record) of each probe
 PROBE_WORDS = ((6, 12), (1, 1), (7, 6), (10, 3), (6, 4), (3, 1), (3, 2), (3, 2), (4, 1), (3, 3))
+SCENE_HIT_RECORDS, SCENE_STEP_BYTES, SCENE_BRICK_MIN = range(3)            # clwh_debug_packed_scene
+VIEW_BRICKS, VIEW_TABLE, VIEW_DILATED, VIEW_COARSE = range(4)               # clwh_debug_view_data
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
 MAX_SEEDS = 64
 TF_MAX_RULES = 16
@@ -366,6 +368,8 @@ _PROTOTYPES = [
     ("clwh_debug_wave_min", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("clwh_debug_device_probe", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     ("clwh_debug_macro_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("clwh_debug_packed_scene", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    ("clwh_debug_view_data", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_start_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_debug_start_cert_dmin", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     ("clwh_debug_hit_records", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
@@ -1090,6 +1094,29 @@ class Context:
         out = np.empty((info[2], info[1], info[0], 8), np.uint8)
         _check(lib().clwh_debug_macro_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_macro_table")
         return out, int(info[3])
+
+    def packed_scene(self, which):
+        """one of the arrays k_repack derived from the scene this context rendered from last, raw and in brick order
+        (clwh_debug_packed_scene): SCENE_HIT_RECORDS uint32 [bricks][512][2], SCENE_STEP_BYTES uint8 [bricks][512], SCENE_BRICK_MIN
+        uint32 [bricks]; and the bricks along (x, y, z)"""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_packed_scene(self.h, which, None, C.c_uint64(0), info), "clwh_debug_packed_scene")
+        n = info[0] * info[1] * info[2]
+        out = (np.empty((n, 512, 2), np.uint32) if which == SCENE_HIT_RECORDS else
+               np.empty((n, 512), np.uint8) if which == SCENE_STEP_BYTES else np.empty(n, np.uint32))
+        _check(lib().clwh_debug_packed_scene(self.h, which, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_packed_scene")
+        return out, (int(info[0]), int(info[1]), int(info[2]))
+
+    def view_data(self, which):
+        """one of the arrays the views derive from the volume, as this context's last view call left them, raw (clwh_debug_view_data):
+        VIEW_BRICKS int16 [bricks][512], VIEW_TABLE / VIEW_DILATED uint32 [bricks], VIEW_COARSE uint32 [cells]; and the bricks along
+        (x, y, z).  Raises (status 7) for VIEW_DILATED / VIEW_COARSE while no call has built them."""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_view_data(self.h, which, None, C.c_uint64(0), info), "clwh_debug_view_data")
+        n = info[0] * info[1] * info[2]
+        out = np.empty((n, 512), np.int16) if which == VIEW_BRICKS else np.empty(info[3] if which == VIEW_COARSE else n, np.uint32)
+        _check(lib().clwh_debug_view_data(self.h, which, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_view_data")
+        return out, (int(info[0]), int(info[1]), int(info[2]))
 
     def start_table(self):
         """the start-certificate table of the scene data this context rendered from last: uint8 [z][y][x], bit o set = the box from

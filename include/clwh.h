@@ -1022,6 +1022,31 @@ int clwh_debug_device_probe(clwh_ctx *ctx, int32_t which, clwh_mem *in, uint64_t
  * its smallest step value; 0x80 | g = it is not, and g (saturating at 127) cells along the octant's diagonal is the nearest cell
  * whose box is free or that lies outside the volume.  CLWH_ERR_BAD_ARGS: the context holds no scene data */
 int clwh_debug_macro_table(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
+/* the arrays k_repack derives from (volume, SDF, transfer function), as the context rendered from them last, raw and in brick order
+ * (DESIGN.md 2): info_out = {bricks along x, y, z, 0}; host_out (may be null: the shape alone) receives the array `which` names.
+ * Voxel (x, y, z) has slot (((z >> 3) * NBY + (y >> 3)) * NBX + (x >> 3)) * 512 + inner, inner = (z & 4) << 6 | (y & 4) << 5 |
+ * (x & 4) << 4 | (z & 3) << 4 | (y & 3) << 2 | (x & 3); a brick's slots beyond the volume are padding.
+ *   HIT_RECORDS  two uint32 per slot: word 0 = gx[16:0] | gy[14:0] << 17, word 1 = gy[16:15] | gz[16:0] << 2 | class << 19 (gx, gy, gz:
+ *                the voxel's central differences, border 0; class: 1 + index of its first matching rule, 0: none).  Written per 4^3
+ *                sub-brick (64 consecutive slots), and only where a voxel of the sub-brick may be an event under some gradient;
+ *                the other sub-bricks hold whatever the memory held before and no march reads them
+ *   STEP_BYTES   one byte per slot: bit 7 = class != 0, bits 0-6 = max(sdf, 0); padding 0
+ *   BRICK_MIN    one uint32 per brick: the smallest free value of its real voxels (0: the voxel may be an event or sdf <= 0, else sdf)
+ * CLWH_ERR_INVALID_VALUE: a null ctx / info_out, an unknown `which`; CLWH_ERR_BAD_ARGS: the context holds no scene data;
+ * CLWH_ERR_SIZE_MISMATCH: `capacity` is short */
+enum clwh_scene_array { CLWH_SCENE_HIT_RECORDS = 0, CLWH_SCENE_STEP_BYTES = 1, CLWH_SCENE_BRICK_MIN = 2 };
+int clwh_debug_packed_scene(clwh_ctx *ctx, int32_t which, void *host_out, uint64_t capacity, int32_t info_out[4]);
+/* the data the views derive from the volume (projections, compositing, isosurface, slices, the mesher), as the context's last view
+ * call left them, raw: info_out = {bricks along x, y, z, cells of 4^3 bricks}; host_out (may be null: the shape alone) receives
+ *   BRICKS   int16 per slot, the brick order above, padding 0
+ *   TABLE    uint32 per brick: (uint16)min | (uint16)max << 16 over its real voxels
+ *   DILATED  the same pair over the brick grown by one voxel, clamped at the volume's faces
+ *   COARSE   the same pair per cell of 4^3 bricks over its bricks' DILATED pairs; cells x fastest, ceil(bricks / 4) per axis
+ * CLWH_ERR_INVALID_VALUE: a null ctx / info_out, an unknown `which`; CLWH_ERR_BAD_ARGS: the context holds no view data, or DILATED /
+ * COARSE is asked for and no call that skips by them (isosurface, slice MAX / MIN, mesher) has built them for the current BRICKS --
+ * info_out is filled all the same, nothing is copied; CLWH_ERR_SIZE_MISMATCH: `capacity` is short */
+enum clwh_view_array { CLWH_VIEW_BRICKS = 0, CLWH_VIEW_TABLE = 1, CLWH_VIEW_DILATED = 2, CLWH_VIEW_COARSE = 3 };
+int clwh_debug_view_data(clwh_ctx *ctx, int32_t which, void *host_out, uint64_t capacity, int32_t info_out[4]);
 /* the start-certificate table of the derived scene data the context rendered from last: info_out = {X, Y, Z,
  * 1 if the table was built else 0}; host_out (may be null: the shape alone) receives one byte per voxel, x fastest: bit o is set when
  * no voxel of the box from this voxel (inclusive) to the volume corner direction octant o heads for may be an event.  Nothing is

@@ -35,6 +35,20 @@ def test_version_and_strerror():
     assert L.clwh_strerror(12345) == b"CLWH_ERR_UNKNOWN"
 
 
+def test_read_back_entries_refuse_null_arguments_without_a_device():
+    """clwh_debug_packed_scene / clwh_debug_view_data decide a null context or info_out before they touch anything"""
+    L = ffi.lib()
+    info = (ctypes.c_int32 * 4)(-1, -1, -1, -1)
+    buf = (ctypes.c_uint8 * 16)()
+    for entry, arrays in ((L.clwh_debug_packed_scene, (ffi.SCENE_HIT_RECORDS, ffi.SCENE_STEP_BYTES, ffi.SCENE_BRICK_MIN)),
+                          (L.clwh_debug_view_data, (ffi.VIEW_BRICKS, ffi.VIEW_TABLE, ffi.VIEW_DILATED, ffi.VIEW_COARSE))):
+        assert arrays == tuple(range(len(arrays)))
+        for which in arrays + (-1, len(arrays)):
+            assert entry(None, which, None, ctypes.c_uint64(0), info) == 1   # CLWH_ERR_INVALID_VALUE
+            assert entry(None, which, buf, ctypes.c_uint64(16), info) == 1
+    assert tuple(info) == (-1, -1, -1, -1) and bytes(buf) == bytes(16)
+
+
 def test_size_helpers():
     # reference allocation X*Y*Z*4 plus the one-row overrun of utility.cl:21 (SURVEY 8a row a9)
     assert ffi.cache_len(38, 35, 38) == (38 * 35 * 38 + 38 * 38 + 38 + 1) * 4

@@ -422,3 +422,65 @@ def test_device_probe_status(o):
     assert probe(ctx.h, ffi.PROBE_ENV_EXACT, o.sixteen.h, n1, o.word.h, o.sixteen.h, (C.c_int32 * 4)(2, 2, 0, 0)) == ffi.OK  # valid
     assert probe(ctx.h, ffi.PROBE_HASH, o.sixteen.h, n1, o.word.h, None, p) == ffi.OK   # valid: aux is not looked at
     ctx.finish()
+
+
+def test_read_back_status(o):
+    """clwh_debug_packed_scene and clwh_debug_view_data: on a context that has built nothing, then after one render / one projection
+    / one isosurface of the 16^3 scene (8 bricks, 1 cell)"""
+    L = ffi.lib()
+    scene_arrays = (ffi.SCENE_HIT_RECORDS, ffi.SCENE_STEP_BYTES, ffi.SCENE_BRICK_MIN)
+    view_arrays = (ffi.VIEW_BRICKS, ffi.VIEW_TABLE, ffi.VIEW_DILATED, ffi.VIEW_COARSE)
+    info = (C.c_int32 * 4)()
+    big = np.zeros(8 * 512 * 8, np.uint8)
+    out, cap = big.ctypes.data_as(C.c_void_p), C.c_uint64(big.nbytes)
+    ctx = ffi.Context(0)
+    try:
+        for entry, arrays in ((L.clwh_debug_packed_scene, scene_arrays), (L.clwh_debug_view_data, view_arrays)):
+            for which in arrays:
+                assert entry(ctx.h, which, None, C.c_uint64(0), info) == BAD_ARGS          # nothing built yet
+                assert entry(ctx.h, which, out, cap, info) == BAD_ARGS
+                assert entry(None, which, out, cap, info) == INVALID_VALUE
+                assert entry(ctx.h, which, out, cap, None) == INVALID_VALUE
+            for which in (-1, len(arrays), 1 << 20):
+                assert entry(ctx.h, which, out, cap, info) == INVALID_VALUE                # the unknown array comes before the data
+        assert not big.any()
+        volume = ctx.image_from(scene.phantom(N))
+        sdf = ctx.image([N, N, N], 1, np.int8, (N, N, N))
+        ctx.sdf_build(volume, o.tf, sdf)
+        env = ctx.image_from(scene.env_map(16, 8).astype(np.uint8), channels=4)
+        frame = ctx.image([W, H], 4, np.uint8, (H, W, 4))
+        accum = ctx.buffer(ffi.accum_len(W, H, 1) * 16, np.float32)
+        ctx.buffer_reset(accum)
+        k = ctx.kernel("ray_marching.cl", "render", o.tf)
+        k.render(frame=None, volume=volume, sdf=sdf, env=env, accum=accum, cam_pos=o.pos, cam_dir=o.dir, seed=1, width=W, height=H,
+                 mode=ffi.ACCUM_IMAGE_SPACE, write_frame=False)
+        packed = L.clwh_debug_packed_scene
+        for which, nbytes in zip(scene_arrays, (8 * 512 * 8, 8 * 512, 8 * 4)):
+            assert packed(ctx.h, which, None, C.c_uint64(0), info) == ffi.OK and tuple(info) == (2, 2, 2, 0)   # the shape alone
+            assert packed(ctx.h, which, out, C.c_uint64(nbytes - 1), info) == SIZE_MISMATCH
+            assert packed(ctx.h, which, out, C.c_uint64(0), info) == SIZE_MISMATCH
+            assert packed(ctx.h, which, out, C.c_uint64(nbytes), info) == ffi.OK                             # valid
+            assert packed(ctx.h, len(scene_arrays), out, C.c_uint64(0), info) == INVALID_VALUE               # before the size
+        view = L.clwh_debug_view_data
+        assert view(ctx.h, ffi.VIEW_BRICKS, None, C.c_uint64(0), info) == BAD_ARGS        # a render builds no view data
+        ctx.render_projection(frame, volume, o.pos, o.dir, W, H)
+        for which, nbytes in ((ffi.VIEW_BRICKS, 8 * 512 * 2), (ffi.VIEW_TABLE, 8 * 4)):
+            assert view(ctx.h, which, None, C.c_uint64(0), info) == ffi.OK and tuple(info) == (2, 2, 2, 1)
+            assert view(ctx.h, which, out, C.c_uint64(nbytes - 1), info) == SIZE_MISMATCH
+            assert view(ctx.h, which, out, C.c_uint64(nbytes), info) == ffi.OK
+        for which in (ffi.VIEW_DILATED, ffi.VIEW_COARSE):   # only the bricked copy exists: missing, whatever the capacity
+            info[:] = [0, 0, 0, 0]
+            assert view(ctx.h, which, None, C.c_uint64(0), info) == BAD_ARGS and tuple(info) == (2, 2, 2, 1)
+            assert view(ctx.h, which, out, C.c_uint64(0), info) == BAD_ARGS and view(ctx.h, which, out, cap, info) == BAD_ARGS
+        ctx.render_isosurface(frame, volume, o.pos, o.dir, W, H, 300.0)
+        for which, nbytes in ((ffi.VIEW_DILATED, 8 * 4), (ffi.VIEW_COARSE, 4)):
+            assert view(ctx.h, which, None, C.c_uint64(0), info) == ffi.OK
+            assert view(ctx.h, which, out, C.c_uint64(nbytes - 1), info) == SIZE_MISMATCH
+            assert view(ctx.h, which, out, C.c_uint64(nbytes), info) == ffi.OK
+        ctx.invalidate_derived(scene=False, camera=False, projection=True)                # dropped again
+        assert all(view(ctx.h, which, out, cap, info) == BAD_ARGS for which in view_arrays)
+        ctx.finish()
+        for m in (volume, sdf, env, frame, accum, k):
+            m.release()
+    finally:
+        ctx.destroy()
