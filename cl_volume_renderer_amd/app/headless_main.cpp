@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,18 +12,23 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
 // view, the mesh or the path-traced frames then show the masked volume.
-// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
+// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
 // labelled (renderer::label_components), the K largest or those of at least N voxels (default: all) become the mask
 // (renderer::select_components) and are applied in place like --grow's region.  One JSON line has n_components, n_voxels, the selected
 // rank range ([0, 0]: none) and count / first / bbox of up to the 8 largest.  --grow and --components exclude each other.
 // dilate=R | erode=R | open=R | close=R, an item of --grow and of --components: the mask is dilated, eroded, opened or closed by a ball
 // of R x-voxels (renderer::morph_mask: lengths in 1/16 x-voxel, the axes weighted by the file's voxel sizes) before it is applied; the
 // JSON line then ends with "morph": {"op", "radius_sq", "weight", "count"}, count being the voxels of the mask that is applied.
+// split=R, an item of --grow and of --components: the mask (after any morphology item) is split into the parts that an erosion by a
+// ball of R x-voxels (erode='s convention) separates: eroded, the pieces ranked largest first, and grown back inside the mask, every
+// voxel to the piece that reaches it first (renderer::split_mask).  One JSON line {"split": {"radius_sq", "weight", "connectivity",
+// "parts", "counts"}}, counts being the voxels of up to the 8 largest parts (renderer::measure_labels), follows the item's other
+// lines; the mask that is applied is unchanged.  With show, the parts are coloured by their id.
 // measure, an item of --grow and of --components: a second JSON line with the exact record (renderer::measure_mask: count, sum, sum_sq,
 // min, max, sum_pos, bbox, faces, border_faces) of the mask that is applied, after any morphology and before the volume is changed:
 // {"measure": {...}}; for --components {"measure_components": [...]}, the records (renderer::measure_labels) of the selected ranks,
@@ -72,6 +77,7 @@ int main(int argc_in, char const *argv_in[]) {
   int morph_op = -1;  // clwh_morph_op of the dilate= | erode= | open= | close= item, or -1
   float morph_radius = 0.0f;
   bool measure = false;  // the measure item
+  float split_radius = -1.0f;  // the split= item's erosion radius in x-voxels, or -1
   int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
   bool rewrites = false; // a keep, remove or fill= item
   // whether `v` is the show item; *ok is cleared if its style is unknown
@@ -97,8 +103,17 @@ int main(int argc_in, char const *argv_in[]) {
     }
     return false;
   };
-  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  // whether `v` is the split= item; *ok is cleared if its radius is not a number >= 0
+  const auto split_item = [&](const std::string &v, bool *ok) {
+    if (v.rfind("split=", 0) != 0) return false;
+    char *end = nullptr;
+    const float radius = std::strtof(v.c_str() + 6, &end);
+    *ok = *ok && v.size() > 6 && *end == '\0' && radius >= 0.0f && radius <= 4095.0f && split_radius < 0.0f;
+    split_radius = radius;
+    return true;
+  };
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -182,6 +197,7 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (v == "26") {
           grow_flags |= CLWH_GROW_26;
         } else if (morph_item(v, &ok)) {
+        } else if (split_item(v, &ok)) {
         } else if (v == "measure") {
           measure = true;
         } else if (show_item(v, &ok)) {
@@ -222,6 +238,7 @@ int main(int argc_in, char const *argv_in[]) {
         } else if (v == "26") {
           comps_flags |= CLWH_LABEL_26;
         } else if (morph_item(v, &ok)) {
+        } else if (split_item(v, &ok)) {
         } else if (v == "measure") {
           measure = true;
         } else if (show_item(v, &ok)) {
@@ -313,7 +330,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -347,6 +364,27 @@ int main(int argc_in, char const *argv_in[]) {
   if (show >= 0) show_style.flags = show;
   static const char *const kShowNames[4] = {"", "fill", "outline", "both"};
 
+  // the split= item: the mask (after any morphology) is split into the parts that an erosion by R separates (renderer::split_mask);
+  // one JSON line with their number and the voxel counts of up to the 8 largest; with show, the parts are coloured by their id
+  std::string split_line;  // printed behind the item's own lines
+  const auto split = [&](ui_state &none, bool conn26) {
+    const renderer::split_summary s = r.split_mask(none, split_radius, conn26 ? CLWH_GEO_26 : 0);
+    std::vector<uint64_t> counts;
+    if (s.n_parts > 0)
+      for (const clwh_region_stats &rec : r.measure_labels(none, (unsigned)std::min<uint64_t>(s.n_parts, 65536))) counts.push_back(rec.count);
+    std::sort(counts.begin(), counts.end(), [](uint64_t a, uint64_t b) { return a > b; });
+    counts.resize(std::min<size_t>(counts.size(), 8));
+    split_line = "{\"split\": {\"radius_sq\": " + std::to_string(s.radius_sq) + ", \"weight\": [" + std::to_string(s.weight[0]) + ", " +
+                 std::to_string(s.weight[1]) + ", " + std::to_string(s.weight[2]) + "], \"connectivity\": " + (conn26 ? "26" : "6") +
+                 ", \"parts\": " + std::to_string(s.n_parts) + ", \"counts\": [";
+    for (size_t k = 0; k < counts.size(); ++k) split_line += (k ? ", " : "") + std::to_string(counts[k]);
+    split_line += "]}}\n";
+    if (show >= 0 && s.n_parts > 0) {
+      show_source = renderer::OVERLAY_LABELS;
+      show_style.id_hi = (uint32_t)std::min<uint64_t>(s.n_parts, 0xFFFFFFFFull);
+    }
+  };
+
   if (grow) {  // first: everything below sees the masked volume
     const auto &size = rv.get_volume_size();
     for (int q = 0; q < 3; ++q)
@@ -360,6 +398,7 @@ int main(int argc_in, char const *argv_in[]) {
     if (morph_op >= 0) m = r.morph_mask(none, morph_op, morph_radius);
     clwh_mask_stats_result measured{};
     if (measure) measured = r.measure_mask(none);  // of the volume as loaded: before the mask changes it
+    if (split_radius >= 0.0f) split(none, (grow_flags & CLWH_GROW_26) != 0);
     if (show < 0) r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
@@ -375,6 +414,7 @@ int main(int argc_in, char const *argv_in[]) {
       print_record(measured.stats);
       std::printf("}\n");
     }
+    std::printf("%s", split_line.c_str());
   }
 
   if (comps) {  // like --grow: everything below sees the masked volume
@@ -400,8 +440,9 @@ int main(int argc_in, char const *argv_in[]) {
     clwh_mask_stats_result measured_mask{};
     if (measure && keep > 0) measured = r.measure_labels(none, (unsigned)std::min<uint64_t>(keep, 256));  // before the mask changes the volume
     if (measure && morph_op >= 0) measured_mask = r.measure_mask(none);  // the morphed mask is no longer the union of the ranks
+    if (split_radius >= 0.0f) split(none, (comps_flags & CLWH_LABEL_26) != 0);  // (replaces the labelling: after it was measured)
     if (show < 0) r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
-    if (show >= 0 && morph_op < 0 && keep > 0) {  // the labelling itself: a colour per rank (else the mask, which may be empty or morphed)
+    if (show >= 0 && morph_op < 0 && keep > 0 && split_radius < 0.0f) {  // the labelling itself: a colour per rank (else the mask, which may be empty or morphed)
       show_source = renderer::OVERLAY_LABELS;
       show_style.id_hi = (uint32_t)keep;
     }
@@ -433,6 +474,7 @@ int main(int argc_in, char const *argv_in[]) {
       }
       std::printf("}\n");
     }
+    std::printf("%s", split_line.c_str());
   }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera

@@ -2,9 +2,11 @@
 // env_map, signed_distance_field) so that pytest can drive the very call sequence the SDL/ImGui
 // application performs (reference app/ui.cpp:170-199, 296) without SDL.  Test / tooling entry points;
 // the product ABI is include/clwh.h.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "hdre_loader.hpp"
 #include "nrrd_loader.hpp"
@@ -172,6 +174,27 @@ unsigned long long clvr_host_morph_mask(clvr_host *h, int op, float radius, unsi
 // renderer::hold_mask / combine_masks: region = region op held
 void clvr_host_hold_mask(clvr_host *h) { h->rend.hold_mask(h->state); }
 void clvr_host_combine_masks(clvr_host *h, int op) { h->rend.combine_masks(h->state, op); }
+// renderer::geodesic_map of the region mask from n_seeds (x, y, z, id) quadruples into out[Z][Y][X]; result = {reached, max_dist}
+void clvr_host_geodesic_map(clvr_host *h, const unsigned *seeds, unsigned n_seeds, int flags, unsigned cap, unsigned *out,
+                            unsigned long long result[2]) {
+  const renderer::geodesic_summary s = h->rend.geodesic_map(h->state, std::vector<uint32_t>(seeds, seeds + 4u * n_seeds), flags, cap);
+  std::memcpy(out, s.dist.data(), s.dist.size() * sizeof(uint32_t));
+  result[0] = s.result.reached;
+  result[1] = s.result.max_dist;
+}
+// renderer::trace_path from `target` over the last geodesic map: up to `capacity` (x, y, z) triples into out; returns the true count
+unsigned long long clvr_host_trace_path(clvr_host *h, const unsigned target[3], int flags, unsigned *out, unsigned long long capacity) {
+  const std::vector<uint32_t> points = h->rend.trace_path(h->state, target, flags);
+  std::memcpy(out, points.data(), std::min<size_t>(points.size(), (size_t)capacity * 3) * sizeof(uint32_t));
+  return points.size() / 3;
+}
+// renderer::split_mask: the region split into parts that become the labelling; out = {radius_sq, wx, wy, wz}; returns the number of parts
+unsigned long long clvr_host_split_mask(clvr_host *h, float radius, int flags, unsigned out[4]) {
+  const renderer::split_summary s = h->rend.split_mask(h->state, radius, flags);
+  out[0] = s.radius_sq;
+  for (int q = 0; q < 3; ++q) out[1 + q] = s.weight[q];
+  return s.n_parts;
+}
 // renderer::measure_mask: the region mask's record into *out (a clwh_mask_stats_result, 120 bytes); n_bins > 0: its histogram into hist
 void clvr_host_measure_mask(clvr_host *h, int hist_lo, int bin_width, int n_bins, unsigned long long *hist, void *out) {
   std::vector<uint64_t> bins;

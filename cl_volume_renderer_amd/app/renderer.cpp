@@ -26,6 +26,7 @@ renderer::renderer(clw_context &c)
       region_mask(ctx, std::vector<uint32_t>(2)),
       held_mask(ctx, std::vector<uint32_t>(2)),
       region_labels(ctx, std::vector<uint32_t>(1)),
+      region_dist(ctx, std::vector<uint32_t>(1)),
       overlay_palette(ctx, std::vector<uint32_t>(overlay_colours()), true),
       sdf(ctx) {}
 
@@ -457,6 +458,112 @@ void renderer::combine_masks(struct ui_state &, int op) {
   for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
   d.op = op;
   clw_fail_hard_on_error(clwh_mask_combine(ctx.get_handle(), &d));
+}
+
+void renderer::geodesic_weights(uint32_t face[3], uint32_t edge[3], uint32_t *corner) const {
+  const auto &sizes = volume->get_voxel_sizes();
+  double s[3];
+  for (int q = 0; q < 3; ++q) s[q] = (double)sizes[q] * 16.0;
+  const auto cost = [](double length) { return (uint32_t)std::min(65535.0, std::max(1.0, std::nearbyint(length))); };
+  for (int q = 0; q < 3; ++q) {
+    face[q] = cost(s[q]);
+    edge[q] = cost(std::sqrt(s[(q + 1) % 3] * s[(q + 1) % 3] + s[(q + 2) % 3] * s[(q + 2) % 3]));
+  }
+  *corner = cost(std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]));
+}
+
+renderer::geodesic_summary renderer::geodesic_map(struct ui_state &, const std::vector<uint32_t> &seeds, int flags, uint32_t cap) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  if (region_labels.size() != voxels) region_labels = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  if (region_dist.size() != voxels) region_dist = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  geodesic_summary out;
+  clwh_geodesic_desc d{};
+  d.domain = region_mask.get_device_reference();
+  d.dist = region_dist.get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  geodesic_weights(d.weight_face, d.weight_edge, &d.weight_corner);
+  d.cap = cap;
+  d.flags = flags & ~CLWH_GEO_FROM_LABELS;
+  d.n_seeds = (uint32_t)(seeds.size() / 4);
+  d.seeds = seeds.data();
+  d.result = &out.result;
+  clw_fail_hard_on_error(clwh_mask_geodesic(ctx.get_handle(), &d));
+  region_dist.pull();
+  out.dist.assign(&region_dist[0], &region_dist[0] + voxels);
+  return out;
+}
+
+std::vector<uint32_t> renderer::trace_path(struct ui_state &, const uint32_t target[3], int flags) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  if (region_dist.size() != voxels || region_labels.size() != voxels) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no map
+  uint64_t n = 0;
+  clwh_geodesic_trace_desc d{};
+  d.dist = region_dist.get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    d.dims[q] = (uint32_t)size[q];
+    d.target[q] = target[q];
+  }
+  geodesic_weights(d.weight_face, d.weight_edge, &d.weight_corner);
+  d.flags = flags & CLWH_GEO_26;
+  d.n_points = &n;
+  clw_fail_hard_on_error(clwh_geodesic_trace(ctx.get_handle(), &d));  // the count; then the points
+  if (n == 0) return {};
+  clw_vector<uint32_t> points(ctx, std::vector<uint32_t>((size_t)n * 3), false);
+  d.points = points.get_device_reference();
+  d.capacity = n;
+  clw_fail_hard_on_error(clwh_geodesic_trace(ctx.get_handle(), &d));
+  points.pull();
+  return std::vector<uint32_t>(&points[0], &points[0] + points.size());
+}
+
+renderer::split_summary renderer::split_mask(struct ui_state &, float radius, int flags) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2], mask_words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];
+  if (region_mask.size() != mask_words) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  if (region_labels.size() != voxels) region_labels = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  split_summary out;
+  out.radius_sq = mask_radius_sq(radius);
+  mask_weights(out.weight);
+  clw_vector<uint32_t> eroded(ctx, std::vector<uint32_t>(mask_words), false);
+  clwh_morph_desc m{};
+  m.mask_in = region_mask.get_device_reference();
+  m.mask_out = eroded.get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    m.dims[q] = (uint32_t)size[q];
+    m.weight[q] = out.weight[q];
+  }
+  m.radius_sq = out.radius_sq;
+  m.op = CLWH_MORPH_ERODE;
+  clw_fail_hard_on_error(clwh_mask_morph(ctx.get_handle(), &m));
+  // the pieces of the eroded mask alone: every value is inside the full window
+  clwh_label_result pieces{};
+  clwh_label_desc l{};
+  l.volume = volume->get_reference_volume().get_device_reference();
+  l.labels = region_labels.get_device_reference();
+  l.mask = eroded.get_device_reference();
+  l.lo = -32768;
+  l.hi = 32767;
+  l.flags = CLWH_LABEL_FROM_MASK | ((flags & CLWH_GEO_26) ? CLWH_LABEL_26 : 0);
+  l.result = &pieces;
+  clw_fail_hard_on_error(clwh_segment_label(ctx.get_handle(), &l));
+  out.n_parts = pieces.n_components;
+  if (out.n_parts == 0) return out;  // nothing survived: every label is 0
+  clwh_geodesic_result grown{};
+  clwh_geodesic_desc d{};
+  d.domain = region_mask.get_device_reference();
+  d.seed_labels = d.labels = region_labels.get_device_reference();  // in place
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q], d.weight_face[q] = d.weight_edge[q] = 1;
+  d.weight_corner = 1;
+  d.cap = CLWH_DIST_NONE;
+  d.flags = CLWH_GEO_FROM_LABELS | (flags & CLWH_GEO_26);
+  d.result = &grown;
+  clw_fail_hard_on_error(clwh_mask_geodesic(ctx.get_handle(), &d));
+  return out;
 }
 
 clwh_mask_stats_result renderer::measure_mask(struct ui_state &, int hist_lo, int bin_width, int n_bins, std::vector<uint64_t> *hist) {

@@ -134,6 +134,32 @@ class renderer : public frame_emitter {
   void hold_mask(struct ui_state &state);
   void combine_masks(struct ui_state &state, int op);
 
+  // not in the reference: shortest paths THROUGH the region mask (clwh_mask_geodesic / clwh_geodesic_trace).  geodesic_weights: the
+  // step costs in mask_weights' unit, the Euclidean length of each step in 1/16 of an x-voxel, rounded, within 1 .. 65535 (face per
+  // axis, edge per axis left unchanged, corner).  geodesic_map: the distance of every voxel of the region to the nearest of `seeds`
+  // ((x, y, z, id) quadruples, id >= 1) inside it, uint32 [z][y][x], CLWH_DIST_NONE elsewhere and above cap; the id of that seed (the
+  // smallest among equals) goes to the labelling select_components, measure_labels and the overlays read, and both maps stay on the
+  // device for trace_path.  flags: CLWH_GEO_26 | CLWH_GEO_DENSE.  trace_path: the (x, y, z) triples of the shortest path from
+  // `target` back to its seed, target first, inside the target's territory; empty for a voxel nothing reached; with the flags of the
+  // map's call.  No camera takes part (`state` is not read); all three wait for the device.
+  void geodesic_weights(uint32_t face[3], uint32_t edge[3], uint32_t *corner) const;
+  struct geodesic_summary {
+    clwh_geodesic_result result{};
+    std::vector<uint32_t> dist;
+  };
+  geodesic_summary geodesic_map(struct ui_state &state, const std::vector<uint32_t> &seeds, int flags = 0, uint32_t cap = CLWH_DIST_NONE);
+  std::vector<uint32_t> trace_path(struct ui_state &state, const uint32_t target[3], int flags = 0);
+  // a region whose parts touch, split: the region is eroded by a ball of `radius` x-voxels (morph_mask's) until the bridges break, the
+  // pieces that survive are ranked largest first (label_components' order), and they grow back inside the region, every voxel going
+  // to the piece that reaches it first in unit steps (flags: CLWH_GEO_26), ties to the smaller rank.  The parts become the labelling
+  // (rank = part); the region mask is unchanged.  A part that vanishes under the erosion leaves its voxels with label 0 unless a
+  // surviving part reaches them.
+  struct split_summary {
+    uint64_t n_parts = 0;
+    uint32_t radius_sq = 0, weight[3] = {1, 1, 1};
+  };
+  split_summary split_mask(struct ui_state &state, float radius, int flags = 0);
+
   // not in the reference: measuring (clwh_mask_statistics / clwh_label_statistics) on the volume the views show.  measure_mask: the
   // exact record of the region mask, whoever made it (count, sum, sum of squares, extremes, centroid numerators, bounding box, faces
   // per axis inside the volume and on its border), and with n_bins > 0 the histogram of its values, n_bins bins of bin_width from
@@ -175,6 +201,7 @@ class renderer : public frame_emitter {
   clw_vector<uint32_t> region_mask;          // grow_region's mask on the device (never pulled: the host side only sizes it)
   clw_vector<uint32_t> held_mask;            // hold_mask's copy of region_mask (never pulled)
   clw_vector<uint32_t> region_labels;        // label_components' ranks on the device, one word per voxel (never pulled)
+  clw_vector<uint32_t> region_dist;          // geodesic_map's distances on the device, for trace_path
   clw_vector<uint32_t> overlay_palette;      // overlay_colours() on the device, pushed once, by the constructor
   template <class Desc>
   void fill_overlay(Desc &d, const struct ui_state &state, int source, const overlay_style &style);

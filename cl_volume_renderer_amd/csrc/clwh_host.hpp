@@ -2,7 +2,7 @@
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
-// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_region_stats.hip: statistics of masks and labels).
+// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
 #pragma once
 
@@ -242,6 +242,14 @@ struct DistanceScratch {
   DeviceBuffer map_a, map_b, bits;
 };
 
+// clwh_mask_geodesic's and clwh_geodesic_trace's scratch: the packed keys (8 bytes per voxel); per tile of 16 x 16 x 8 voxels the round it
+// is to be visited in and its place in the round's list, behind them the round counters and the result; the copied seeds; and the
+// pinned line the counters and the results travel to the host in.  Every call rewrites what it reads: only the allocations are kept.
+struct GeodesicScratch {
+  DeviceBuffer keys, tiles, seeds, trace;  // trace: clwh_geodesic_trace's count and verdict
+  PinnedWord host;
+};
+
 // clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
 // Every call rewrites what it reads: only the allocation is kept.
 struct RegionStatsScratch {
@@ -308,6 +316,7 @@ struct clwh_ctx {
   clvr::GrowScratch grow;
   clvr::LabelScratch label;
   clvr::DistanceScratch distance;
+  clvr::GeodesicScratch geodesic;
   clvr::RegionStatsScratch region_stats;
   clvr::OverlayScratch overlay;
   clvr::ProjectionData proj;

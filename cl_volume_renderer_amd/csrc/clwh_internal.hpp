@@ -582,6 +582,58 @@ hipError_t launch_dist_lines_bits(const DistArgs &a, const uint32_t *src, unsign
 hipError_t launch_mask_combine(const unsigned long long *a, const unsigned long long *b, unsigned long long *out, int32_t X, int32_t Y,
                                int32_t Z, int32_t W64, int32_t op, hipStream_t s);
 
+// ---- geodesic distance maps and nearest-seed territories inside a mask, and the path behind a distance (geodesic_kernels.hip; host
+// side clwh_geodesic.hip).  The working keys (dist << 32 | id) are a packed array of one 64-bit word per voxel, [z][y][x] without
+// padding; the volume is cut into tiles of kGeoTileX x kGeoTileY x kGeoTileZ voxels, tile (tx, ty, tz) at (tz * TY + ty) * TX + tx; rounds are grow's.
+// The tile's core; a block of 256 threads owns it, a thread the column along z at its (x, y).  16 x 16 x 8 is what was measured best
+// (DESIGN.md, section 4); the macros are there so that tools/time_geodesic.py can time another build of the library against it.
+#ifndef CLVR_GEO_TILE_X
+#define CLVR_GEO_TILE_X 16
+#define CLVR_GEO_TILE_Y 16
+#define CLVR_GEO_TILE_Z 8
+#endif
+constexpr int kGeoTileX = CLVR_GEO_TILE_X, kGeoTileY = CLVR_GEO_TILE_Y, kGeoTileZ = CLVR_GEO_TILE_Z;
+static_assert(kGeoTileX * kGeoTileY == 256 && kGeoTileZ >= 1 && kGeoTileZ <= 32, "a thread per column, a bit per voxel of it");
+struct GeoDeviceResult {       // what k_geo_finish accumulates, zero on entry
+  unsigned long long reached;
+  uint32_t max_dist, reserved;
+};
+struct GeoArgs {
+  const uint8_t *domain;       // grow's bit rows, read only
+  const uint32_t *seed_labels; // CLWH_GEO_FROM_LABELS: the caller's words; else null
+  unsigned long long *keys;    // scratch, one per voxel
+  uint32_t *dist, *labels;     // the caller's maps; either may be null
+  int32_t X, Y, Z, W64;
+  int32_t TX, TY, TZ;
+  uint32_t w_face[3], w_edge[3], w_corner;  // the edge's index is the axis that does not change
+  uint32_t cap;                // <= 0xFFFF0000
+  int32_t conn26, dense;
+  uint32_t *stamps;            // per tile: the round (1, 2, ...) in which it is to be visited
+  uint32_t *list;              // the tiles of the round being run
+  uint32_t *counters;          // kGrowBatch x {tiles listed, ticket}
+  const uint32_t *seeds;       // device copy, uint32[n_seeds][4] = x, y, z, id
+  uint32_t n_seeds;
+  GeoDeviceResult *result;
+};
+struct GeoTraceResult {
+  unsigned long long n_points;
+  uint32_t broken, reserved;   // broken: no direction qualified at a point with dist > 0
+};
+struct GeoTraceArgs {
+  const uint32_t *dist, *labels;  // labels may be null
+  uint32_t *points;            // [capacity][3]
+  unsigned long long capacity;
+  int32_t X, Y, Z;
+  int32_t target[3];
+  uint32_t w_face[3], w_edge[3], w_corner;
+  int32_t conn26;
+  GeoTraceResult *result;
+};
+hipError_t launch_geo_init(const GeoArgs &a, hipStream_t s);  // every key, the listed seeds, the stamps of the tiles that hold a seed
+hipError_t launch_geo_round(const GeoArgs &a, uint32_t round, int slot, hipStream_t s);  // k_geo_list + k_geo_round, counters[2 * slot]
+hipError_t launch_geo_finish(const GeoArgs &a, hipStream_t s);  // dist, labels, *result
+hipError_t launch_geo_trace(const GeoTraceArgs &a, hipStream_t s);
+
 // ---- exact statistics of a mask's region and of every rank of a labelling (region_stats_kernels.hip; host side clwh_region_stats.hip).
 // Records are accumulated in place, in clwh_region_stats' layout: launch_stats_init sets the identities (extremes, bbox_lo), the sums'
 // kernels add with vector atomics, launch_stats_finish writes the empty record where nothing was added and makes bbox_hi exclusive.

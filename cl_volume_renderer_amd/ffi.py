@@ -30,6 +30,8 @@ GROW_MAX_SEEDS = 65536
 LABEL_26, LABEL_FROM_MASK = 1, 2
 DIST_NONE = 0xFFFFFFFF
 DIST_TO_CLEAR = 1
+GEO_26, GEO_FROM_LABELS, GEO_DENSE = 1, 2, 4
+GEO_CAP_MAX = 0xFFFF0000
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
@@ -240,6 +242,36 @@ class MorphDesc(C.Structure):
                 ("radius_sq", C.c_uint32), ("op", C.c_int32), ("flags", C.c_int32)]
 
 
+class GeodesicResult(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("max_dist", C.c_uint32), ("rounds", C.c_uint32)]
+
+    def as_dict(self):
+        """the contract's fields (`rounds` is informational and left out)"""
+        return {"reached": int(self.reached), "max_dist": int(self.max_dist)}
+
+
+class GeodesicDesc(C.Structure):
+    _fields_ = [
+        ("domain", C.c_void_p), ("seed_labels", C.c_void_p), ("dist", C.c_void_p), ("labels", C.c_void_p),
+        ("dims", C.c_uint32 * 3), ("weight_face", C.c_uint32 * 3), ("weight_edge", C.c_uint32 * 3), ("weight_corner", C.c_uint32),
+        ("cap", C.c_uint32), ("flags", C.c_int32),
+        ("n_seeds", C.c_uint32), ("seeds", C.POINTER(C.c_uint32)),
+        ("result", C.POINTER(GeodesicResult)),
+    ]
+
+
+class GeodesicTraceDesc(C.Structure):
+    _fields_ = [
+        ("dist", C.c_void_p), ("labels", C.c_void_p), ("points", C.c_void_p), ("capacity", C.c_uint64),
+        ("dims", C.c_uint32 * 3), ("weight_face", C.c_uint32 * 3), ("weight_edge", C.c_uint32 * 3), ("weight_corner", C.c_uint32),
+        ("flags", C.c_int32), ("target", C.c_uint32 * 3),
+        ("n_points", C.POINTER(C.c_uint64)),
+    ]
+
+
+assert C.sizeof(GeodesicDesc) == 104 and C.sizeof(GeodesicTraceDesc) == 96 and C.sizeof(GeodesicResult) == 16
+
+
 class MaskCombineDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
 
@@ -354,6 +386,8 @@ _PROTOTYPES = [
     ("clwh_mask_distance", C.c_int, [C.c_void_p, C.POINTER(DistanceDesc)]),
     ("clwh_mask_morph", C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
+    ("clwh_mask_geodesic", C.c_int, [C.c_void_p, C.POINTER(GeodesicDesc)]),
+    ("clwh_geodesic_trace", C.c_int, [C.c_void_p, C.POINTER(GeodesicTraceDesc)]),
     ("clwh_mask_statistics", C.c_int, [C.c_void_p, C.POINTER(MaskStatsDesc)]),
     ("clwh_label_statistics", C.c_int, [C.c_void_p, C.POINTER(LabelStatsDesc)]),
     ("clwh_overlay_slice", C.c_int, [C.c_void_p, C.POINTER(OverlaySliceDesc)]),
@@ -1013,6 +1047,116 @@ class Context:
             out.release()
         _check(status, "clwh_mask_combine")
         return out
+
+    @staticmethod
+    def _geodesic_weights(d, weights):
+        """weights: None (all 1), (fx, fy, fz), or (face, edge, corner) as scene.geodesic_weights returns them"""
+        face, edge, corner = (1, 1, 1), (1, 1, 1), 1
+        if weights is not None:
+            if len(weights) == 3 and np.ndim(weights[0]) == 1:
+                face, edge, corner = weights
+            else:
+                face = weights
+        for k in range(3):
+            d.weight_face[k], d.weight_edge[k] = int(face[k]), int(edge[k])
+        d.weight_corner = int(corner)
+
+    def mask_geodesic_raw(self, domain: Mem, dims, seeds=None, seed_labels: Mem = None, flags=0, weights=None, cap=DIST_NONE,
+                          dist: Mem = None, labels: Mem = None, result=True):
+        """one clwh_mask_geodesic call: (status, GeodesicResult); nothing is raised.  seeds: rows of (x, y, z, id), or None.
+        result=False passes a NULL result."""
+        d, res = GeodesicDesc(), GeodesicResult()
+        d.domain, d.seed_labels, d.dist, d.labels = _handle(domain), _handle(seed_labels), _handle(dist), _handle(labels)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        self._geodesic_weights(d, weights)
+        d.cap, d.flags = int(cap), int(flags)
+        if seeds is not None:
+            s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint32).reshape(-1, 4))
+            d.n_seeds = len(s)
+            d.seeds = s.ctypes.data_as(C.POINTER(C.c_uint32))
+        if result:
+            d.result = C.pointer(res)
+        return lib().clwh_mask_geodesic(self.h, C.byref(d)), res
+
+    def mask_geodesic(self, domain: Mem, dims, seeds=None, seed_labels: Mem = None, connectivity=6, weights=None, cap=None,
+                      dist: Mem = None, labels: Mem = None, dense=False):
+        """shortest paths inside the mask `domain` (grow's layout, dims = (X, Y, Z)) from labelled seeds: (dist, labels,
+        GeodesicResult).  seeds: rows of (x, y, z, id), id >= 1; seed_labels: a uint32 [z][y][x] device buffer whose nonzero words
+        inside the domain are seeds with that id as well.  dist: the length of the shortest path to the nearest seed, DIST_NONE
+        outside the domain and where no seed reaches within `cap`; labels: the smallest id among the nearest seeds, 0 there.  Both
+        are uint32 [z][y][x] on the device, allocated when none is given; `labels` may be `seed_labels`.  weights: None (every step
+        costs 1), (fx, fy, fz), or (face, edge, corner) from scene.geodesic_weights.  dense: every tile in every round (tests,
+        timing).  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        own = [dist is None, labels is None]
+        if own[0]:
+            dist = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        if own[1]:
+            labels = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        flags = (GEO_26 if connectivity == 26 else 0) | (GEO_FROM_LABELS if seed_labels is not None else 0) | (GEO_DENSE if dense else 0)
+        status, res = self.mask_geodesic_raw(domain, dims, seeds, seed_labels, flags, weights, DIST_NONE if cap is None else cap,
+                                             dist, labels)
+        if status != OK:
+            for mine, m in zip(own, (dist, labels)):
+                if mine:
+                    m.release()
+        _check(status, "clwh_mask_geodesic")
+        return dist, labels, res
+
+    def geodesic_trace_raw(self, dist: Mem, dims, target, labels: Mem = None, flags=0, weights=None, points: Mem = None, capacity=0,
+                           result=True):
+        """one clwh_geodesic_trace call: (status, n_points); nothing is raised.  result=False passes a NULL n_points."""
+        d, n = GeodesicTraceDesc(), C.c_uint64(0)
+        d.dist, d.labels, d.points = _handle(dist), _handle(labels), _handle(points)
+        d.capacity, d.flags = int(capacity), int(flags)
+        for k in range(3):
+            d.dims[k], d.target[k] = int(dims[k]), int(target[k])
+        self._geodesic_weights(d, weights)
+        if result:
+            d.n_points = C.pointer(n)
+        return lib().clwh_geodesic_trace(self.h, C.byref(d)), int(n.value)
+
+    def geodesic_trace(self, dist: Mem, dims, target, labels: Mem = None, connectivity=6, weights=None, capacity=4096):
+        """the shortest path behind mask_geodesic's `dist` from `target` = (x, y, z) back to a seed (inside the target's territory
+        when `labels` is given), connectivity and weights as in that call: (points, n_points).  points: uint32 [n][3] = (x, y, z),
+        target first, the first min(n_points, capacity) of them; n_points: the true count, 0 for an unreached target.  ClwhError
+        for a map that mask_geodesic did not write.  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        capacity = int(capacity)
+        buf = self.buffer(max(capacity, 1) * 12, np.uint32)
+        try:
+            status, n = self.geodesic_trace_raw(dist, dims, target, labels, GEO_26 if connectivity == 26 else 0, weights, buf, capacity)
+            _check(status, "clwh_geodesic_trace")
+            k = min(n, capacity)
+            return (buf.pull(np.uint32)[:3 * k].reshape(k, 3).copy() if k else np.zeros((0, 3), np.uint32)), n
+        finally:
+            buf.release()
+
+    def split_mask(self, volume: Mem, mask: Mem, dims, radius_sq, weights=(1, 1, 1), connectivity=6):
+        """a mask whose parts touch, split: (labels, number of parts).  Three steps: the mask is eroded by the ball of radius_sq
+        (mask_morph's, with its `weights`) until the bridges break; the pieces that survive are labelled 1, 2, ... largest first
+        (label_components over the eroded mask alone: `volume`, the S16 image the mask belongs to, is read with the full value
+        window); and the pieces grow back inside the original mask, every voxel going to the piece that reaches it first
+        (mask_geodesic with unit steps under `connectivity`, ties to the smaller label).  labels: uint32 [z][y][x] on the device.
+        A part of the mask that vanishes under the erosion leaves its voxels unreached (label 0) unless a surviving part reaches
+        them.  The call waits for the device."""
+        eroded = self.mask_morph(mask, dims, MORPH_ERODE, radius_sq, weights)
+        try:
+            ranks, res, _ = self.label_components(volume, -32768, 32767, connectivity, mask=eroded, capacity=0)
+        finally:
+            eroded.release()
+        n_parts = int(res.n_components)
+        if n_parts == 0:  # nothing survived: label_components wrote 0 everywhere
+            return ranks, 0
+        status, _ = self.mask_geodesic_raw(mask, dims, None, ranks, GEO_FROM_LABELS | (GEO_26 if connectivity == 26 else 0), labels=ranks)
+        if status != OK:
+            ranks.release()
+        _check(status, "clwh_mask_geodesic")
+        return ranks, n_parts
 
     def mask_statistics_raw(self, volume: Mem, mask: Mem, hist: Mem = None, hist_lo=0, bin_width=0, n_bins=0, flags=0, result=True):
         """one clwh_mask_statistics call: (status, MaskStatsResult); nothing is raised.  result=False passes a NULL result."""

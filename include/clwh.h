@@ -745,6 +745,102 @@ typedef struct clwh_mask_combine_desc {
 } clwh_mask_combine_desc;
 int clwh_mask_combine(clwh_ctx *ctx, const clwh_mask_combine_desc *desc);
 
+/* ---- geodesic distance maps and nearest-seed territories inside a mask (not in the reference): shortest paths THROUGH a mask from a set
+ * of labelled seeds, giving every voxel a distance and the id of its nearest seed.  "These two bones touch: give me each one" is erode,
+ * label, and this call with the pieces as seeds; "how far along this vessel" is this call with one seed.  Integers and sets only:
+ * defined bit for bit, independent of how the device schedules anything.
+ * Domain.  dims = X, Y, Z.  D = the voxels of the volume whose bit in `domain` (clwh_segment_grow's mask layout; read only) is set.
+ * Bits at x >= X and the padding words are ignored, whatever they hold.
+ * Steps and costs.  Neighbours are clwh_segment_grow's: 6, or 26 with CLWH_GEO_26; no clamping, no wrap-around.  A step that changes
+ * one coordinate costs weight_face[axis]; with CLWH_GEO_26 a step that changes two costs weight_edge[k], k the axis that does NOT
+ * change (0: y and z change, 1: x and z, 2: x and y), and a step that changes all three costs weight_corner.  Every weight in use is
+ * an integer in 1 .. 65535; edge and corner weights are ignored without CLWH_GEO_26.  No triangle inequality is demanded.  A path is
+ * a sequence of voxels of D, each a neighbour of the one before; its length is the sum of its steps' costs.
+ * Seeds.  `seeds` is a HOST pointer to uint32[n_seeds][4] = (x, y, z, id), n_seeds <= CLWH_GROW_MAX_SEEDS, id >= 1; duplicates and
+ * several ids on one voxel are allowed; a seed outside D contributes nothing.  With CLWH_GEO_FROM_LABELS every voxel of D whose word
+ * in `seed_labels` (uint32 [Z][Y][X], a plain device buffer, 4-byte aligned) is nonzero is a seed with that word as its id as well;
+ * n_seeds may then be 0.  Without the flag n_seeds == 0 is an error and seed_labels is ignored.
+ * Result.  For p in D: dist(p) = the smallest length of a path from any seed to p (a seed's own voxel: 0); label(p) = the smallest id
+ * among the seeds that attain it.  cap <= 0xFFFF0000 limits the distance (CLWH_DIST_NONE means 0xFFFF0000; any other value above
+ * 0xFFFF0000 is an error): with weights <= 65535 no sum then overflows 32 bits, and a voxel whose distance exceeds the cap counts as
+ * not reached.  Voxels not in D, and voxels of D that no seed reaches within the cap, get dist = CLWH_DIST_NONE and label = 0.
+ * Outputs.  `dist` and `labels`: plain device buffers, 4-byte aligned, uint32 [Z][Y][X] without padding; all X * Y * Z words are
+ * written and nothing behind them.  Either may be NULL, not both.  `labels` may name seed_labels' memory (in place).  *result (HOST,
+ * required): reached, the number of voxels with a finite distance; max_dist, the largest of them (0 when nothing is reached); rounds:
+ * informational, may differ between calls, not part of the contract.
+ * CLWH_GEO_DENSE visits every tile of 16 x 16 x 8 voxels in every round instead of the worklist: same bytes, by the contract.
+ * Limits.  Those of clwh_labels_to_mask: no dim of 0, dims within the projections' rule, X * Y * Z <= 2^31 - 1.
+ * SYNCHRONOUS, like clwh_segment_grow (the host reads the round counters): ordered on the context's stream, returns with everything
+ * written.  No derived data is built or invalidated.  Scratch, kept with the context, holds nothing between calls: the packed 64-bit
+ * keys, 8 * X * Y * Z bytes (1 GiB at 512^3, what clwh_mask_distance keeps), 8 bytes per tile, and the copied seeds.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a domain that breaks grow's rules for
+ * a mask (NULL, an image, not 8-byte aligned); dist and labels both NULL, one of them an image or not 4-byte aligned;
+ * CLWH_GEO_FROM_LABELS with a NULL, image or misaligned seed_labels; unknown flag bits; dims that break the limits; a weight in use
+ * of 0 or above 65535; a cap above 0xFFFF0000 other than CLWH_DIST_NONE; n_seeds > CLWH_GROW_MAX_SEEDS, n_seeds > 0 with NULL
+ * seeds, n_seeds == 0 without CLWH_GEO_FROM_LABELS; a seed outside the volume or with id 0.  CLWH_ERR_SIZE_MISMATCH: a domain smaller
+ * than its layout; dist, labels or (with the flag) seed_labels smaller than 4 * X * Y * Z bytes.  CLWH_ERR_OUT_OF_MEMORY: scratch that
+ * cannot be allocated.  Nothing is written on any of these.  (CLWH_ERR_INTERNAL_OVERFLOW: the iteration passed its hard cap of
+ * X * Y * Z + 2 rounds, which no input can cause: a shortest path crosses fewer tile faces than it has voxels.) */
+enum clwh_geodesic_flags {
+  CLWH_GEO_26 = 1,           /* 26-connectivity instead of 6 */
+  CLWH_GEO_FROM_LABELS = 2,  /* the nonzero words of seed_labels inside D are seeds too */
+  CLWH_GEO_DENSE = 4         /* every tile in every round: same result by contract; for tests and timing */
+};
+#define CLWH_GEO_CAP_MAX 0xFFFF0000u
+typedef struct clwh_geodesic_result {
+  uint64_t reached;
+  uint32_t max_dist;
+  uint32_t rounds;
+} clwh_geodesic_result;
+typedef struct clwh_geodesic_desc {
+  clwh_mem *domain;           /* plain device buffer in the mask layout; read only */
+  clwh_mem *seed_labels;      /* CLWH_GEO_FROM_LABELS: plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *dist;             /* optional plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *labels;           /* optional, the same; may name seed_labels' memory */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t weight_face[3];    /* the step along x, y, z */
+  uint32_t weight_edge[3];    /* CLWH_GEO_26: the step that leaves x, y, z unchanged */
+  uint32_t weight_corner;     /* CLWH_GEO_26 */
+  uint32_t cap;               /* CLWH_DIST_NONE = 0xFFFF0000 */
+  int32_t flags;
+  uint32_t n_seeds;
+  const uint32_t *seeds;      /* host; uint32[n_seeds][4] = x, y, z, id */
+  clwh_geodesic_result *result;  /* host; required */
+} clwh_geodesic_desc;
+int clwh_mask_geodesic(clwh_ctx *ctx, const clwh_geodesic_desc *desc);
+
+/* ---- the path behind a geodesic distance: from `target` back to a seed along a shortest path.  `dist` is a map written by
+ * clwh_mask_geodesic, `labels` (optional) the labelling written with it; dims, weights and CLWH_GEO_26 as in that call.
+ * Definition.  The path starts at the target.  From p with dist(p) > 0 the next point is p + dir for the first direction that
+ * qualifies, the directions running in the order (dz, dy, dx) ascending with dx fastest and those that are not neighbours under the
+ * connectivity skipped: p + dir lies inside the volume, dist(p + dir) != CLWH_DIST_NONE, dist(p + dir) + w(dir) == dist(p), and, if
+ * labels is given, labels(p + dir) == labels(p).  Such a direction always exists for a map of clwh_mask_geodesic.  The path ends at the
+ * first point with dist == 0.
+ * Output.  `points`: a plain device buffer, 4-byte aligned, uint32[capacity][3] = (x, y, z), target first; *n_points (HOST, required)
+ * is the true count and min(n_points, capacity) points are written; points may be NULL when capacity is 0.  A target with
+ * dist == CLWH_DIST_NONE gives n_points = 0 and CLWH_OK.  SYNCHRONOUS; one wave walks the path.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or n_points; a NULL dist, a dist that is an image
+ * or not 4-byte aligned; labels or points that are an image or misaligned, NULL points with capacity > 0; flag bits other than
+ * CLWH_GEO_26; dims that break clwh_mask_geodesic's limits; a weight in use of 0 or above 65535; a target outside the volume.
+ * CLWH_ERR_SIZE_MISMATCH: dist or labels smaller than 4 * X * Y * Z bytes, points smaller than 12 * capacity bytes.  Nothing is
+ * written on any of these.  A map that is not clwh_mask_geodesic's, where no direction qualifies at a point with dist > 0, ends the
+ * path there: the points up to it and *n_points are written and the call returns CLWH_ERR_INVALID_VALUE.  It never loops: every step
+ * strictly lowers dist. */
+typedef struct clwh_geodesic_trace_desc {
+  clwh_mem *dist;             /* plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *labels;           /* optional, the same */
+  clwh_mem *points;           /* plain device buffer, uint32[capacity][3] */
+  uint64_t capacity;
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t weight_face[3];
+  uint32_t weight_edge[3];
+  uint32_t weight_corner;
+  int32_t flags;              /* CLWH_GEO_26 or 0 */
+  uint32_t target[3];         /* x, y, z */
+  uint64_t *n_points;         /* host; required */
+} clwh_geodesic_trace_desc;
+int clwh_geodesic_trace(clwh_ctx *ctx, const clwh_geodesic_trace_desc *desc);
+
 /* ---- measuring a region (not in the reference): once a mask has been grown, dilated, closed, intersected or selected from a
  * labelling, "how many voxels is this now, what is its mean density, where is it, how large is its surface" -- on the device, as exact
  * integers.  A region is a set R of voxels of the volume V[z][y][x] (an S16 3-D image with one channel; the dims come from it).  The
