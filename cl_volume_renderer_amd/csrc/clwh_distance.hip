@@ -9,17 +9,6 @@ using namespace clvr;
 static_assert(sizeof(clwh_distance_desc) == 48 && sizeof(clwh_morph_desc) == 56 && sizeof(clwh_mask_combine_desc) == 40,
               "the descriptors as the Python binding lays them out");
 
-// grow's rules for a mask and its size, label's for a buffer of words and for the dims (clwh_grow.hip, clwh_label.hip)
-static bool mask_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 7u) == 0u; }
-static bool words_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 3u) == 0u; }
-static bool dims_ok(const uint32_t *dims) {
-  const uint64_t X = dims[0], Y = dims[1], Z = dims[2];
-  if (X == 0 || Y == 0 || Z == 0 || X > 0x7FFFFFFFu || Y > 0x7FFFFFFFu || Z > 0x7FFFFFFFu) return false;
-  return X * Y <= 0x7FFFFFFFull && Z <= 0x7FFFFFFFull / (X * Y);  // X * Y * Z <= 2^31 - 1, by division: the product may not fit
-}
-static bool mask_fits(const uint32_t *dims, const clwh_mem *mask) {
-  return mask->bytes / ((((uint64_t)dims[0] + 63u) / 64u) * 8u) >= (uint64_t)dims[1] * dims[2];
-}
 // wx (X - 1)^2 + wy (Y - 1)^2 + wz (Z - 1)^2 <= 2^32 - 2 and no weight of 0; each term by division, the products may not fit
 static bool weights_ok(const uint32_t *dims, const uint32_t *weight) {
   const uint64_t bound = 0xFFFFFFFEull;
@@ -38,7 +27,7 @@ static DistArgs dist_args(const uint32_t *dims, const uint32_t *weight, uint32_t
   a.X = (int32_t)dims[0];
   a.Y = (int32_t)dims[1];
   a.Z = (int32_t)dims[2];
-  a.W64 = (int32_t)((dims[0] + 63u) / 64u);
+  a.W64 = (int32_t)mask_w64(dims[0]);
   for (int q = 0; q < 3; ++q) a.weight[q] = weight[q];
   a.cap = cap == CLWH_DIST_NONE ? ~0ull : (unsigned long long)cap;
   return a;
@@ -55,10 +44,11 @@ extern "C" int clwh_mask_distance(clwh_ctx *ctx, const clwh_distance_desc *d) {
   if (!mask_ok(d->mask)) return CLWH_ERR_INVALID_VALUE;
   if (!words_ok(d->dist)) return CLWH_ERR_INVALID_VALUE;
   if ((d->flags & ~CLWH_DIST_TO_CLEAR) != 0) return CLWH_ERR_INVALID_VALUE;
-  if (!dims_ok(d->dims)) return CLWH_ERR_INVALID_VALUE;
+  const uint64_t X = d->dims[0], Y = d->dims[1], Z = d->dims[2];
+  if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
   if (!weights_ok(d->dims, d->weight)) return CLWH_ERR_INVALID_VALUE;
-  const size_t voxels = (size_t)d->dims[0] * d->dims[1] * d->dims[2];
-  if (!mask_fits(d->dims, d->mask)) return CLWH_ERR_SIZE_MISMATCH;
+  const size_t voxels = (size_t)(X * Y * Z);
+  if (!mask_fits(X, Y, Z, d->mask)) return CLWH_ERR_SIZE_MISMATCH;
   if (d->dist->bytes / 4u < voxels) return CLWH_ERR_SIZE_MISMATCH;
   HIP_TRY(hipSetDevice(ctx->device));
   const DistArgs a = dist_args(d->dims, d->weight, d->cap);
@@ -88,16 +78,17 @@ extern "C" int clwh_mask_morph(clwh_ctx *ctx, const clwh_morph_desc *d) {
   if (!mask_ok(d->mask_in) || !mask_ok(d->mask_out)) return CLWH_ERR_INVALID_VALUE;
   if (d->op < CLWH_MORPH_DILATE || d->op > CLWH_MORPH_CLOSE) return CLWH_ERR_INVALID_VALUE;
   if (d->flags != 0) return CLWH_ERR_INVALID_VALUE;
-  if (!dims_ok(d->dims)) return CLWH_ERR_INVALID_VALUE;
+  const uint64_t X = d->dims[0], Y = d->dims[1], Z = d->dims[2];
+  if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
   if (!weights_ok(d->dims, d->weight)) return CLWH_ERR_INVALID_VALUE;
-  if (!mask_fits(d->dims, d->mask_in) || !mask_fits(d->dims, d->mask_out)) return CLWH_ERR_SIZE_MISMATCH;
+  if (!mask_fits(X, Y, Z, d->mask_in) || !mask_fits(X, Y, Z, d->mask_out)) return CLWH_ERR_SIZE_MISMATCH;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t voxels = (size_t)d->dims[0] * d->dims[1] * d->dims[2];
+  const size_t voxels = (size_t)(X * Y * Z);
   const bool two_steps = d->op == CLWH_MORPH_OPEN || d->op == CLWH_MORPH_CLOSE;
   DistanceScratch &g = ctx->distance;
   CLWH_TRY(g.map_a.reserve(ctx->stream, voxels * 4u));
   CLWH_TRY(g.map_b.reserve(ctx->stream, voxels * 4u));
-  if (two_steps) CLWH_TRY(g.bits.reserve(ctx->stream, (size_t)((d->dims[0] + 63u) / 64u) * 8u * d->dims[1] * d->dims[2]));
+  if (two_steps) CLWH_TRY(g.bits.reserve(ctx->stream, mask_w64(X) * 8u * (size_t)(Y * Z)));
 
   // NONE is farther than any radius: a radius_sq of 0xFFFFFFFF asks for every finite distance, which is what "no cap" computes
   const DistArgs a = dist_args(d->dims, d->weight, d->radius_sq);
@@ -121,11 +112,12 @@ extern "C" int clwh_mask_combine(clwh_ctx *ctx, const clwh_mask_combine_desc *d)
   if (d->op < CLWH_MASK_AND || d->op > CLWH_MASK_NOT) return CLWH_ERR_INVALID_VALUE;
   const bool binary = d->op != CLWH_MASK_NOT;
   if (binary && !mask_ok(d->b)) return CLWH_ERR_INVALID_VALUE;
-  if (!dims_ok(d->dims)) return CLWH_ERR_INVALID_VALUE;
-  if (!mask_fits(d->dims, d->a) || !mask_fits(d->dims, d->out) || (binary && !mask_fits(d->dims, d->b))) return CLWH_ERR_SIZE_MISMATCH;
+  const uint64_t X = d->dims[0], Y = d->dims[1], Z = d->dims[2];
+  if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
+  if (!mask_fits(X, Y, Z, d->a) || !mask_fits(X, Y, Z, d->out) || (binary && !mask_fits(X, Y, Z, d->b))) return CLWH_ERR_SIZE_MISMATCH;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(launch_mask_combine((const unsigned long long *)d->a->dptr, binary ? (const unsigned long long *)d->b->dptr : nullptr,
                               (unsigned long long *)d->out->dptr, (int32_t)d->dims[0], (int32_t)d->dims[1], (int32_t)d->dims[2],
-                              (int32_t)((d->dims[0] + 63u) / 64u), d->op, ctx->stream));
+                              (int32_t)mask_w64(X), d->op, ctx->stream));
   return CLWH_OK;
 }

@@ -219,13 +219,19 @@ struct SdfScratch {
 #endif
 };
 
-// clwh_segment_grow's scratch: the admissible bit image (one bit per voxel in the mask's layout); per tile of 64 x 16 x 16 voxels the round it
-// is to be visited in and its place in the round's list, behind them the round counters and the reduction's result; the copied seeds; and
-// the pinned line the counters and the result travel to the host in.  Every call rewrites what it reads, so nothing here outlives a
-// call: only the allocations are kept, and they go with the context.
-struct GrowScratch {
-  DeviceBuffer admissible, tiles, seeds;
+// a tile worklist's scratch (tile_work_begin): per tile the round it is to be visited in and its place in the round's list, behind them
+// the round counters and the caller's result; the copied seeds; and the pinned line the counters and the result travel to the host in
+struct TileScratch {
+  DeviceBuffer tiles, seeds;
   PinnedWord host;
+};
+
+// clwh_segment_grow's scratch: the admissible bit image (one bit per voxel in the mask's layout) and the worklist of its tiles of
+// 64 x 16 x 16 voxels.  Every call rewrites what it reads, so nothing here outlives a call: only the allocations are kept, and they go
+// with the context.
+struct GrowScratch {
+  DeviceBuffer admissible;
+  TileScratch work;
 };
 
 // clwh_segment_label's scratch: the admissible bit image; the components' sort keys (in | out) and the sort's work space; the three
@@ -242,12 +248,12 @@ struct DistanceScratch {
   DeviceBuffer map_a, map_b, bits;
 };
 
-// clwh_mask_geodesic's and clwh_geodesic_trace's scratch: the packed keys (8 bytes per voxel); per tile of 16 x 16 x 8 voxels the round it
-// is to be visited in and its place in the round's list, behind them the round counters and the result; the copied seeds; and the
-// pinned line the counters and the results travel to the host in.  Every call rewrites what it reads: only the allocations are kept.
+// clwh_mask_geodesic's and clwh_geodesic_trace's scratch: the packed keys (8 bytes per voxel) and the worklist of their tiles of
+// 16 x 16 x 8 voxels, whose pinned line the trace's result travels in too.  Every call rewrites what it reads: only the allocations
+// are kept.
 struct GeodesicScratch {
-  DeviceBuffer keys, tiles, seeds, trace;  // trace: clwh_geodesic_trace's count and verdict
-  PinnedWord host;
+  DeviceBuffer keys, trace;  // trace: clwh_geodesic_trace's count and verdict
+  TileScratch work;
 };
 
 // clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
@@ -405,6 +411,80 @@ inline void env_into_args(RenderArgs &a, const clwh_mem *env) {
   a.env = (const uint32_t *)env->dptr;
   a.env_w = (int32_t)env->dims[0];
   a.env_h = (int32_t)env->dims[1];
+}
+// -- the mask operations' (grow, label, distance, geodesic, region statistics)
+// a mask handle the kernels can use: a plain device buffer whose rows are aligned 64-bit words
+inline bool mask_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 7u) == 0u; }
+// a buffer of 32-bit words: labels, distances, path points
+inline bool words_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 3u) == 0u; }
+// the S16 volume the kernels read or write: an image with memory and no empty axis
+inline bool volume_ok(const clwh_mem *m) {
+  return is_image(m, 3, 1, CLWH_ELEM_S16) && m->dptr && m->dims[0] != 0 && m->dims[1] != 0 && m->dims[2] != 0;
+}
+// voxels are numbered in 31 bits: no dim zero, each below 2^31, X * Y * Z <= 2^31 - 1 (by division: the product may not fit)
+inline bool voxels_fit_31_bits(uint64_t X, uint64_t Y, uint64_t Z) {
+  if (X == 0 || Y == 0 || Z == 0 || X > 0x7FFFFFFFu || Y > 0x7FFFFFFFu || Z > 0x7FFFFFFFu) return false;
+  return X * Y <= 0x7FFFFFFFull && Z <= 0x7FFFFFFFull / (X * Y);
+}
+// 64-bit words per row of a mask; whether the buffer holds the whole mask (dims below 2^31 each; compared by division: the product
+// may not fit)
+inline size_t mask_w64(uint64_t X) { return (size_t)((X + 63u) / 64u); }
+inline bool mask_fits(uint64_t X, uint64_t Y, uint64_t Z, const clwh_mem *mask) { return mask->bytes / (mask_w64(X) * 8u) >= Y * Z; }
+// grow's and label's admissible set: the value window lo <= hi within int16, and the box in voxels, box_hi all zero = the whole
+// volume, lo <= hi <= dim on every axis.  False: CLWH_ERR_INVALID_VALUE.  `empty`: nothing is admissible
+struct ResolvedBox {
+  uint64_t lo[3], hi[3];
+  bool empty;
+};
+inline bool resolve_window_and_box(int32_t lo, int32_t hi, const uint32_t *box_lo, const uint32_t *box_hi, const clwh_mem *vol, ResolvedBox &b) {
+  if (!(lo >= -32768 && lo <= hi && hi <= 32767)) return false;
+  const bool whole = (box_hi[0] | box_hi[1] | box_hi[2]) == 0u;
+  for (int q = 0; q < 3; ++q) {
+    b.lo[q] = box_lo[q];
+    b.hi[q] = whole ? (uint64_t)vol->dims[q] : (uint64_t)box_hi[q];
+    if (!(b.lo[q] <= b.hi[q] && b.hi[q] <= (uint64_t)vol->dims[q])) return false;
+  }
+  b.empty = b.lo[0] == b.hi[0] || b.lo[1] == b.hi[1] || b.lo[2] == b.hi[2];
+  return true;
+}
+// ... and their answer when nothing is admissible: the output all zero, written when the call returns
+inline int clear_and_wait(clwh_ctx *ctx, void *out, size_t bytes) {
+  HIP_TRY(hipMemsetAsync(out, 0, bytes, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return CLWH_OK;
+}
+
+// ---- the tile worklist on the host (TileWork; the protocol is in tile_work_device.hpp).  The caller has set w's TX, TY, TZ and dense.
+// One allocation: stamps | list | counters | result, the counters on a 64-byte line of their own and `result_bytes` for the caller
+// behind them (*result); the seeds' copy and the pinned line beside it.  The stamps are cleared.
+inline int tile_work_begin(clwh_ctx *ctx, TileScratch &g, TileWork &w, size_t seed_bytes, size_t result_bytes, void **result) {
+  const size_t tile_words = ((size_t)w.TX * (size_t)w.TY * (size_t)w.TZ + 15u) & ~(size_t)15u;
+  CLWH_TRY(g.tiles.reserve(ctx->stream, (2u * tile_words + 2u * (size_t)kGrowBatch) * sizeof(uint32_t) + result_bytes));
+  CLWH_TRY(g.seeds.reserve(ctx->stream, seed_bytes > 16u ? seed_bytes : 16u));
+  CLWH_TRY(g.host.ensure());
+  w.stamps = g.tiles.as<uint32_t>();
+  w.list = w.stamps + tile_words;
+  w.counters = w.list + tile_words;
+  *result = w.counters + 2 * kGrowBatch;
+  HIP_TRY(hipMemsetAsync(w.stamps, 0, tile_words * sizeof(uint32_t), ctx->stream));
+  return CLWH_OK;
+}
+// Rounds until one lists no tile, eight to a batch: the pinned line holds eight {listed, ticket} pairs, and a batch that turns out to
+// be longer than the search costs its empty rounds one word read per block.  `enqueue_round(round, slot)` returns a hipError_t.
+// *rounds: the rounds that listed a tile; once they reach `cap` (the caller's bound, which only keeps a defect from spinning) the
+// answer is CLWH_ERR_INTERNAL_OVERFLOW.
+template <class F>
+int tile_work_run(clwh_ctx *ctx, TileScratch &g, const TileWork &w, uint64_t cap, F &&enqueue_round, uint64_t *rounds) {
+  *rounds = 0;
+  for (uint32_t round = 1;; round += (uint32_t)kGrowBatch) {
+    HIP_TRY(hipMemsetAsync(w.counters, 0, 2u * (size_t)kGrowBatch * sizeof(uint32_t), ctx->stream));
+    for (int slot = 0; slot < kGrowBatch; ++slot) HIP_TRY(enqueue_round(round + (uint32_t)slot, slot));
+    HIP_TRY(hipMemcpyAsync(g.host.ptr, w.counters, 2u * (size_t)kGrowBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int slot = 0; slot < kGrowBatch; ++slot) *rounds += g.host.ptr[2 * slot] != 0u;
+    if (g.host.ptr[2 * (kGrowBatch - 1)] == 0u) return CLWH_OK;  // the batch's last round listed nothing: converged
+    if (*rounds >= cap) return CLWH_ERR_INTERNAL_OVERFLOW;
+  }
 }
 
 // ---- the derived data the views and the mesher share (clwh_views.hip): the bricked copy of `volume` and its {min, max} table, which

@@ -511,6 +511,16 @@ hipError_t launch_mesh_fill(const MeshArgs &a, hipStream_t s);  // k_mesh_vertic
 // image A) hold a row of the volume as W64 = ceil(X / 64) 64-bit words, row (z * Y + y); the volume is cut into tiles of 64 x 16 x 16
 // voxels, tile (tx, ty, tz) at (tz * TY + ty) * TX + tx: one word of each of its 256 rows.
 constexpr int kGrowBatch = 8;  // rounds enqueued between two reads of the device's counters: {listed, ticket} x 8 = the 64 pinned bytes
+// the tile worklist of a search that runs in rounds (grow's and the geodesic maps'; the protocol is in tile_work_device.hpp)
+struct TileWork {
+  int32_t TX, TY, TZ;          // the grid of tiles
+  int32_t dense;               // CLWH_GROW_DENSE, CLWH_GEO_DENSE: one stamped tile lists them all
+  uint32_t *stamps;            // per tile: the round (1, 2, ...) in which it is to be visited
+  uint32_t *list;              // the tiles of the round being run
+  uint32_t *counters;          // kGrowBatch x {tiles listed, ticket}
+};
+// k_tile_list (tile_work_kernels.hip) into counters[2 * slot]; launch_tile_round, its one caller, asks for the error behind both launches
+void enqueue_tile_list(const TileWork &w, uint32_t round, int slot, hipStream_t s);
 struct GrowDeviceResult {      // what k_grow_reduce accumulates (grow_result_identity: the start values)
   unsigned long long count, sum, sum_sq;  // sum: int64 in two's complement
   int32_t vmin, vmax;
@@ -521,20 +531,17 @@ struct GrowArgs {
   unsigned long long *mask;    // R
   unsigned long long *adm;     // A
   int32_t X, Y, Z, W64;
-  int32_t TX, TY, TZ;
   int32_t lo, hi;              // the window
   int32_t box_lo[3], box_hi[3];
-  int32_t conn26, from_mask, dense;
-  uint32_t *stamps;            // per tile: the round (1, 2, ...) in which it is to be visited
-  uint32_t *list;              // the tiles of the round being run
-  uint32_t *counters;          // kGrowBatch x {tiles listed, ticket}
+  int32_t conn26, from_mask;
+  TileWork tiles;
   const uint32_t *seeds;       // device copy, uint32[n_seeds][3]
   uint32_t n_seeds;
   GrowDeviceResult *result;
 };
 hipError_t launch_grow_admissible(const GrowArgs &a, hipStream_t s);  // A; mask &= A or mask = 0; stamps of the tiles that hold a bit
 hipError_t launch_grow_seeds(const GrowArgs &a, hipStream_t s);
-hipError_t launch_grow_round(const GrowArgs &a, uint32_t round, int slot, hipStream_t s);  // k_grow_list + k_grow_round, counters[2 * slot]
+hipError_t launch_grow_round(const GrowArgs &a, uint32_t round, int slot, hipStream_t s);  // k_tile_list + k_grow_round, counters[2 * slot]
 hipError_t launch_grow_reduce(const GrowArgs &a, hipStream_t s);
 hipError_t launch_apply_mask(const int16_t *in, int16_t *out, const unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64,
                              int32_t fill, int32_t invert, hipStream_t s);
@@ -604,13 +611,10 @@ struct GeoArgs {
   unsigned long long *keys;    // scratch, one per voxel
   uint32_t *dist, *labels;     // the caller's maps; either may be null
   int32_t X, Y, Z, W64;
-  int32_t TX, TY, TZ;
   uint32_t w_face[3], w_edge[3], w_corner;  // the edge's index is the axis that does not change
   uint32_t cap;                // <= 0xFFFF0000
-  int32_t conn26, dense;
-  uint32_t *stamps;            // per tile: the round (1, 2, ...) in which it is to be visited
-  uint32_t *list;              // the tiles of the round being run
-  uint32_t *counters;          // kGrowBatch x {tiles listed, ticket}
+  int32_t conn26;
+  TileWork tiles;
   const uint32_t *seeds;       // device copy, uint32[n_seeds][4] = x, y, z, id
   uint32_t n_seeds;
   GeoDeviceResult *result;
@@ -630,7 +634,7 @@ struct GeoTraceArgs {
   GeoTraceResult *result;
 };
 hipError_t launch_geo_init(const GeoArgs &a, hipStream_t s);  // every key, the listed seeds, the stamps of the tiles that hold a seed
-hipError_t launch_geo_round(const GeoArgs &a, uint32_t round, int slot, hipStream_t s);  // k_geo_list + k_geo_round, counters[2 * slot]
+hipError_t launch_geo_round(const GeoArgs &a, uint32_t round, int slot, hipStream_t s);  // k_tile_list + k_geo_round, counters[2 * slot]
 hipError_t launch_geo_finish(const GeoArgs &a, hipStream_t s);  // dist, labels, *result
 hipError_t launch_geo_trace(const GeoTraceArgs &a, hipStream_t s);
 

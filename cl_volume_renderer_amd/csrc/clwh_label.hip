@@ -8,34 +8,17 @@ using namespace clvr;
 
 static_assert(sizeof(clwh_label_component) == 48 && sizeof(LabelRecord) == 48, "the table's record is 48 bytes");
 
-// grow's rules for a mask, a volume and the mask's size (clwh_grow.hip)
-static bool mask_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 7u) == 0u; }
-static bool volume_ok(const clwh_mem *m) {
-  return is_image(m, 3, 1, CLWH_ELEM_S16) && m->dptr && m->dims[0] != 0 && m->dims[1] != 0 && m->dims[2] != 0;
-}
-static bool labels_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 3u) == 0u; }
-// X * Y * Z <= 2^31 - 1, by division: the product may not fit (dims below 2^31 each and none zero)
-static bool voxels_fit_31_bits(uint64_t X, uint64_t Y, uint64_t Z) { return X * Y <= 0x7FFFFFFFull && Z <= 0x7FFFFFFFull / (X * Y); }
-static bool mask_fits(uint64_t X, uint64_t Y, uint64_t Z, const clwh_mem *mask) { return mask->bytes / (((X + 63u) / 64u) * 8u) >= Y * Z; }
-
 extern "C" int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *d) {
   if (!ctx || !d || !d->result) return CLWH_ERR_INVALID_VALUE;
   if (!volume_ok(d->volume)) return CLWH_ERR_INVALID_VALUE;
-  if (!labels_ok(d->labels)) return CLWH_ERR_INVALID_VALUE;
+  if (!words_ok(d->labels)) return CLWH_ERR_INVALID_VALUE;
   if (d->components ? !mask_ok(d->components) : d->component_capacity > 0) return CLWH_ERR_INVALID_VALUE;  // (a mask's rule: plain, 8-byte aligned)
   const bool from_mask = (d->flags & CLWH_LABEL_FROM_MASK) != 0;
   if (from_mask && !mask_ok(d->mask)) return CLWH_ERR_INVALID_VALUE;
   if ((d->flags & ~(CLWH_LABEL_26 | CLWH_LABEL_FROM_MASK)) != 0) return CLWH_ERR_INVALID_VALUE;
-  if (!(d->lo >= -32768 && d->lo <= d->hi && d->hi <= 32767)) return CLWH_ERR_INVALID_VALUE;
   const clwh_mem *vol = d->volume;
-  const bool whole = (d->box_hi[0] | d->box_hi[1] | d->box_hi[2]) == 0u;
-  uint64_t lo[3], hi[3];
-  for (int q = 0; q < 3; ++q) {
-    lo[q] = d->box_lo[q];
-    hi[q] = whole ? (uint64_t)vol->dims[q] : (uint64_t)d->box_hi[q];
-    if (!(lo[q] <= hi[q] && hi[q] <= (uint64_t)vol->dims[q])) return CLWH_ERR_INVALID_VALUE;
-  }
-  if (!dims_fit_int32(vol)) return CLWH_ERR_INVALID_VALUE;
+  ResolvedBox box;
+  if (!resolve_window_and_box(d->lo, d->hi, d->box_lo, d->box_hi, vol, box)) return CLWH_ERR_INVALID_VALUE;
   const uint64_t X = vol->dims[0], Y = vol->dims[1], Z = vol->dims[2];
   if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
   const uint64_t voxels = X * Y * Z;
@@ -46,15 +29,14 @@ extern "C" int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *d) {
   HIP_TRY(hipSetDevice(ctx->device));
   clwh_label_result out;
   std::memset(&out, 0, sizeof out);
-  if (lo[0] == hi[0] || lo[1] == hi[1] || lo[2] == hi[2]) {  // nothing is admissible
-    HIP_TRY(hipMemsetAsync(d->labels->dptr, 0, voxels * 4u, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (box.empty) {
+    CLWH_TRY(clear_and_wait(ctx, d->labels->dptr, voxels * 4u));
     *d->result = out;
     return CLWH_OK;
   }
 
   LabelScratch &g = ctx->label;
-  const size_t W64 = (size_t)((X + 63u) / 64u);
+  const size_t W64 = mask_w64(X);
   CLWH_TRY(g.admissible.reserve(ctx->stream, W64 * 8u * Y * Z));
   CLWH_TRY(g.counters.reserve(ctx->stream, 64));
   CLWH_TRY(g.host.ensure());
@@ -72,8 +54,8 @@ extern "C" int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *d) {
   a.lo = d->lo;
   a.hi = d->hi;
   for (int q = 0; q < 3; ++q) {
-    a.box_lo[q] = (int32_t)lo[q];
-    a.box_hi[q] = (int32_t)hi[q];
+    a.box_lo[q] = (int32_t)box.lo[q];
+    a.box_hi[q] = (int32_t)box.hi[q];
   }
   a.conn26 = (d->flags & CLWH_LABEL_26) != 0;
   a.counters = g.counters.as<unsigned long long>();
@@ -88,8 +70,7 @@ extern "C" int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *d) {
   out.n_voxels = counts[1];
   out.passes = 4;
   if (counts[0] == 0) {
-    HIP_TRY(hipMemsetAsync(d->labels->dptr, 0, voxels * 4u, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    CLWH_TRY(clear_and_wait(ctx, d->labels->dptr, voxels * 4u));
     *d->result = out;
     return CLWH_OK;
   }
@@ -114,16 +95,15 @@ extern "C" int clwh_segment_label(clwh_ctx *ctx, const clwh_label_desc *d) {
 
 extern "C" int clwh_labels_to_mask(clwh_ctx *ctx, const clwh_labels_to_mask_desc *d) {
   if (!ctx || !d) return CLWH_ERR_INVALID_VALUE;
-  if (!labels_ok(d->labels)) return CLWH_ERR_INVALID_VALUE;
+  if (!words_ok(d->labels)) return CLWH_ERR_INVALID_VALUE;
   if (!mask_ok(d->mask)) return CLWH_ERR_INVALID_VALUE;
   const uint64_t X = d->dims[0], Y = d->dims[1], Z = d->dims[2];
-  if (X == 0 || Y == 0 || Z == 0 || X > 0x7FFFFFFFu || Y > 0x7FFFFFFFu || Z > 0x7FFFFFFFu) return CLWH_ERR_INVALID_VALUE;
   if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
   if (d->rank_lo == 0u || d->rank_lo > d->rank_hi) return CLWH_ERR_INVALID_VALUE;
   if (d->labels->bytes / 4u < X * Y * Z) return CLWH_ERR_SIZE_MISMATCH;
   if (!mask_fits(X, Y, Z, d->mask)) return CLWH_ERR_SIZE_MISMATCH;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(launch_labels_to_mask((const uint32_t *)d->labels->dptr, (unsigned long long *)d->mask->dptr, (int32_t)X, (int32_t)Y, (int32_t)Z,
-                                (int32_t)((X + 63u) / 64u), d->rank_lo, d->rank_hi, ctx->stream));
+                                (int32_t)mask_w64(X), d->rank_lo, d->rank_hi, ctx->stream));
   return CLWH_OK;
 }

@@ -10,22 +10,6 @@ static_assert(sizeof(clwh_region_stats) == 104 && sizeof(clwh_mask_stats_result)
                   sizeof(clwh_label_stats_desc) == 40,
               "the record and the descriptors as the Python binding lays them out");
 
-// grow's rules for a mask and a volume, label's for a buffer of words and for the dims (clwh_grow.hip, clwh_label.hip)
-static bool mask_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 7u) == 0u; }
-static bool words_ok(const clwh_mem *m) { return is_plain_buffer(m) && ((uintptr_t)m->dptr & 3u) == 0u; }
-static bool volume_ok(const clwh_mem *m) {
-  return is_image(m, 3, 1, CLWH_ELEM_S16) && m->dptr && m->dims[0] != 0 && m->dims[1] != 0 && m->dims[2] != 0;
-}
-static bool dims_ok(const clwh_mem *vol) {  // X * Y * Z <= 2^31 - 1, by division: the product may not fit
-  if (!dims_fit_int32(vol)) return false;
-  const uint64_t X = vol->dims[0], Y = vol->dims[1], Z = vol->dims[2];
-  return X * Y <= 0x7FFFFFFFull && Z <= 0x7FFFFFFFull / (X * Y);
-}
-static size_t mask_w64(const clwh_mem *volume) { return (volume->dims[0] + 63u) / 64u; }
-static bool mask_fits(const clwh_mem *volume, const clwh_mem *mask) {
-  return mask->bytes / (mask_w64(volume) * 8u) >= volume->dims[1] * volume->dims[2];
-}
-
 extern "C" int clwh_mask_statistics(clwh_ctx *ctx, const clwh_mask_stats_desc *d) {
   if (!ctx || !d || !d->result) return CLWH_ERR_INVALID_VALUE;
   if (!volume_ok(d->volume)) return CLWH_ERR_INVALID_VALUE;
@@ -38,8 +22,8 @@ extern "C" int clwh_mask_statistics(clwh_ctx *ctx, const clwh_mask_stats_desc *d
     return CLWH_ERR_INVALID_VALUE;
   }
   const clwh_mem *vol = d->volume;
-  if (!dims_ok(vol)) return CLWH_ERR_INVALID_VALUE;
-  if (!mask_fits(vol, d->mask)) return CLWH_ERR_SIZE_MISMATCH;
+  if (!voxels_fit_31_bits(vol->dims[0], vol->dims[1], vol->dims[2])) return CLWH_ERR_INVALID_VALUE;
+  if (!mask_fits(vol->dims[0], vol->dims[1], vol->dims[2], d->mask)) return CLWH_ERR_SIZE_MISMATCH;
   if (d->hist && d->hist->bytes / 8u < (size_t)d->n_bins) return CLWH_ERR_SIZE_MISMATCH;
 
   HIP_TRY(hipSetDevice(ctx->device));
@@ -54,7 +38,7 @@ extern "C" int clwh_mask_statistics(clwh_ctx *ctx, const clwh_mask_stats_desc *d
   a.X = (int32_t)vol->dims[0];
   a.Y = (int32_t)vol->dims[1];
   a.Z = (int32_t)vol->dims[2];
-  a.W64 = (int32_t)mask_w64(vol);
+  a.W64 = (int32_t)mask_w64(vol->dims[0]);
   a.result = &dev->stats;
   a.tails = reinterpret_cast<unsigned long long *>(&dev->hist_below);
   if (d->hist) {
@@ -83,7 +67,7 @@ extern "C" int clwh_label_statistics(clwh_ctx *ctx, const clwh_label_stats_desc 
   if (d->capacity < 1u || d->capacity > (1ull << 24)) return CLWH_ERR_INVALID_VALUE;
   if (d->flags != 0) return CLWH_ERR_INVALID_VALUE;
   const clwh_mem *vol = d->volume;
-  if (!dims_ok(vol)) return CLWH_ERR_INVALID_VALUE;
+  if (!voxels_fit_31_bits(vol->dims[0], vol->dims[1], vol->dims[2])) return CLWH_ERR_INVALID_VALUE;
   const size_t voxels = vol->dims[0] * vol->dims[1] * vol->dims[2];
   if (d->labels->bytes / 4u < voxels) return CLWH_ERR_SIZE_MISMATCH;
   if (d->stats->bytes / sizeof(clwh_region_stats) < d->capacity) return CLWH_ERR_SIZE_MISMATCH;

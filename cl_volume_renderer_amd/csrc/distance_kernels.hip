@@ -15,7 +15,7 @@
 // is one voxel, a wave 64 consecutive x, so every load and store of a step is one coalesced 256-byte row.
 // Integers only.  A finite value is at most 2^32 - 2 (the weights' rule), NONE = 2^32 - 1 is "no site (within cap)"; NONE is widened
 // to an infinity of 64 bits before anything is added to it, and every sum and product is 64-bit.
-#include "clwh_internal.hpp"
+#include "mask_device.hpp"
 
 namespace clvr {
 
@@ -205,10 +205,6 @@ __global__ __launch_bounds__(256) void k_mask_combine(const u64 *a, const u64 *b
   if ((X & 63) != 0 && id % (size_t)W64 == (size_t)(W64 - 1)) v &= (1ull << (X & 63)) - 1ull;
   out[id] = v;
 }
-
-namespace {
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255u) / 256u); }
-}  // namespace
 
 hipError_t launch_dist_rows(const DistArgs &a, const unsigned long long *mask, uint32_t *out, int32_t flip, hipStream_t s) {
   const size_t rows = (size_t)a.Y * (size_t)a.Z;

@@ -24,7 +24,7 @@
 // 64 x 16 x 16 would need 128 KiB; 32 x 8 x 8, 64 x 4 x 8 and 32 x 8 x 16 were timed and lost: DESIGN.md, section 4).  A thread owns the column of 8 voxels along z at its (x, y), in registers.  Voxels outside D hold
 // the all-ones key, voxels of D that nothing has reached yet hold kUnreached: neither is ever a candidate (their distance field is
 // above every cap), and a voxel takes candidates iff its key is not all ones.
-#include "clwh_internal.hpp"
+#include "tile_work_device.hpp"
 
 namespace clvr {
 
@@ -46,7 +46,7 @@ __device__ __forceinline__ u64 geo_step(u64 k, uint32_t w, uint32_t cap) {
   return (c < k || (uint32_t)(c >> 32) > cap) ? kOutside : c;
 }
 __device__ __forceinline__ uint32_t geo_tile_of(const GeoArgs &a, int x, int y, int z) {
-  return (uint32_t)(((z / kGZ) * a.TY + (y / kGY)) * a.TX + (x / kGX));
+  return (uint32_t)(((z / kGZ) * a.tiles.TY + (y / kGY)) * a.tiles.TX + (x / kGX));
 }
 __device__ __forceinline__ size_t geo_voxel(const GeoArgs &a, int x, int y, int z) {
   return ((size_t)z * (size_t)a.Y + (size_t)y) * (size_t)a.X + (size_t)x;
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_geo_init(const GeoArgs a) {
     const uint32_t word = a.seed_labels ? a.seed_labels[id] : 0u;
     if (word) {
       key = (u64)word;
-      a.stamps[geo_tile_of(a, x, y, z)] = 1u;
+      a.tiles.stamps[geo_tile_of(a, x, y, z)] = 1u;
     }
   }
   a.keys[id] = key;
@@ -82,42 +82,22 @@ __global__ __launch_bounds__(256) void k_geo_seeds(const GeoArgs a) {
   u64 *key = a.keys + geo_voxel(a, x, y, z);
   if (*key == kOutside) return;  // (nobody turns a key into all ones or back)
   atomicMin(key, (u64)a.seeds[4u * i + 3u]);
-  a.stamps[geo_tile_of(a, x, y, z)] = 1u;
+  a.tiles.stamps[geo_tile_of(a, x, y, z)] = 1u;
 }
 
-// grow's list: the tiles stamped for `round` into the list of counter slot `slot`; CLWH_GEO_DENSE: one stamped tile lists them all
-__global__ __launch_bounds__(256) void k_geo_list(const GeoArgs a, uint32_t round, int slot) {
-  if (slot > 0 && a.counters[2 * (slot - 1)] == 0u) return;
-  const uint32_t n_tiles = (uint32_t)(a.TX * a.TY * a.TZ), i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n_tiles || a.stamps[i] != round) return;
-  if (a.dense) a.counters[2 * slot] = n_tiles;  // (the same value from every writer)
-  else a.list[atomicAdd(&a.counters[2 * slot], 1u)] = i;
-}
-
-// One round: a persistent grid takes the listed tiles by ticket; see the head of the file.
+// One round: a persistent grid takes the listed tiles by ticket; see the head of the file and tile_work_device.hpp.
 template <bool CONN26>
 __global__ __launch_bounds__(256) void k_geo_round(const GeoArgs a, uint32_t round, int slot) {
   __shared__ u64 s_key[kLZ * kLY * kLX];  // [z + 1][y + 1][x + 1]
-  __shared__ uint32_t s_ticket, s_wake;
-  const uint32_t n = a.counters[2 * slot];
+  __shared__ TileShared s_tile;
+  const uint32_t n = a.tiles.counters[2 * slot];
   if (n == 0u) return;  // an empty round: one word read
   const unsigned t = threadIdx.x;
   const int cx = (int)(t % (unsigned)kGX), cy = (int)(t / (unsigned)kGX);
   const uint32_t cap = a.cap;
   const uint32_t wfx = a.w_face[0], wfy = a.w_face[1], wfz = a.w_face[2];
   u64 *const mine = s_key + (kLY + cy + 1) * kLX + (cx + 1);  // the column's voxel z = 0; a z step is kLY * kLX words
-  for (;;) {
-    __syncthreads();  // the previous tile's last reads of s_wake, s_ticket and s_key
-    if (t == 0u) {
-      s_ticket = atomicAdd(&a.counters[2 * slot + 1], 1u);
-      s_wake = 0u;
-    }
-    __syncthreads();
-    const uint32_t ticket = s_ticket;
-    if (ticket >= n) break;
-    const uint32_t tile = a.dense ? ticket : a.list[ticket];
-    const int tx = (int)(tile % (uint32_t)a.TX), ty = (int)((tile / (uint32_t)a.TX) % (uint32_t)a.TY), tz = (int)(tile / (uint32_t)(a.TX * a.TY));
-
+  for (int tx, ty, tz; tile_take(a.tiles, n, slot, s_tile, tx, ty, tz);) {  // (its first barrier: the previous tile's last reads of s_key)
     // the region's keys; what lies outside the volume is outside D
     for (unsigned i = t; i < (unsigned)(kLZ * kLY * kLX); i += 256u) {
       const int lz = (int)(i / (unsigned)(kLY * kLX)), rem = (int)(i % (unsigned)(kLY * kLX)), ly = rem / kLX, lx = rem % kLX;
@@ -198,31 +178,15 @@ __global__ __launch_bounds__(256) void k_geo_round(const GeoArgs a, uint32_t rou
 #pragma unroll
     for (int z = 0; z < kGZ; ++z)
       if ((lowered >> z) & 1u) geo_store(a.keys + geo_voxel(a, gx, gy, tz * kGZ + z), k[z]);
-    // the neighbouring tiles that can see a lowered key are visited in the next round.  Round 1 counts every real key as lowered: the
-    // seeds were stored by other kernels, and nobody has looked at them from the other side of a tile face yet
+    // the neighbouring tiles that can see a lowered key are woken; round 1 counts every real key as lowered
     uint32_t fresh = lowered;
     if (round == 1u) {
 #pragma unroll
       for (int z = 0; z < kGZ; ++z) fresh |= (uint32_t)(k[z] >> 32) != 0xFFFFFFFFu ? 1u << z : 0u;
     }
-    if (fresh) {
-      const bool at_x[3] = {cx == 0, true, cx == kGX - 1}, at_y[3] = {cy == 0, true, cy == kGY - 1};
-      const bool at_z[3] = {(fresh & 1u) != 0u, true, ((fresh >> (kGZ - 1)) & 1u) != 0u};
-      uint32_t wake = 0u;
-#pragma unroll
-      for (int q = 0; q < 27; ++q) {
-        const int dx = q % 3, dy = (q / 3) % 3, dz = q / 9;
-        const int moved = (dx != 1) + (dy != 1) + (dz != 1);
-        if (moved == 0 || (!CONN26 && moved != 1)) continue;  // an edge or corner neighbour is adjacent only under 26-connectivity
-        if (at_x[dx] && at_y[dy] && at_z[dz]) wake |= 1u << q;
-      }
-      if (wake) atomicOr(&s_wake, wake);
-    }
-    __syncthreads();
-    if (t < 27u && ((s_wake >> t) & 1u)) {
-      const int nx = tx + (int)(t % 3u) - 1, ny = ty + (int)((t / 3u) % 3u) - 1, nz = tz + (int)(t / 9u) - 1;
-      if (nx >= 0 && nx < a.TX && ny >= 0 && ny < a.TY && nz >= 0 && nz < a.TZ) a.stamps[((size_t)nz * a.TY + ny) * a.TX + nx] = round + 1u;
-    }
+    const bool at_x[3] = {cx == 0, true, cx == kGX - 1}, at_y[3] = {cy == 0, true, cy == kGY - 1};
+    const bool at_z[3] = {(fresh & 1u) != 0u, true, ((fresh >> (kGZ - 1)) & 1u) != 0u};
+    tile_wake<CONN26>(a.tiles, round, s_tile, tx, ty, tz, fresh != 0u, at_x, at_y, at_z);
   }
 }
 
@@ -315,10 +279,6 @@ __global__ __launch_bounds__(64) void k_geo_trace(const GeoTraceArgs a) {
   }
 }
 
-namespace {
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255u) / 256u); }
-}  // namespace
-
 hipError_t launch_geo_init(const GeoArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_geo_init, dim3(blocks_for((size_t)a.X * (size_t)a.Y * (size_t)a.Z)), dim3(256), 0, s, a);
   if (a.n_seeds != 0u) hipLaunchKernelGGL(k_geo_seeds, dim3(blocks_for(a.n_seeds)), dim3(256), 0, s, a);
@@ -326,12 +286,8 @@ hipError_t launch_geo_init(const GeoArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_geo_round(const GeoArgs &a, uint32_t round, int slot, hipStream_t s) {
-  const size_t n_tiles = (size_t)a.TX * (size_t)a.TY * (size_t)a.TZ;
-  hipLaunchKernelGGL(k_geo_list, dim3(blocks_for(n_tiles)), dim3(256), 0, s, a, round, slot);
-  // five blocks per CU hold their 26 KB of LDS each with room to spare; fewer tiles need fewer blocks
-  const unsigned grid = (unsigned)(n_tiles < 1280u ? n_tiles : 1280u);
-  hipLaunchKernelGGL(a.conn26 ? k_geo_round<true> : k_geo_round<false>, dim3(grid), dim3(256), 0, s, a, round, slot);
-  return hipGetLastError();
+  // five blocks per CU hold their 26 KB of LDS each with room to spare
+  return launch_tile_round(a.conn26 ? k_geo_round<true> : k_geo_round<false>, 1280u, a, round, slot, s);
 }
 
 hipError_t launch_geo_finish(const GeoArgs &a, hipStream_t s) {

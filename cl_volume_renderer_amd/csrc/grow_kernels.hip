@@ -10,7 +10,7 @@
 //   set; and an owner whose boundary changed stamps the reader for the next round, which starts behind a kernel boundary.  So every
 //   stored set lies between the seeds and the least fixpoint, and when a round lists no tile every tile is at its local fixpoint with
 //   the halos it would read now: the global fixpoint.  No result depends on the order of blocks, and no block waits for another.
-#include "clwh_internal.hpp"
+#include "tile_work_device.hpp"
 
 namespace clvr {
 
@@ -19,66 +19,38 @@ namespace {
 typedef unsigned long long u64;
 constexpr int kTile = 16;  // rows of a tile along y and along z
 
-// the eight voxels of one 16-byte load
-__device__ __forceinline__ void grow_load8(const int16_t *p, int (&v)[8]) {
-  const uint4 q = *reinterpret_cast<const uint4 *>(p);
-  const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int h = 0; h < 8; ++h) v[h] = (int)(int16_t)(w[h >> 1] >> (16 * (h & 1)));
-}
-
 __device__ __forceinline__ uint32_t grow_tile_of(const GrowArgs &a, int x, int y, int z) {
-  return (uint32_t)(((z >> 4) * a.TY + (y >> 4)) * a.TX + (x >> 6));
-}
-
-__device__ __forceinline__ bool grow_in_window_and_box(const GrowArgs &a, int v, int x) {
-  return v >= a.lo && v <= a.hi && x >= a.box_lo[0] && x < a.box_hi[0];
+  return (uint32_t)(((z >> 4) * a.tiles.TY + (y >> 4)) * a.tiles.TX + (x >> 6));
 }
 
 }  // namespace
 
 // A, and the mask's start: mask &= A (CLWH_GROW_FROM_MASK; a tile that keeps a bit is stamped for round 1) or mask = 0.  Rows of a
-// multiple of 8 voxels: a lane classifies the 8 voxels of one 16-byte load and owns one byte of both bit images (k_sdfbit_events8's
-// shape); the bytes at x >= X are the padding and become zero.
+// multiple of 8 voxels: a lane owns one byte of both bit images (admissible_byte).
 __global__ __launch_bounds__(256) void k_grow_admissible8(const GrowArgs a) {
-  const size_t bytes_per_row = (size_t)a.W64 * 8u, total = bytes_per_row * (size_t)a.Y * (size_t)a.Z;
-  const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+  const size_t total = (size_t)a.W64 * 8u * (size_t)a.Y * (size_t)a.Z, id = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (id >= total) return;
-  const size_t row = id / bytes_per_row;
-  const int x0 = (int)(id - row * bytes_per_row) * 8;
-  const int z = (int)(row / (size_t)a.Y), y = (int)(row - (size_t)z * (size_t)a.Y);
-  uint32_t bits = 0u;
-  if (x0 < a.X && y >= a.box_lo[1] && y < a.box_hi[1] && z >= a.box_lo[2] && z < a.box_hi[2]) {  // X is a multiple of 8: all eight exist
-    int v[8];
-    grow_load8(a.volume + row * (size_t)a.X + (size_t)x0, v);
-#pragma unroll
-    for (int h = 0; h < 8; ++h) bits |= grow_in_window_and_box(a, v[h], x0 + h) ? (1u << h) : 0u;
-  }
+  int x0, y, z;
+  const uint32_t bits = admissible_byte(a, id, x0, y, z);
   reinterpret_cast<uint8_t *>(a.adm)[id] = (uint8_t)bits;
   uint8_t *mask = reinterpret_cast<uint8_t *>(a.mask);
   const uint32_t m = a.from_mask ? ((uint32_t)mask[id] & bits) : 0u;
   mask[id] = (uint8_t)m;
-  if (m) a.stamps[grow_tile_of(a, x0, y, z)] = 1u;
+  if (m) a.tiles.stamps[grow_tile_of(a, x0, y, z)] = 1u;
 }
 
-// the same for any row length: a thread per voxel of the padded row, a wave per 64-bit word (k_sdfbit_events' shape)
+// the same for any row length: a thread per voxel of the padded row, a wave per 64-bit word (admissible_voxel)
 __global__ __launch_bounds__(256) void k_grow_admissible(const GrowArgs a) {
-  const size_t padded = (size_t)a.W64 * 64u, total = padded * (size_t)a.Y * (size_t)a.Z;
-  const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+  const size_t total = (size_t)a.W64 * 64u * (size_t)a.Y * (size_t)a.Z, id = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (id >= total) return;  // (whole waves: `total` and a wave's first id are multiples of 64)
-  const size_t row = id / padded;
-  const int x = (int)(id - row * padded);
-  const int z = (int)(row / (size_t)a.Y), y = (int)(row - (size_t)z * (size_t)a.Y);
-  bool in = false;
-  if (x < a.X && y >= a.box_lo[1] && y < a.box_hi[1] && z >= a.box_lo[2] && z < a.box_hi[2])
-    in = grow_in_window_and_box(a, (int)a.volume[row * (size_t)a.X + (size_t)x], x);
-  const u64 bits = __ballot(in);
+  int x, y, z;
+  const u64 bits = __ballot(admissible_voxel(a, id, x, y, z));
   if ((threadIdx.x & 63u) == 0u) {
     const size_t w = id >> 6;
     a.adm[w] = bits;
     const u64 m = a.from_mask ? (a.mask[w] & bits) : 0ull;
     a.mask[w] = m;
-    if (m) a.stamps[grow_tile_of(a, x, y, z)] = 1u;
+    if (m) a.tiles.stamps[grow_tile_of(a, x, y, z)] = 1u;
   }
 }
 
@@ -91,18 +63,8 @@ __global__ __launch_bounds__(256) void k_grow_seeds(const GrowArgs a) {
   const u64 bit = 1ull << (x & 63);
   if (a.adm[w] & bit) {
     atomicOr(&a.mask[w], bit);
-    a.stamps[grow_tile_of(a, x, y, z)] = 1u;
+    a.tiles.stamps[grow_tile_of(a, x, y, z)] = 1u;
   }
-}
-
-// the tiles stamped for `round` into the list of counter slot `slot`; CLWH_GROW_DENSE: one stamped tile lists them all (the round kernel
-// then takes the ticket itself for the tile).  A round behind an empty one has nothing to list.
-__global__ __launch_bounds__(256) void k_grow_list(const GrowArgs a, uint32_t round, int slot) {
-  if (slot > 0 && a.counters[2 * (slot - 1)] == 0u) return;
-  const uint32_t n_tiles = (uint32_t)(a.TX * a.TY * a.TZ), i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n_tiles || a.stamps[i] != round) return;
-  if (a.dense) a.counters[2 * slot] = n_tiles;  // (the same value from every writer)
-  else a.list[atomicAdd(&a.counters[2 * slot], 1u)] = i;
 }
 
 namespace {
@@ -144,29 +106,18 @@ __device__ __forceinline__ u64 grow_dilate_x(const GrowRow &r) { return r.word |
 
 }  // namespace
 
-// One round: a persistent grid takes the listed tiles by ticket; see the head of the file.
+// One round: a persistent grid takes the listed tiles by ticket; see the head of the file and tile_work_device.hpp.
 template <bool CONN26>
 __global__ __launch_bounds__(256) void k_grow_round(const GrowArgs a, uint32_t round, int slot) {
   // 6: the region's rows of R; 26: the same dilated along x.  [rz + 1][ry + 1]
   __shared__ u64 lx[kTile + 2][kTile + 2];
   __shared__ u64 ly[kTile + 2][kTile];  // 26 only: lx dilated along y, [rz + 1][ry]
-  __shared__ uint32_t s_ticket, s_wake;
-  const uint32_t n = a.counters[2 * slot];
+  __shared__ TileShared s_tile;
+  const uint32_t n = a.tiles.counters[2 * slot];
   if (n == 0u) return;  // an empty round: one word read
   const unsigned t = threadIdx.x;
   const int cy = (int)(t & 15u), cz = (int)(t >> 4);
-  for (;;) {
-    __syncthreads();  // the previous tile's last reads of s_wake and s_ticket
-    if (t == 0u) {
-      s_ticket = atomicAdd(&a.counters[2 * slot + 1], 1u);
-      s_wake = 0u;
-    }
-    __syncthreads();
-    const uint32_t ticket = s_ticket;
-    if (ticket >= n) break;
-    const uint32_t tile = a.dense ? ticket : a.list[ticket];
-    const int tx = (int)(tile % (uint32_t)a.TX), ty = (int)((tile / (uint32_t)a.TX) % (uint32_t)a.TY), tz = (int)(tile / (uint32_t)(a.TX * a.TY));
-
+  for (int tx, ty, tz; tile_take(a.tiles, n, slot, s_tile, tx, ty, tz);) {
     // the core row of this thread, and the halo: 18 + 18 rows at rz = -1 and 16, 16 + 16 at ry = -1 and 16
     const int gy = ty * kTile + cy, gz = tz * kTile + cz;
     const bool exists = gy < a.Y && gz < a.Z;
@@ -216,27 +167,11 @@ __global__ __launch_bounds__(256) void k_grow_round(const GrowArgs a, uint32_t r
     }
 
     if (exists && r != r0) a.mask[own] = r;
-    // the neighbouring tiles that a new voxel touches are visited in the next round.  Round 1 counts every voxel as new: its seeds
-    // were stored by other kernels, and nobody has looked at them from the other side of a tile face yet
+    // the neighbouring tiles that a new voxel touches are woken; round 1 counts every voxel as new
     const u64 fresh = round == 1u ? r : (r & ~r0);
-    if (fresh) {
-      const bool at_x[3] = {(fresh & 1ull) != 0ull, true, (fresh >> 63) != 0ull};
-      const bool at_y[3] = {cy == 0, true, cy == kTile - 1}, at_z[3] = {cz == 0, true, cz == kTile - 1};
-      uint32_t wake = 0u;
-#pragma unroll
-      for (int q = 0; q < 27; ++q) {
-        const int dx = q % 3, dy = (q / 3) % 3, dz = q / 9;
-        const int moved = (dx != 1) + (dy != 1) + (dz != 1);
-        if (moved == 0 || (!CONN26 && moved != 1)) continue;  // an edge or corner neighbour is adjacent only under 26-connectivity
-        if (at_x[dx] && at_y[dy] && at_z[dz]) wake |= 1u << q;
-      }
-      if (wake) atomicOr(&s_wake, wake);
-    }
-    __syncthreads();
-    if (t < 27u && ((s_wake >> t) & 1u)) {
-      const int nx = tx + (int)(t % 3u) - 1, ny = ty + (int)((t / 3u) % 3u) - 1, nz = tz + (int)(t / 9u) - 1;
-      if (nx >= 0 && nx < a.TX && ny >= 0 && ny < a.TY && nz >= 0 && nz < a.TZ) a.stamps[((size_t)nz * a.TY + ny) * a.TX + nx] = round + 1u;
-    }
+    const bool at_x[3] = {(fresh & 1ull) != 0ull, true, (fresh >> 63) != 0ull};
+    const bool at_y[3] = {cy == 0, true, cy == kTile - 1}, at_z[3] = {cz == 0, true, cz == kTile - 1};
+    tile_wake<CONN26>(a.tiles, round, s_tile, tx, ty, tz, fresh != 0ull, at_x, at_y, at_z);
   }
 }
 
@@ -259,7 +194,7 @@ __global__ __launch_bounds__(256) void k_grow_reduce(const GrowArgs a) {
     const int16_t *p = a.volume + row * (size_t)a.X + (size_t)x0;  // (set bits lie at x < X)
     int v[8];
     if (ROWS8) {
-      grow_load8(p, v);
+      load8(p, v);
     } else {
 #pragma unroll
       for (int h = 0; h < 8; ++h) v[h] = ((m >> h) & 1u) ? (int)p[h] : 0;
@@ -358,11 +293,6 @@ __global__ __launch_bounds__(256) void k_apply_mask(const int16_t *in, int16_t *
   out[id] = bit != invert ? in[id] : (int16_t)(uint16_t)fill;
 }
 
-namespace {
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255u) / 256u); }
-inline bool rows_of_8(const void *p, int32_t X) { return (X % 8) == 0 && ((uintptr_t)p & 15u) == 0u; }
-}  // namespace
-
 hipError_t launch_grow_admissible(const GrowArgs &a, hipStream_t s) {
   const size_t rows = (size_t)a.Y * (size_t)a.Z;
   if (rows_of_8(a.volume, a.X)) hipLaunchKernelGGL(k_grow_admissible8, dim3(blocks_for(rows * (size_t)a.W64 * 8u)), dim3(256), 0, s, a);
@@ -377,12 +307,8 @@ hipError_t launch_grow_seeds(const GrowArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_grow_round(const GrowArgs &a, uint32_t round, int slot, hipStream_t s) {
-  const size_t n_tiles = (size_t)a.TX * (size_t)a.TY * (size_t)a.TZ;
-  hipLaunchKernelGGL(k_grow_list, dim3(blocks_for(n_tiles)), dim3(256), 0, s, a, round, slot);
-  // four blocks per CU hold the 4.8 KB of LDS and 256 threads each with room to spare; fewer tiles need fewer blocks
-  const unsigned grid = (unsigned)(n_tiles < 1024u ? n_tiles : 1024u);
-  hipLaunchKernelGGL(a.conn26 ? k_grow_round<true> : k_grow_round<false>, dim3(grid), dim3(256), 0, s, a, round, slot);
-  return hipGetLastError();
+  // four blocks per CU hold the 4.8 KB of LDS and 256 threads each with room to spare
+  return launch_tile_round(a.conn26 ? k_grow_round<true> : k_grow_round<false>, 1024u, a, round, slot, s);
 }
 
 hipError_t launch_grow_reduce(const GrowArgs &a, hipStream_t s) {

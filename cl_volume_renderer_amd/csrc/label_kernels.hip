@@ -24,7 +24,7 @@
 // the flatten is sums, minima, maxima and a sort of distinct keys: the bytes do not depend on the schedule.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "clwh_internal.hpp"
+#include "mask_device.hpp"
 
 namespace clvr {
 
@@ -86,10 +86,6 @@ __device__ __forceinline__ bool label_word(const LabelArgs &a, LabelWord &o) {
   return true;
 }
 
-__device__ __forceinline__ bool label_in_window_and_box(const LabelArgs &a, int v, int x) {
-  return v >= a.lo && v <= a.hi && x >= a.box_lo[0] && x < a.box_hi[0];
-}
-
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
   return v;
@@ -105,38 +101,22 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 
 }  // namespace
 
-// A.  Rows of a multiple of 8 voxels: a lane classifies the 8 voxels of one 16-byte load and owns one byte of A (k_grow_admissible8's
-// shape, without its store to the mask); the bytes at x >= X are the padding and become zero.
+// A, ANDed with the caller's mask if there is one.  Rows of a multiple of 8 voxels: a lane owns one byte of A (admissible_byte).
 __global__ __launch_bounds__(256) void k_label_admissible8(const LabelArgs a) {
-  const size_t bytes_per_row = (size_t)a.W64 * 8u, total = bytes_per_row * (size_t)a.Y * (size_t)a.Z;
-  const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+  const size_t total = (size_t)a.W64 * 8u * (size_t)a.Y * (size_t)a.Z, id = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (id >= total) return;
-  const size_t row = id / bytes_per_row;
-  const int x0 = (int)(id - row * bytes_per_row) * 8;
-  const int z = (int)(row / (size_t)a.Y), y = (int)(row - (size_t)z * (size_t)a.Y);
-  uint32_t bits = 0u;
-  if (x0 < a.X && y >= a.box_lo[1] && y < a.box_hi[1] && z >= a.box_lo[2] && z < a.box_hi[2]) {  // X is a multiple of 8: all eight exist
-    const uint4 q = *reinterpret_cast<const uint4 *>(a.volume + row * (size_t)a.X + (size_t)x0);
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int h = 0; h < 8; ++h) bits |= label_in_window_and_box(a, (int)(int16_t)(w[h >> 1] >> (16 * (h & 1))), x0 + h) ? (1u << h) : 0u;
-    if (a.mask) bits &= (uint32_t)reinterpret_cast<const uint8_t *>(a.mask)[id];
-  }
+  int x0, y, z;
+  uint32_t bits = admissible_byte(a, id, x0, y, z);
+  if (bits != 0u && a.mask) bits &= (uint32_t)reinterpret_cast<const uint8_t *>(a.mask)[id];
   reinterpret_cast<uint8_t *>(a.adm)[id] = (uint8_t)bits;
 }
 
-// the same for any row length or alignment: a thread per voxel of the padded row, a wave per 64-bit word
+// the same for any row length or alignment: a thread per voxel of the padded row, a wave per 64-bit word (admissible_voxel)
 __global__ __launch_bounds__(256) void k_label_admissible(const LabelArgs a) {
-  const size_t padded = (size_t)a.W64 * 64u, total = padded * (size_t)a.Y * (size_t)a.Z;
-  const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+  const size_t total = (size_t)a.W64 * 64u * (size_t)a.Y * (size_t)a.Z, id = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (id >= total) return;  // (whole waves: `total` and a wave's first id are multiples of 64)
-  const size_t row = id / padded;
-  const int x = (int)(id - row * padded);
-  const int z = (int)(row / (size_t)a.Y), y = (int)(row - (size_t)z * (size_t)a.Y);
-  bool in = false;
-  if (x < a.X && y >= a.box_lo[1] && y < a.box_hi[1] && z >= a.box_lo[2] && z < a.box_hi[2])
-    in = label_in_window_and_box(a, (int)a.volume[row * (size_t)a.X + (size_t)x], x);
-  u64 bits = __ballot(in);
+  int x, y, z;
+  u64 bits = __ballot(admissible_voxel(a, id, x, y, z));
   if ((threadIdx.x & 63u) == 0u) {
     if (a.mask) bits &= a.mask[id >> 6];
     a.adm[id >> 6] = bits;
@@ -429,14 +409,13 @@ __global__ __launch_bounds__(256) void k_labels_to_mask_ragged(const uint32_t *_
 }
 
 namespace {
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255u) / 256u); }
 inline size_t label_words(const LabelArgs &a) { return (size_t)a.W64 * (size_t)a.Y * (size_t)a.Z; }
 }  // namespace
 
 // A, the runs, their unions, the flatten with its two counts
 hipError_t launch_label_classes(const LabelArgs &a, hipStream_t s) {
   const size_t words = label_words(a);
-  if ((a.X % 8) == 0 && ((uintptr_t)a.volume & 15u) == 0u) hipLaunchKernelGGL(k_label_admissible8, dim3(blocks_for(words * 8u)), dim3(256), 0, s, a);
+  if (rows_of_8(a.volume, a.X)) hipLaunchKernelGGL(k_label_admissible8, dim3(blocks_for(words * 8u)), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_label_admissible, dim3(blocks_for(words * 64u)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_label_init, dim3(blocks_for(words)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(a.conn26 ? k_label_merge<true> : k_label_merge<false>, dim3(blocks_for(words)), dim3(256), 0, s, a);
@@ -467,7 +446,7 @@ hipError_t launch_label_ranks(const LabelArgs &a, hipStream_t s) {
 hipError_t launch_labels_to_mask(const uint32_t *labels, unsigned long long *mask, int32_t X, int32_t Y, int32_t Z, int32_t W64, uint32_t rank_lo,
                                  uint32_t rank_hi, hipStream_t s) {
   const size_t rows = (size_t)Y * (size_t)Z;
-  if ((X % 8) == 0 && ((uintptr_t)labels & 15u) == 0u)
+  if (rows_of_8(labels, X))
     hipLaunchKernelGGL(k_labels_to_mask, dim3(blocks_for(rows * (size_t)W64 * 8u)), dim3(256), 0, s, labels, (uint8_t *)mask, X, rows, W64, rank_lo, rank_hi);
   else
     hipLaunchKernelGGL(k_labels_to_mask_ragged, dim3(blocks_for(rows * (size_t)W64 * 64u)), dim3(256), 0, s, labels, mask, X, rows, W64, rank_lo, rank_hi);

@@ -2,7 +2,7 @@
 // clwh_label_statistics; host side clwh_region_stats.hip).  Integers only: sums, extremes and counts commute, so the order in which
 // lanes, waves and blocks add their parts does not show in the result.  A record is accumulated in the layout of clwh_region_stats with
 // the extremes and bbox_lo at their identities and bbox_hi inclusive (k_stats_init), and brought into its final form by k_stats_finish.
-#include "clwh_internal.hpp"
+#include "mask_device.hpp"
 
 namespace clvr {
 
@@ -104,14 +104,6 @@ __device__ __forceinline__ void partial_merge(Partial &s, const Partial &p) {
   }
 }
 
-// eight voxels of a row that is a multiple of 8 long, 16-byte aligned (grow_load8's load)
-__device__ __forceinline__ void stats_load8(const int16_t *p, int (&v)[8]) {
-  const uint4 q = *reinterpret_cast<const uint4 *>(p);
-  const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int h = 0; h < 8; ++h) v[h] = (int)(int16_t)(w[h >> 1] >> (16 * (h & 1)));
-}
-
 // ---- the mask path: k_grow_reduce's walk (a lane takes a byte of the mask, 8 voxels, in a grid-stride loop) with the positions, the
 // faces from the bits alone, and the histogram in k_tf_sort_values' LDS hash (its slot count was measured there)
 constexpr int kHistSlotsLog2 = 12, kHistSlots = 1 << kHistSlotsLog2;
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(256) void k_mask_stats(const MaskStatsArgs a) {
     const int16_t *p = a.volume + row * (size_t)X + (size_t)x0;
     int v[8];
     if (ROWS8) {
-      stats_load8(p, v);
+      load8(p, v);
     } else {
 #pragma unroll
       for (int h = 0; h < 8; ++h) v[h] = ((m >> h) & 1u) ? (int)p[h] : 0;
@@ -389,7 +381,7 @@ __global__ __launch_bounds__(256) void k_label_stats(const LabelStatsArgs a) {
 
     int v[8];
     if (ROWS8) {
-      stats_load8(a.volume + at, v);
+      load8(a.volume + at, v);
     } else {
 #pragma unroll
       for (int h = 0; h < 8; ++h) v[h] = (uint32_t)h < rem ? (int)a.volume[at + (size_t)h] : 0;
@@ -492,9 +484,6 @@ __global__ __launch_bounds__(256) void k_stats_finish(RegionRec *stats, uint32_t
   }
 }
 
-inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255u) / 256u); }
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0u; }
-
 }  // namespace
 
 hipError_t launch_stats_init(clwh_region_stats *stats, uint32_t n, hipStream_t s) {
@@ -510,7 +499,7 @@ hipError_t launch_stats_finish(clwh_region_stats *stats, uint32_t n, hipStream_t
 hipError_t launch_mask_stats(const MaskStatsArgs &a, hipStream_t s) {
   const size_t bytes = (size_t)a.Y * (size_t)a.Z * (size_t)a.W64 * 8u;
   const unsigned need = blocks_for(bytes), grid = need < 2048u ? need : 2048u;
-  const bool rows8 = (a.X % 8) == 0 && aligned16(a.volume);
+  const bool rows8 = rows_of_8(a.volume, a.X);
   auto kernel = a.hist ? (rows8 ? k_mask_stats<true, true> : k_mask_stats<false, true>) : (rows8 ? k_mask_stats<true, false> : k_mask_stats<false, false>);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -520,7 +509,7 @@ hipError_t launch_label_stats(const LabelStatsArgs &a, hipStream_t s) {
   const size_t items = (((size_t)a.X + 7u) / 8u) * (size_t)a.Y * (size_t)a.Z;
   // four blocks per CU hold their tables (27 KB each); a grid of that size walks the volume
   const unsigned need = blocks_for(items), grid = need < 1024u ? need : 1024u;
-  const bool rows8 = (a.X % 8) == 0 && aligned16(a.volume) && aligned16(a.labels);
+  const bool rows8 = rows_of_8(a.volume, a.X) && aligned16(a.labels);
   hipLaunchKernelGGL(rows8 ? k_label_stats<true> : k_label_stats<false>, dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
 }

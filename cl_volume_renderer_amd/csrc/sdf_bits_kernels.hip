@@ -12,6 +12,7 @@
 // holds no reached voxel yet, leave after reading a few state bytes.  A voxel's value is written once, in the launch
 // in which its bit appears (layer index recorded bit-sliced per core word), with the sign of its event bit.
 // Bit-exact against the oracle / the reference's golden vector like the byte front it replaces (tests/test_gpu_sdf.py).
+#include "mask_device.hpp"  // load8
 #include "sdf_device.hpp"
 
 namespace clvr {
@@ -48,12 +49,6 @@ __global__ __launch_bounds__(256) void k_sdfbit_events8(const SdfArgs a, uint8_t
   uint32_t bits = 0u;
   if (x0 < a.X) {  // X is a multiple of 8: all eight voxels exist
     const int16_t *own = a.volume + row * (size_t)a.X + (size_t)x0;
-    auto load8 = [](const int16_t *p, int (&v)[8]) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(p);
-      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int h = 0; h < 8; ++h) v[h] = (int)(int16_t)(w[h >> 1] >> (16 * (h & 1)));
-    };
     int value[8], gradient[8];
     load8(own, value);
 #pragma unroll
