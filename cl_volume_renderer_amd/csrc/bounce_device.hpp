@@ -125,6 +125,17 @@ __device__ __forceinline__ f3 hull_direction(unsigned k) {
   const float r = __builtin_amdgcn_rsqf((x * x + y * y) + z * z);
   return f3{x * r, y * r, z * r};
 }
+// The octahedral cell a vector of any length falls in: hull_direction's inverse on its cell centres (the reciprocal and the products
+// are off by an ulp, the centres lie half a cell from every border).  k_bounce's tilted planes pick their plane with it;
+// ANY cell is a safe answer -- only the yield depends on it -- but it must be a cell: fmaxf / fminf drop a NaN, so a NaN lands in cell 0.
+__device__ __forceinline__ unsigned hull_cell(f3 n) {
+  static_assert(kHullGrid == 64, "cell (i, j) covers u in [i / 32 - 1, (i + 1) / 32 - 1)");
+  const float r = __builtin_amdgcn_rcpf((fabsf(n.x) + fabsf(n.y)) + fabsf(n.z));
+  const float x = n.x * r, y = n.y * r;
+  const float u = n.z >= 0.0f ? x : copysignf(1.0f - fabsf(y), x), v = n.z >= 0.0f ? y : copysignf(1.0f - fabsf(x), y);
+  const int i = (int)fminf(fmaxf(floorf(u * 32.0f + 32.0f), 0.0f), 63.0f), j = (int)fminf(fmaxf(floorf(v * 32.0f + 32.0f), 0.0f), 63.0f);
+  return (unsigned)(j * 64 + i);
+}
 // (the test itself: k_bounce's opening half.  The far-face crawl and NaN directions as in certify_exit.)
 __device__ __forceinline__ bool certify_exit(const RenderArgs &a, f3 p, f3 d, int budget) {
   int away;
@@ -179,6 +190,8 @@ template <> struct BounceStatsT<false> {
   __device__ void hull_cert(bool, bool, bool) {}
   __device__ void hull_more(bool, bool, bool, bool) {}
   __device__ void hull_fired(bool, bool) {}
+  __device__ void hull_tilt(bool, bool, bool, bool, bool) {}
+  __device__ void hull_late(bool) {}
   __device__ void march_end(uint32_t *, int) {}
   template <bool TWO_RAYS> __device__ void flush(uint32_t *) {}
 };
@@ -245,17 +258,35 @@ template <> struct BounceStatsT<true> {
     more_tried[1] += (uint32_t)__popcll(__ballot(rebound_tried)); more_granted[1] += (uint32_t)__popcll(__ballot(rebound_granted));
     if (rebound_granted) more_open = 1;
   }
-  __device__ __forceinline__ void hull_fired(bool fired, bool first_leg) {
+  __device__ __forceinline__ void hull_fired(bool fired_any, bool first_leg) {
+    const bool fired = fired_any && !tilt_armed, tilted = fired_any && tilt_armed;  // whose arming it was
     more_granted[0] += (uint32_t)__popcll(__ballot(fired && first_leg)); more_granted[2] += (uint32_t)__popcll(__ballot(fired && !first_leg));
     if (fired) more_open = first_leg ? 0 : 2;
+    tilt_granted[1] += (uint32_t)__popcll(__ballot(tilted && first_leg)); tilt_granted[3] += (uint32_t)__popcll(__ballot(tilted && !first_leg));
+    if (tilted) tilt_open = first_leg ? 1 : 3;
   }
+  // item 14's classes, verified the same way: 0 first legs granted at once by a tilted plane, 1 first legs granted after a few literal
+  // steps, 2 / 3 the same for rebounds; `starts`: the lane starts a march in this opening half (armed by the tilted plane or not)
+  uint32_t tilt_tried[4] = {0, 0, 0, 0}, tilt_granted[4] = {0, 0, 0, 0}, tilt_late = 0;
+  int tilt_open = -1;
+  bool tilt_armed = false;  // this lane's current march was armed by a tilted plane
+  __device__ __forceinline__ void hull_tilt(bool tried, bool granted, bool armed, bool starts, bool first_leg) {
+    tilt_tried[0] += (uint32_t)__popcll(__ballot(tried && first_leg)); tilt_tried[2] += (uint32_t)__popcll(__ballot(tried && !first_leg));
+    tilt_granted[0] += (uint32_t)__popcll(__ballot(granted && first_leg)); tilt_granted[2] += (uint32_t)__popcll(__ballot(granted && !first_leg));
+    tilt_tried[1] += (uint32_t)__popcll(__ballot(armed && first_leg)); tilt_tried[3] += (uint32_t)__popcll(__ballot(armed && !first_leg));
+    if (granted) tilt_open = first_leg ? 0 : 2;
+    if (starts) tilt_armed = armed;
+  }
+  __device__ __forceinline__ void hull_late(bool late) { tilt_late += (uint32_t)__popcll(__ballot(late)); }
   __device__ __forceinline__ void march_end(uint32_t *counters, int ev) {
     if (start_open && ev != EV_EXIT) atomicAdd(&counters[CTR_START_WRONG], 1u);
     if (hull_open && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_WRONG], 1u);
     if (more_open >= 0 && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_DEFER + 3 * more_open + 2], 1u);
+    if (tilt_open >= 0 && ev != EV_EXIT) atomicAdd(&counters[CTR_HULL_TILT + 3 * tilt_open + 2], 1u);
     start_open = false;
     hull_open = false;
     more_open = -1;
+    tilt_open = -1;
   }
   // lane 0 of a wave that ends
   template <bool TWO_RAYS> __device__ __forceinline__ void flush(uint32_t *counters) {
@@ -269,6 +300,8 @@ template <> struct BounceStatsT<true> {
     atomicAdd(&counters[CTR_START_TRIED], start_tried); atomicAdd(&counters[CTR_START_GRANTED], start_granted);
     atomicAdd(&counters[CTR_HULL_TRIED], hull_tried); atomicAdd(&counters[CTR_HULL_GRANTED], hull_granted); atomicAdd(&counters[CTR_HULL_BOTH], hull_both);
     for (int k = 0; k < 3; ++k) { atomicAdd(&counters[CTR_HULL_DEFER + 3 * k], more_tried[k]); atomicAdd(&counters[CTR_HULL_DEFER + 3 * k + 1], more_granted[k]); }
+    for (int k = 0; k < 4; ++k) { atomicAdd(&counters[CTR_HULL_TILT + 3 * k], tilt_tried[k]); atomicAdd(&counters[CTR_HULL_TILT + 3 * k + 1], tilt_granted[k]); }
+    atomicAdd(&counters[CTR_HULL_TILT + 12], tilt_late);
   }
 };
 using BounceStats = BounceStatsT<kBounceStats>;

@@ -175,6 +175,7 @@ Tuning clvr::tuning_from_environment() {
   if (const char *e = std::getenv("CLWH_TUNE_START_CERT")) t.start_cert = std::atoi(e) != 0;
   if (const char *e = std::getenv("CLWH_TUNE_HULL_CERT")) t.hull_cert = std::atoi(e) != 0;
   if (const char *e = std::getenv("CLWH_TUNE_HULL_DEFER")) t.hull_defer = std::atoi(e) != 0;
+  if (const char *e = std::getenv("CLWH_TUNE_HULL_TILT")) t.hull_tilt = std::atoi(e) != 0;
   return t;
 }
 

@@ -141,6 +141,7 @@ struct Tuning {
   int32_t start_cert = 1;      // CLWH_TUNE_START_CERT=0: no start-certificate table (a byte per voxel), first legs march from their first step
   int32_t hull_cert = 1;       // CLWH_TUNE_HULL_CERT=0: no hull-certificate table, no plane search in k_primary, no test in k_bounce
   int32_t hull_defer = 1;      // CLWH_TUNE_HULL_DEFER=0: hull certificates for first legs that start in front of their plane only
+  int32_t hull_tilt = 1;       // CLWH_TUNE_HULL_TILT=0: no tilted planes, armed marches keep kHullDeferSteps
   int32_t cert_min_step = -1;  // CLWH_TUNE_CERT: 0 = exit certificates off; -1 = by volume size (12 at 512^3, 24 at 1024^3, 48 at 2048^3:
                                // the best of the sweeps in profiles/r02_sweep_k_bounce_lds_state.txt)
   uint32_t bounce_max_blocks = 2048;  // CLWH_TUNE_BLOCKS
@@ -184,7 +185,7 @@ struct PrimaryHits {
 
 // work buffers of one pass
 struct PassScratch {
-  static constexpr size_t kCounters = CTR_QUEUE_STRIDE * 10;  // the first line, eight queue heads, and a line of statistics (CTR_HULL_DEFER)
+  static constexpr size_t kCounters = CTR_QUEUE_STRIDE * 10;  // the first line, eight queue heads, and a line of statistics (CTR_HULL_DEFER, CTR_HULL_TILT)
   DeviceBuffer counters;      // kCounters x u32 on the device
   DeviceBuffer fixups, delta;
   DeviceBuffer sticky_flags;  // [0] fix-up buffer overflow: set by kernels, cleared only when the host has read it

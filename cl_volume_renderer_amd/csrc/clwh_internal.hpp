@@ -65,6 +65,9 @@ enum : uint32_t {
   // k_bounce only, behind the last queue head: tried / granted / wrong of the hull certificates item 13 added, three slots per class --
   // first legs granted after a few literal steps, rebounds granted at once, rebounds granted after a few literal steps
   CTR_HULL_DEFER = CTR_QUEUE_STRIDE * 9, CTR_HULL_DEFER_END = CTR_HULL_DEFER + 9,
+  // ... and of the tilted planes item 14 adds, four classes: first legs at once / after a few literal steps, rebounds at once / after a few;
+  // then one slot: armed lanes that covered their path too late and went back to marching without a look-up
+  CTR_HULL_TILT = CTR_HULL_DEFER_END, CTR_HULL_TILT_END = CTR_HULL_TILT + 13,
 };
 struct RenderArgs {
   int32_t X, Y, Z;
@@ -93,7 +96,12 @@ struct RenderArgs {
   // ... and (hull_planes, a second word per hit) 1 + the index of the best plane the search found even when the start point lies up to
   // kHullDeferDeficit BEHIND it, with the signed margin in bits 16-23 (k_primary; clwh_debug_hull_planes); nullptr: CLWH_TUNE_HULL_DEFER=0, or no table
   uint32_t *hull_planes;
-  float hull_defer_delta0;  // a march that gets in front of such a plane within kHullDeferSteps steps is granted there if direction . n_k is at least this
+  float hull_defer_delta0;  // a march that gets in front of such a plane within J steps (kHullDeferSteps; kHullTiltSteps with hull_h) is granted there if direction . n_k is at least this
+  // ... and the table's h_k alone (kHullPlanes floats, k_hull_finish): a march that neither rule above grants or arms asks the plane whose
+  // normal is the hit's plane normal tilted towards its own direction; nullptr: CLWH_TUNE_HULL_TILT=0, no hull_planes, or no table
+  const float *hull_h;
+  float hull_tilt_target;   // t: the tilt aims at direction . n' = t = hull_defer_delta0 + kHullTiltMargin
+  float hull_tilt_gain;     // t / sqrt(1 - t^2)
   int32_t NBX, NBY;
   const uint32_t *env;     // RGBA8 packed, row-major
   int32_t env_w, env_h;
@@ -285,13 +293,13 @@ inline float hull_cert_delta0(int X, int Y, int Z) {
 constexpr int kHullDeferSteps = 3;            // J: the most literal steps a march may have taken when a deferred grant fires
 constexpr float kHullDeferDeficit = 1.5f;     // D: planes further than this in front of the start point are not worth waiting for
 constexpr int kHullMarginScale = 16;          // the stored margin's grid: 1/16 voxel, eight bits signed (-8 .. +7.9375, clamped)
-inline float hull_defer_delta0(int X, int Y, int Z) {
+inline float hull_defer_delta0(int X, int Y, int Z, int J = kHullDeferSteps) {
   const double longest = (double)(X > Y ? (X > Z ? X : Z) : (Y > Z ? Y : Z));
   const double reach = 1.7320508075688772 * (longest + 1.0), cap = (double)start_cert_cap(X, Y, Z);
   for (int k = 1; k <= 64; ++k) {
     const double delta0 = (double)k / 64.0;
     double t = 0.0;
-    for (int step = 0; step < 70 - 5 - kHullDeferSteps && t <= reach; ++step) {
+    for (int step = 0; step < 70 - 5 - J && t <= reach; ++step) {
       const double m = (double)(long long)(t * delta0 / 1.7320508075688772) - 2.0;
       const double bound = m > cap ? cap : m;
       t += bound < 1.0 ? 1.0 : bound;
@@ -300,8 +308,38 @@ inline float hull_defer_delta0(int X, int Y, int Z) {
   }
   return 2.0f;
 }
-// `ends`: scratch of Y * Z int2 (k_start_rows leaves a row's first and last event voxel there); `hull`: kHullPlanes float4
-hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, int X, int Y, int Z, hipStream_t s);
+// Tilted planes.  The theorem asks nothing of WHICH plane of the table a march names either: every corner of every
+// event voxel lies behind every plane k (n_k . c <= h_k - kHullSlack, k_hull_*), so a position in front of plane k', a constant direction
+// with d . n_k' >= delta and 70 - J steps left carry the march out of the volume exactly as in items 12 and 13.  A march of fresh budget
+// 70 that starts from a bounce and that the hit's own plane neither grants nor arms picks k' in closed form:
+//   n0   the hit's plane normal n_k (hull_direction of the hit's word; a hit without a word: the bounce's own normal),
+//   c    = d . n0,  t = hull_defer_delta0(J) + kHullTiltMargin,  lambda = 0 if c >= t, else -c + sqrt(1 - c^2) * t / sqrt(1 - t^2),
+//   n'   = n0 + lambda d: the vector of the plane spanned by n0 and d with d . n' / |n'| = t that is nearest n0,
+//   k'   = hull_cell(n'), the octahedral cell n' falls in (bounce_device.hpp).
+// None of this is part of the proof -- ANY cell is safe, a NaN included (hull_cell clamps it into the table); only the yield depends on
+// it.  The proof starts at the two numbers formed from k' itself, with the operations of items 12 and 13:
+//   dn'  = d . n_k',  n_k' = hull_direction(k'), the same bits as in the table's builder;
+//   M'   = n_k' . start - h_k', start the march's first position in binary32, h_k' read from the table (hull_h).
+// (a) M' >= 0 and dn' >= hull_cert_delta0: granted before the first step.
+// (b) M' < 0, dn' >= hull_defer_delta0(J) and need = ceil(-M' / dn') <= kHullTiltPath: armed exactly as item 13 arms (kArmed, the low field
+//     of `march` at kCertReady - need); the certificate phase fires the grant if at most J steps were taken.  After a counted path >= need
+//     the position is start + t d with t dn' >= -M': in front of plane k'.  No deficit limit D; the path limit is no part of the proof
+//     either: an armed lane cannot ask the macro-cell table before it has counted its path, so the path has to end in the near field.
+// The step loop compares against ONE J per launch (a constant picked by the wave-uniform flag), so with the rule on item 13's armed
+// marches take kHullTiltSteps and its delta as well.
+// Rounding budget of M' against kHullSlack = 2^-4: n_k' . start is k_primary's n_k . P with another k -- coordinates below 2^11 + 3, three
+// products and two additions of half an ulp (2^-13) each, the subtraction of h_k' one more: below 2^-10, the share the slack already
+// reserves for "k_primary's n_k . P"; the table's maximum 2^-10; the march's 70 additions 2^-5 (the literal steps before a deferred grant
+// are among them); |n_k'| off by 2^-22 at 2^12: 2^-10.  Item 13's relative margin (3 x 2^-10) is not used on this path.  2^-5 + 3 x 2^-10
+// < 0.035 of 0.0625: it fits, the slack is not touched and no guard is subtracted.  need comes from a reciprocal good to 2^-22, widened
+// by 2^-19: never below the quotient.  Direction guards as in items 12 and 13: no NaN, min |component| >= 2^-10; a NaN in start or in
+// h_k' (+inf: no event voxel, or step bytes that are not regular) makes M' a NaN or -inf, which fails (a) and (b).
+constexpr int kHullTiltSteps = 16;                // J with tilted planes (tools/hull_tilt.py; 12 / 16 / 20 on the GPU: profiles/bounce_hull_tilt_ab.txt)
+constexpr float kHullTiltMargin = 0.0625f;        // the tilt aims this far above delta(J), so that the cell's own normal still qualifies
+constexpr int kHullTiltPath = 48;                 // P: the longest path a tilted plane may ask a march to count before its grant
+// `ends`: scratch of Y * Z int2 (k_start_rows leaves a row's first and last event voxel there); `hull`: kHullPlanes float4;
+// `hull_h`: kHullPlanes floats, the entries' h_k alone
+hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, float *hull_h, int X, int Y, int Z, hipStream_t s);
 constexpr uint64_t kStartTableBudget = 2ull << 30;  // bytes (= voxels): larger volumes get no start certificates
 hipError_t launch_primary(const RenderArgs &a, hipStream_t s);
 hipError_t launch_bounce(const RenderArgs &a, hipStream_t s);

@@ -1,6 +1,7 @@
 // clwh_render.hip -- clwh_render on the host: the registry of derived scene data, the camera's primary hits, one pass;
 // and the entry points that resolve an image-space accumulation.  The kernels: {scene,primary,render,accumulate}_kernels.hip.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -26,9 +27,9 @@ PackedScene::~PackedScene() {
 // layout of a PackedScene's allocation
 struct PackedLayout {
   int X, Y, Z, NBX, NBY, NBZ, mshift, MNX, MNY, MNZ;
-  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, off_start, off_hull_ends, off_hull, bytes;
+  size_t records, n_bricks, off_stepb, off_brick_min, off_macro, off_start, off_hull_ends, off_hull, off_hull_h, bytes;
   bool start_table;  // the start-certificate table is part of the allocation
-  bool hull_table;   // ... and behind it the hull-certificate table with its scratch (the rows' first and last event voxels)
+  bool hull_table;   // ... and behind it the hull-certificate table with its scratch (the rows' first and last event voxels) and, last, its h_k alone
 };
 // Start certificates (k_start_*, scene_kernels.hip) are built for tables the step byte decides alone (no rule reads `gradient`), under
 // which the border texel is no event (the other exit certificates are off there too), for volumes whose table fits the budget (and the
@@ -43,6 +44,13 @@ static bool wants_hull_table(const Tuning &t, const TfDev &tf, const clwh_mem *v
   return t.hull_cert != 0 && wants_start_table(t, tf, volume) && volume->dims[0] <= (size_t)kHullMaxDim && volume->dims[1] <= (size_t)kHullMaxDim &&
          volume->dims[2] <= (size_t)kHullMaxDim;
 }
+// tilted planes: the tilt's target and gain as bind_scene hands them to k_bounce
+static void hull_tilt_target(float delta, float &target, float &gain) {
+  const double t = std::min((double)delta + (double)kHullTiltMargin, 0.984375);  // (delta = 2, none qualifies: any target will do)
+  target = (float)t;
+  gain = (float)(t / std::sqrt(1.0 - t * t));
+}
+
 static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift, bool start_table, bool hull_table) {
   PackedLayout L;
   L.X = (int)volume->dims[0]; L.Y = (int)volume->dims[1]; L.Z = (int)volume->dims[2];
@@ -63,7 +71,8 @@ static PackedLayout packed_layout(const clwh_mem *volume, int forced_macro_shift
   L.hull_table = hull_table;
   L.off_hull = L.off_hull_ends + (hull_table ? (size_t)L.Y * L.Z * sizeof(int2) : 0u);  // (a multiple of 8; float4 loads need 16)
   L.off_hull = (L.off_hull + 15u) & ~(size_t)15u;
-  L.bytes = hull_table ? L.off_hull + (size_t)kHullPlanes * sizeof(float4) : L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u);
+  L.off_hull_h = L.off_hull + (size_t)kHullPlanes * sizeof(float4);
+  L.bytes = hull_table ? L.off_hull_h + (size_t)kHullPlanes * sizeof(float) : L.off_start + (start_table ? 16u + (size_t)L.X * L.Y * L.Z : 0u);
   return L;
 }
 
@@ -135,7 +144,7 @@ static int ensure_packed(clwh_ctx *ctx, const PackedLayout &L, const clwh_mem *v
       int2 *ends = L.hull_table ? reinterpret_cast<int2 *>(data + L.off_hull_ends) : nullptr;
       const hipError_t e = launch_start_table(r.stepb, data + L.off_start + 16u, reinterpret_cast<uint32_t *>(data + L.off_start), ends, L.X, L.Y, L.Z, L.NBX, L.NBY, L.NBZ, ctx->stream);
       if (e != hipSuccess || !L.hull_table) return e;
-      return launch_hull_table(ends, reinterpret_cast<const uint32_t *>(data + L.off_start), reinterpret_cast<float4 *>(data + L.off_hull), L.X, L.Y, L.Z, ctx->stream);
+      return launch_hull_table(ends, reinterpret_cast<const uint32_t *>(data + L.off_start), reinterpret_cast<float4 *>(data + L.off_hull), reinterpret_cast<float *>(data + L.off_hull_h), L.X, L.Y, L.Z, ctx->stream);
     }));
   HIP_TRY(hipEventRecord(entry->ready.ev, ctx->stream));
   ctx->scene = entry;
@@ -286,6 +295,12 @@ static int bind_scene(clwh_kernel *k, const clwh_render_desc *d, RenderArgs &a) 
   a.macro = packed + L.off_macro;
   a.start_free = L.start_table ? packed + L.off_start + 16u : nullptr;
   a.hull = L.hull_table ? reinterpret_cast<const float4 *>(packed + L.off_hull) : nullptr;
+  // tilted planes ride on item 13's armed counter and its layout of the lane's word: no hull_planes, no tilt
+  a.hull_h = L.hull_table && ctx->tune.hull_defer != 0 && ctx->tune.hull_tilt != 0 ? reinterpret_cast<const float *>(packed + L.off_hull_h) : nullptr;
+  if (a.hull_h) {
+    a.hull_defer_delta0 = hull_defer_delta0(a.X, a.Y, a.Z, kHullTiltSteps);  // k_bounce's one J for every armed march
+    hull_tilt_target(a.hull_defer_delta0, a.hull_tilt_target, a.hull_tilt_gain);
+  }
   a.macro_shift = L.mshift;
   a.MNX = L.MNX; a.MNY = L.MNY; a.MNZ = L.MNZ;
   // An exit certificate proves "this march leaves the volume without a Hit"; a position with a coordinate == dimension or NaN
@@ -433,7 +448,7 @@ static int plan_voxel_grants(clwh_ctx *ctx, RenderArgs &a) {
 
 #ifdef CLVR_BOUNCE_STATS  // experiment builds only (CLVR_EXTRA_HIPCC_FLAGS=-DCLVR_BOUNCE_STATS): scheduling statistics of the launch
 static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
-  uint32_t h[CTR_HULL_DEFER_END];
+  uint32_t h[CTR_HULL_TILT_END];
   HIP_TRY(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   auto per = [&](int sum, int n) { return h[n] ? (double)h[sum] / h[n] : 0.0; };
@@ -453,8 +468,12 @@ static int print_bounce_stats(clwh_ctx *ctx, const RenderArgs &a) {
                (double)a.hull_delta0);
   const uint32_t *m = h + CTR_HULL_DEFER;
   std::fprintf(stderr, "[bounce stats] hull certificates tried/granted/wrong: first legs deferred=%u/%u/%u rebounds at once=%u/%u/%u rebounds deferred=%u/%u/%u; "
-               "J=%d D=%.4g defer_delta0=%.6f; look-ups=%u\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], kHullDeferSteps, (double)kHullDeferDeficit,
-               (double)a.hull_defer_delta0, h[CTR_CERT_LANES] - ((CLVR_BOUNCE_STATS + 0) == 2 ? m[1] + m[7] : 0u));
+               "J=%d D=%.4g defer_delta0=%.6f; look-ups=%u\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], a.hull_h ? kHullTiltSteps : kHullDeferSteps, (double)kHullDeferDeficit,
+               (double)a.hull_defer_delta0, h[CTR_CERT_LANES] - ((CLVR_BOUNCE_STATS + 0) == 2 ? m[1] + m[7] + h[CTR_HULL_TILT + 4] + h[CTR_HULL_TILT + 10] : 0u) - h[CTR_HULL_TILT + 12]);
+  const uint32_t *t = h + CTR_HULL_TILT;
+  std::fprintf(stderr, "[bounce stats] tilted planes (%s) tried/granted/wrong: first legs at once=%u/%u/%u first legs deferred=%u/%u/%u rebounds at once=%u/%u/%u "
+               "rebounds deferred=%u/%u/%u; armed lanes that got there late and were sent back without a look-up=%u; target=%.6f\n", a.hull_h ? "on" : "off", t[0], t[1], t[2], t[3], t[4], t[5],
+               t[6], t[7], t[8], t[9], t[10], t[11], t[12], (double)a.hull_tilt_target);
   return CLWH_OK;
 }
 #endif
@@ -725,6 +744,30 @@ int clwh_debug_hull_defer_bound(int32_t X, int32_t Y, int32_t Z, float out[4]) {
   out[1] = (float)kHullDeferSteps;
   out[2] = kHullDeferDeficit;
   out[3] = (float)kHullMarginScale;
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_tilt_bound(int32_t X, int32_t Y, int32_t Z, float out[6]) {
+  if (!out || X < 1 || Y < 1 || Z < 1) return CLWH_ERR_INVALID_VALUE;
+  out[0] = hull_defer_delta0(X, Y, Z, kHullTiltSteps);
+  out[1] = (float)kHullTiltSteps;
+  out[2] = (float)kHullTiltPath;
+  out[3] = kHullTiltMargin;
+  hull_tilt_target(out[0], out[4], out[5]);
+  return CLWH_OK;
+}
+
+int clwh_debug_hull_h(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]) {
+  if (!ctx || !info_out) return CLWH_ERR_INVALID_VALUE;
+  if (!ctx->scene) return CLWH_ERR_BAD_ARGS;  // nothing rendered yet (or the derived data was dropped)
+  const PackedLayout L = scene_layout(ctx);
+  info_out[0] = kHullGrid; info_out[1] = kHullPlanes; info_out[2] = 0; info_out[3] = L.hull_table ? 1 : 0;
+  if (!host_out || !L.hull_table) return CLWH_OK;  // the size alone; or there is no table
+  const size_t bytes = (size_t)kHullPlanes * sizeof(float);
+  if (capacity < bytes || ctx->scene->data.bytes != L.bytes) return CLWH_ERR_SIZE_MISMATCH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(host_out, ctx->scene->data.as<uint8_t>() + L.off_hull_h, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return CLWH_OK;
 }
 

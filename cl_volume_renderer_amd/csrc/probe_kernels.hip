@@ -5,7 +5,7 @@
 // they are; this file holds no arithmetic of its own.  tests/test_gpu_device_functions.py compares every word with the
 // oracle (or, for the plain arithmetic, with numpy's binary32 operations in the order written).  The C entry, with its
 // checks of handles and sizes, stands with the other diagnostics in clwh_render.hip.
-#include "render_device.hpp"
+#include "bounce_device.hpp"
 
 namespace clvr {
 
@@ -22,6 +22,7 @@ __host__ __device__ __forceinline__ ProbeShape probe_shape_of(int which) {
     case CLWH_PROBE_ENV_APPROX: return {3u, 2u};
     case CLWH_PROBE_TONE: return {4u, 1u};
     case CLWH_PROBE_TAPS: return {3u, 3u};
+    case CLWH_PROBE_HULL: return {5u, 5u};
     default: return {0u, 0u};
   }
 }
@@ -99,6 +100,14 @@ __global__ __launch_bounds__(256) void k_debug_device_probe(int which, const uin
       o[0] = taps_are_voxel_neighbours(p) ? 1u : 0u;
       o[1] = (uint32_t)((uint64_t)e & 0xFFFFFFFFu);
       o[2] = (uint32_t)((uint64_t)e >> 32);
+      break;
+    }
+    case CLWH_PROBE_HULL: {
+      const f3 n = hull_direction(r[0]);
+      const float scale = __uint_as_float(r[1]);
+      put_f3(o, n);
+      o[3] = hull_cell(f3{n.x * scale, n.y * scale, n.z * scale});
+      o[4] = hull_cell(f3_at(r + 2));
       break;
     }
     default: break;

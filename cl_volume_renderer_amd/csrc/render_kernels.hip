@@ -124,6 +124,11 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   const bool hull_defer = hull_cert && a.hull_planes != nullptr;
   const int entry_hi_bits = hull_defer ? 3 : 8;  // C_ENTRY_HI's layout (wave-uniform)
   const uint32_t *hull_words = hull_defer ? a.hull_planes : a.hull_codes;  // the word per hit the refill reads
+  // ... and a march that the hit's plane neither grants nor arms asks the plane tilted towards its own direction (CLWH_TUNE_HULL_TILT=0: no)
+  const bool hull_tilt = hull_defer && a.hull_h != nullptr;
+  // an armed lane's grant fires while it has at least this budget left: two constants and the flag -- J as a kernel argument, one more
+  // scalar live across the step loop, gave every instance a private segment
+  constexpr uint32_t kFireDefer = (uint32_t)(70 - kHullDeferSteps) * kOneStep, kFireTilt = (uint32_t)(70 - kHullTiltSteps) * kOneStep;
   bool exhausted = false;  // wave-uniform: the queue has no more items
   BounceStats stats;
 
@@ -180,16 +185,24 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         const int n_cert = __popcll(__ballot(st == ST_CERT));
         if (n_cert != 0 && (n_cert >= cert_min_lanes || __popcll(__ballot(st == ST_MARCH)) < a.step_min_lanes)) {
           stats.cert_begin(st, n_cert);
-          // deferred hull grant: the lane has covered the path that puts it in front of its hit's plane; with at most kHullDeferSteps
+          // deferred hull grant: the lane has covered the path that puts it in front of its plane; with at most J (kHullDeferSteps, with
+          // tilted planes kHullTiltSteps)
           // steps taken the theorem holds from here (hull_defer_delta0, clwh_internal.hpp) -- no look-up.  Later than that it is a march
-          // like any other.
-          const bool fired = !USE_GRAD && st == ST_CERT && (march & kArmed) != 0u && (march & ~kArmed) >= (uint32_t)(70 - kHullDeferSteps) * kOneStep;
+          // like any other; with tilted planes (three times as many lanes are armed, 7.25 M instead of 2.3 M per configs[1] launch, and
+          // 1.17 M of them get there late: profiles/bounce_hull_tilt_counters.txt) one whose next step is too short to ask the table
+          // goes back to marching without a look-up.
+          const bool was_armed = !USE_GRAD && st == ST_CERT && (march & kArmed) != 0u;
+          const bool fired = was_armed && (march & ~kArmed) >= (hull_tilt ? kFireTilt : kFireDefer);
+          const bool late = hull_tilt && was_armed && !fired && sd < cert_at;
           stats.hull_fired(fired, i == 8);
+          stats.hull_late(late);
           if (st == ST_CERT) {
             if (!USE_GRAD) march &= ~kArmed;  // (no lane of a USE_GRAD instance is ever armed)
             int away;
             if (fired && !kStartCertVerify) {
               st = ST_EVENT + EV_EXIT;
+            } else if (late) {
+              st = ST_MARCH;  // (bit 23 stays set: it asks at its next step that is long enough)
             } else if (certify_exit(a, ray.origin, ray.direction, (int)(march >> 24), away)) {
               st = ST_EVENT + EV_EXIT;  // the march WOULD end in Exit_volume; only its direction matters from here on
             } else {
@@ -410,6 +423,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
     bool hc_tried = false, hc_granted = false;  // ... a hull certificate
     bool rb_tried = false, rb_granted = false;  // this lane's rebound from a secondary hit asked for / holds a hull certificate
     uint32_t armed_path = 0u;                   // != 0: this lane's march may be granted once it has covered this path (deferred grant)
+    bool tl_tried = false, tl_granted = false, tl_armed = false;  // this lane's march asked a tilted plane / holds its certificate / is armed by it
+    bool started = false;                       // this lane starts a march in this half (statistics)
     if (st >= ST_EVENT) {
       const int ev = st - ST_EVENT;
       bool start_path = (ev == EV_START);  // begin distribution ray `o` from the primary hit
@@ -498,11 +513,29 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
           else { hc_tried = tried && m >= 0.0f; hc_granted = granted; }
           if (tried && dir_ok && !sc_granted && m < 0.0f && m >= -kHullDeferDeficit && dn >= a.hull_defer_delta0)
             armed_path = (uint32_t)ceilf(-m * __builtin_amdgcn_rcpf(dn) * (1.0f + 0x1p-19f));  // at least -m / dn, at most 8 x 64 + 1
+          // Tilted plane (clwh_internal.hpp: the proof).  What the hit's own plane neither grants nor arms asks the plane of the same table
+          // whose normal is n_k (a hit without a word: the bounce's normal) turned towards the direction of travel just far enough that
+          // direction . n' reaches the target: found in closed form, its h_k' read from the 16 KB copy of the table's fourth column.
+          if (hull_tilt && dir_ok && !granted && !sc_granted && armed_path == 0u) {
+            const f3 n0{tried ? n.x : bn.x, tried ? n.y : bn.y, tried ? n.z : bn.z};
+            const float c = dot3(dir, n0);
+            const float lambda = c >= a.hull_tilt_target ? 0.0f : a.hull_tilt_gain * __builtin_amdgcn_sqrtf(fmaxf(1.0f - c * c, 0.0f)) - c;
+            const unsigned k2 = hull_cell(f3{n0.x + lambda * dir.x, n0.y + lambda * dir.y, n0.z + lambda * dir.z});
+            const f3 n2 = hull_direction(k2);
+            const float dn2 = dot3(dir, n2), m2 = dot3(n2, nr.origin) - a.hull_h[k2];
+            tl_tried = true;
+            if (m2 >= 0.0f && dn2 >= a.hull_delta0) {
+              tl_granted = true;
+            } else if (m2 < 0.0f && dn2 >= a.hull_defer_delta0) {
+              const float need = ceilf(-m2 * __builtin_amdgcn_rcpf(dn2) * (1.0f + 0x1p-19f));  // at least -m2 / dn2 (+inf: a table without events)
+              if (need <= (float)kHullTiltPath) { armed_path = (uint32_t)need; tl_armed = true; }
+            }
+          }
         }
         ray = nr;
       }
 
-      if ((sc_granted || hc_granted || rb_granted) && !kStartCertVerify) {
+      if ((sc_granted || hc_granted || rb_granted || tl_granted) && !kStartCertVerify) {
         st = ST_EVENT + EV_EXIT;  // the next closing half takes it from here
       } else {
         // start (or continue) a march: its first SDF read is at trunc(origin) (utility_ray.cl:148-150)
@@ -510,11 +543,13 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
         march = 70u * kOneStep + kCertReady;
         if (armed_path != 0u) march = kArmed + 70u * kOneStep + kCertReady - armed_path;
         st = ST_MARCH;
+        started = true;
       }
     }
     stats.start_cert(sc_tried, sc_granted);
     stats.hull_cert(hc_tried, hc_granted, hc_granted && sc_granted);
-    stats.hull_more(rb_tried, rb_granted, armed_path != 0u && st == ST_MARCH, i == 8);
+    stats.hull_more(rb_tried, rb_granted, armed_path != 0u && !tl_armed && st == ST_MARCH, i == 8);
+    stats.hull_tilt(tl_tried, tl_granted, tl_armed && st == ST_MARCH, started, i == 8);
   }
 #undef COLD_ENTRY_HI
 #undef COLD

@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void k_hull_support(const int2 *__restrict__ e
   }
   if (best > -INFINITY) atomicMax(&best_out[4u * k + 3u], ordered_bits(best));  // the entry's fourth word
 }
-__global__ __launch_bounds__(256) void k_hull_finish(const uint32_t *__restrict__ regular, float4 *__restrict__ hull) {
+__global__ __launch_bounds__(256) void k_hull_finish(const uint32_t *__restrict__ regular, float4 *__restrict__ hull, float *__restrict__ hull_h) {
   const unsigned k = blockIdx.x * 256u + threadIdx.x;
   const f3 n = hull_direction(k);
   const uint32_t o = reinterpret_cast<const uint32_t *>(hull)[4u * k + 3u];  // k_hull_support's maximum, 0: no event voxel
@@ -390,8 +390,9 @@ __global__ __launch_bounds__(256) void k_hull_finish(const uint32_t *__restrict_
   float h = INFINITY;
   if (o != 0u && *regular != 0u) h = (__uint_as_float(b) + ((fmaxf(n.x, 0.0f) + fmaxf(n.y, 0.0f)) + fmaxf(n.z, 0.0f))) + kHullSlack;
   hull[k] = make_float4(n.x, n.y, n.z, h);
+  hull_h[k] = h;  // the same bits, alone: 16 KB that k_bounce's tilted-plane test reads (render_kernels.hip)
 }
-hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, int X, int Y, int Z, hipStream_t s) {
+hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *hull, float *hull_h, int X, int Y, int Z, hipStream_t s) {
   (void)X;
   const hipError_t e = hipMemsetAsync(hull, 0, (size_t)kHullPlanes * sizeof(float4), s);
   if (e != hipSuccess) return e;
@@ -399,7 +400,7 @@ hipError_t launch_hull_table(const int2 *ends, const uint32_t *regular, float4 *
   // the running maxima sit in the entries' fourth words (stride 4 words)
   hipLaunchKernelGGL(k_hull_support, dim3((unsigned)kHullPlanes / 256u, ((unsigned)n_rows + (unsigned)kHullRows - 1u) / (unsigned)kHullRows), dim3(256), 0, s, ends, Y, n_rows,
                      reinterpret_cast<uint32_t *>(hull));
-  hipLaunchKernelGGL(k_hull_finish, dim3((unsigned)kHullPlanes / 256u), dim3(256), 0, s, regular, hull);
+  hipLaunchKernelGGL(k_hull_finish, dim3((unsigned)kHullPlanes / 256u), dim3(256), 0, s, regular, hull, hull_h);
   return hipGetLastError();
 }
 

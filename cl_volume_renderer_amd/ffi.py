@@ -39,9 +39,9 @@ REGION_MASK, REGION_LABELS = 0, 1
 OVERLAY_FILL, OVERLAY_OUTLINE, OVERLAY_DENSE = 1, 2, 4
 SHADE_LIGHT, SHADE_AO = 0, 1
 (PROBE_ARITH, PROBE_HASH, PROBE_HEMISPHERE, PROBE_RAY, PROBE_CUT, PROBE_ENV_EXACT, PROBE_ENV_FAST, PROBE_ENV_APPROX, PROBE_TONE,
- PROBE_TAPS) = range(10)
+ PROBE_TAPS, PROBE_HULL) = range(11)
 # clwh_debug_device_probe: (words per input record, words per output record) of each probe
-PROBE_WORDS = ((6, 12), (1, 1), (7, 6), (10, 3), (6, 4), (3, 1), (3, 2), (3, 2), (4, 1), (3, 3))
+PROBE_WORDS = ((6, 12), (1, 1), (7, 6), (10, 3), (6, 4), (3, 1), (3, 2), (3, 2), (4, 1), (3, 3), (5, 5))
 SCENE_HIT_RECORDS, SCENE_STEP_BYTES, SCENE_BRICK_MIN = range(3)            # clwh_debug_packed_scene
 VIEW_BRICKS, VIEW_TABLE, VIEW_DILATED, VIEW_COARSE = range(4)               # clwh_debug_view_data
 TIMERS = ("bounce", "primary", "fixup", "resolve", "repack", "ao")
@@ -412,6 +412,8 @@ _PROTOTYPES = [
     ("clwh_debug_hull_codes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("clwh_debug_hull_planes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("clwh_debug_hull_defer_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    ("clwh_debug_hull_tilt_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    ("clwh_debug_hull_h", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     ("clwh_strerror", C.c_char_p, [C.c_int]),
     ("clwh_last_hip_error", C.c_int, []),
     ("clwh_version", C.c_char_p, []),
@@ -469,6 +471,15 @@ def hull_defer_bound(X: int, Y: int, Z: int):
     v = (C.c_float * 4)()
     _check(lib().clwh_debug_hull_defer_bound(X, Y, Z, v), "clwh_debug_hull_defer_bound")
     return float(v[0]), int(v[1]), float(v[2]), int(v[3])
+
+
+def hull_tilt_bound(X: int, Y: int, Z: int):
+    """(delta, J, P, margin, target, gain) of the tilted planes: the bound over 70 - 5 - J steps, the J armed marches
+    get with the rule on, the longest path a tilted plane may ask a march to count, and the tilt's target t = delta + margin with
+    gain = t / sqrt(1 - t^2), as k_bounce gets them"""
+    v = (C.c_float * 6)()
+    _check(lib().clwh_debug_hull_tilt_bound(X, Y, Z, v), "clwh_debug_hull_tilt_bound")
+    return float(v[0]), int(v[1]), int(v[2]), float(v[3]), float(v[4]), float(v[5])
 
 
 def start_cert_dmin(X: int, Y: int, Z: int) -> float:
@@ -1282,6 +1293,17 @@ class Context:
             return None
         out = np.empty((info[1], 4), np.float32)
         _check(lib().clwh_debug_hull_table(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_hull_table")
+        return out
+
+    def hull_h(self):
+        """the hull table's h_k alone, float32 [planes], as k_bounce's tilted-plane test reads them (clwh_debug_hull_h); None when the
+        table was not built"""
+        info = (C.c_int32 * 4)()
+        _check(lib().clwh_debug_hull_h(self.h, None, C.c_uint64(0), info), "clwh_debug_hull_h")
+        if not info[3]:
+            return None
+        out = np.empty(info[1], np.float32)
+        _check(lib().clwh_debug_hull_h(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.nbytes), info), "clwh_debug_hull_h")
         return out
 
     def hull_codes(self):

@@ -1094,6 +1094,8 @@ int clwh_debug_wave_min(clwh_ctx *ctx, clwh_mem *u32_in, uint64_t n, clwh_mem *u
  *   TONE         sr sg sb count                                 tone_map_rgba8
  *   TAPS         p[3]                                           taps_are_voxel_neighbours(p), cache_entry_of(params[0], params[1], p) as
  *                                                               int64: low word, high word
+ *   HULL         k (uint32), scale, v[3]                        hull_direction(k)[3], hull_cell(scale * hull_direction(k)), hull_cell(v):
+ *                                                               the hull table's directions and the octahedral cell a vector falls in
  * `aux` is read by the two ENV probes only (null otherwise): an environment image of w * h words, row-major; a caller that stores
  * j * w + i in texel (i, j) reads back the texel the sampler chose.  CLWH_ERR_INVALID_VALUE: a null ctx / in / out / params, an unknown
  * `which`, an ENV probe without aux or with w < 1 or h < 1; CLWH_ERR_SIZE_MISMATCH: n >= 2^31, or `in`, `out` or `aux` shorter than
@@ -1109,7 +1111,8 @@ enum clwh_probe {
   CLWH_PROBE_ENV_APPROX = 7,
   CLWH_PROBE_TONE = 8,
   CLWH_PROBE_TAPS = 9,
-  CLWH_PROBE_COUNT = 10
+  CLWH_PROBE_HULL = 10,
+  CLWH_PROBE_COUNT = 11
 };
 int clwh_debug_device_probe(clwh_ctx *ctx, int32_t which, clwh_mem *in, uint64_t n, clwh_mem *out, clwh_mem *aux, const int32_t params[4]);
 /* the exit-certificate table of the derived scene data the context rendered from last: info_out = {cells along x, y, z,
@@ -1175,6 +1178,13 @@ int clwh_debug_hull_planes(clwh_ctx *ctx, void *host_out, uint64_t capacity, uin
 /* out = {the smallest direction . n_k with which a march that has got in front of its plane within J literal steps is granted in a
  * volume of X x Y x Z voxels (2: never), J, D (voxels), scale} */
 int clwh_debug_hull_defer_bound(int32_t X, int32_t Y, int32_t Z, float out[4]);
+/* tilted planes: out = {the same bound over 70 - 5 - J steps with the J that armed marches get when the rule is on
+ * (2: never), that J, the longest path P a tilted plane may ask a march to count, the margin the tilt aims above the bound, the target
+ * t, t / sqrt(1 - t^2)} */
+int clwh_debug_hull_tilt_bound(int32_t X, int32_t Y, int32_t Z, float out[6]);
+/* the hull table's h_k alone (4096 floats), as k_bounce's tilted-plane test reads them; info_out = {grid, planes, 0, 1 if the scene has
+ * the table}.  host_out NULL: the size alone */
+int clwh_debug_hull_h(clwh_ctx *ctx, void *host_out, uint64_t capacity, int32_t info_out[4]);
 const char *clwh_strerror(int status);
 int clwh_last_hip_error(void);
 const char *clwh_version(void);
