@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,7 +12,7 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
@@ -29,6 +29,11 @@
 // voxel to the piece that reaches it first (renderer::split_mask).  One JSON line {"split": {"radius_sq", "weight", "connectivity",
 // "parts", "counts"}}, counts being the voxels of up to the 8 largest parts (renderer::measure_labels), follows the item's other
 // lines; the mask that is applied is unchanged.  With show, the parts are coloured by their id.
+// centerline=X,Y,Z, an item of --grow: the centreline of the mask that is applied (after any morphology) from the grow seed to the voxel
+// (X, Y, Z), by the cheapest path through a cost that is low in the middle of the structure and high at its wall, 26 neighbours
+// (renderer::centerline).  One JSON line {"centerline": {"from", "to", "points"}} follows the item's other lines, and with an `out`
+// argument the points are written beside it, to <out>.centerline.txt, one "x y z" line each, the seed first.  An end outside the
+// mask gives 0 points.  The three numbers follow the item's name, so the item takes three fields of the list.
 // measure, an item of --grow and of --components: a second JSON line with the exact record (renderer::measure_mask: count, sum, sum_sq,
 // min, max, sum_pos, bbox, faces, border_faces) of the mask that is applied, after any morphology and before the volume is changed:
 // {"measure": {...}}; for --components {"measure_components": [...]}, the records (renderer::measure_labels) of the selected ranks,
@@ -78,6 +83,8 @@ int main(int argc_in, char const *argv_in[]) {
   float morph_radius = 0.0f;
   bool measure = false;  // the measure item
   float split_radius = -1.0f;  // the split= item's erosion radius in x-voxels, or -1
+  bool centerline = false;     // the centerline= item of --grow
+  uint32_t centerline_end[3] = {0, 0, 0};
   int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
   bool rewrites = false; // a keep, remove or fill= item
   // whether `v` is the show item; *ok is cleared if its style is unknown
@@ -113,7 +120,7 @@ int main(int argc_in, char const *argv_in[]) {
     return true;
   };
   static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -198,6 +205,21 @@ int main(int argc_in, char const *argv_in[]) {
           grow_flags |= CLWH_GROW_26;
         } else if (morph_item(v, &ok)) {
         } else if (split_item(v, &ok)) {
+        } else if (v.rfind("centerline=", 0) == 0) {  // X here, Y and Z in the next two fields
+          ok = ok && !centerline;
+          centerline = true;
+          std::string number = v.substr(11);
+          for (int q = 0; q < 3 && ok; ++q) {
+            if (q > 0) {
+              const size_t next = rest.find(',');
+              number = rest.substr(0, next);
+              ok = !rest.empty() && !(next != std::string::npos && next + 1 == rest.size());
+              rest = next == std::string::npos ? "" : rest.substr(next + 1);
+            }
+            const long long n = std::strtoll(number.c_str(), &end, 10);
+            ok = ok && !number.empty() && *end == '\0' && n >= 0 && n <= 0x7fffffffLL;
+            centerline_end[q] = (uint32_t)n;
+          }
         } else if (v == "measure") {
           measure = true;
         } else if (show_item(v, &ok)) {
@@ -330,7 +352,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -399,6 +421,19 @@ int main(int argc_in, char const *argv_in[]) {
     clwh_mask_stats_result measured{};
     if (measure) measured = r.measure_mask(none);  // of the volume as loaded: before the mask changes it
     if (split_radius >= 0.0f) split(none, (grow_flags & CLWH_GROW_26) != 0);
+    std::vector<uint32_t> line;  // the centerline= item: from its end back to the seed
+    if (centerline) {
+      for (int q = 0; q < 3; ++q)
+        if (centerline_end[q] >= size[q]) {
+          std::cout << "The centerline end (" << centerline_end[0] << ", " << centerline_end[1] << ", " << centerline_end[2] << ") lies outside the volume\n";
+          return 1;
+        }
+      line = r.centerline(none, grow_seed, centerline_end);
+      if (argc > 6) {
+        std::ofstream file(std::string(argv[6]) + ".centerline.txt");
+        for (size_t k = line.size() / 3; k-- > 0;) file << line[3 * k] << ' ' << line[3 * k + 1] << ' ' << line[3 * k + 2] << '\n';
+      }
+    }
     if (show < 0) r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
@@ -415,6 +450,9 @@ int main(int argc_in, char const *argv_in[]) {
       std::printf("}\n");
     }
     std::printf("%s", split_line.c_str());
+    if (centerline)
+      std::printf("{\"centerline\": {\"from\": [%u, %u, %u], \"to\": [%u, %u, %u], \"points\": %llu}}\n", grow_seed[0], grow_seed[1], grow_seed[2],
+                  centerline_end[0], centerline_end[1], centerline_end[2], (unsigned long long)(line.size() / 3));
   }
 
   if (comps) {  // like --grow: everything below sees the masked volume

@@ -188,6 +188,15 @@ unsigned long long clvr_host_trace_path(clvr_host *h, const unsigned target[3], 
   std::memcpy(out, points.data(), std::min<size_t>(points.size(), (size_t)capacity * 3) * sizeof(uint32_t));
   return points.size() / 3;
 }
+// renderer::centerline from `start` to `end` inside the region mask: up to `capacity` (x, y, z) triples into out, `end` first; returns
+// the true count
+unsigned long long clvr_host_centerline(clvr_host *h, const unsigned start[3], const unsigned end[3], int flags, float max_radius,
+                                        unsigned sharpness, unsigned *out, unsigned long long capacity) {
+  const std::vector<uint32_t> points = h->rend.centerline(h->state, start, end, flags, max_radius, sharpness);
+  std::memcpy(out, points.data(), std::min<size_t>(points.size(), (size_t)capacity * 3) * sizeof(uint32_t));
+  return points.size() / 3;
+}
+
 // renderer::split_mask: the region split into parts that become the labelling; out = {radius_sq, wx, wy, wz}; returns the number of parts
 unsigned long long clvr_host_split_mask(clvr_host *h, float radius, int flags, unsigned out[4]) {
   const renderer::split_summary s = h->rend.split_mask(h->state, radius, flags);

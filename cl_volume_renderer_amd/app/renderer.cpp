@@ -27,6 +27,7 @@ renderer::renderer(clw_context &c)
       held_mask(ctx, std::vector<uint32_t>(2)),
       region_labels(ctx, std::vector<uint32_t>(1)),
       region_dist(ctx, std::vector<uint32_t>(1)),
+      region_cost(ctx, std::vector<uint16_t>(1)),
       overlay_palette(ctx, std::vector<uint32_t>(overlay_colours()), true),
       sdf(ctx) {}
 
@@ -564,6 +565,138 @@ renderer::split_summary renderer::split_mask(struct ui_state &, float radius, in
   d.result = &grown;
   clw_fail_hard_on_error(clwh_mask_geodesic(ctx.get_handle(), &d));
   return out;
+}
+
+void renderer::cost_multipliers(uint32_t face[3], uint32_t edge[3], uint32_t *corner) const {
+  const auto &sizes = volume->get_voxel_sizes();
+  double s[3];
+  for (int q = 0; q < 3; ++q) s[q] = (double)sizes[q] * 10.0;
+  const auto mult = [](double length) {
+    const double m = std::max(1.0, std::nearbyint(length));
+    if (m > 255.0) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);  // voxels too unequal for a multiplier of 8 bits
+    return (uint32_t)m;
+  };
+  for (int q = 0; q < 3; ++q) {
+    face[q] = mult(s[q]);
+    edge[q] = mult(std::sqrt(s[(q + 1) % 3] * s[(q + 1) % 3] + s[(q + 2) % 3] * s[(q + 2) % 3]));
+  }
+  *corner = mult(std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]));
+}
+
+std::vector<uint16_t> renderer::centerline_cost_table(uint32_t r_sq_max, uint32_t sharpness) {
+  if (r_sq_max < 1 || r_sq_max > 65535 || sharpness > 65534) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  std::vector<uint16_t> table((size_t)r_sq_max + 1);
+  const uint64_t r = r_sq_max;  // sharpness * r^2 < 2^48
+  for (uint64_t d = 0; d <= r; ++d) table[d] = (uint16_t)(1 + ((uint64_t)sharpness * (r - d) * (r - d)) / (r * r));
+  return table;
+}
+
+void renderer::cost_field(struct ui_state &, int source, const std::vector<uint16_t> &table, int64_t lo, uint32_t shift, bool masked) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  const bool have_mask = region_mask.size() == 2 * ((size[0] + 63) / 64) * size[1] * size[2];
+  if ((masked || source == COST_FROM_DEPTH) && !have_mask) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  if (region_cost.size() != voxels) region_cost = clw_vector<uint16_t>(ctx, std::vector<uint16_t>(voxels), false);
+  clw_vector<uint32_t> depth(ctx, std::vector<uint32_t>(source == COST_FROM_DEPTH ? voxels : 1), false);
+  clwh_cost_field_desc d{};
+  if (source == COST_FROM_DEPTH) {
+    clwh_distance_desc m{};
+    m.mask = region_mask.get_device_reference();
+    m.dist = depth.get_device_reference();
+    for (int q = 0; q < 3; ++q) m.dims[q] = (uint32_t)size[q];
+    mask_weights(m.weight);
+    m.cap = CLWH_DIST_NONE;
+    m.flags = CLWH_DIST_TO_CLEAR;
+    clw_fail_hard_on_error(clwh_mask_distance(ctx.get_handle(), &m));
+    d.source = depth.get_device_reference();
+    d.kind = CLWH_COST_SRC_U32;
+  } else {
+    d.source = volume->get_reference_volume().get_device_reference();
+    d.kind = source == COST_FROM_VALUE ? CLWH_COST_SRC_VALUE : CLWH_COST_SRC_GRADIENT;
+  }
+  d.domain = masked ? region_mask.get_device_reference() : nullptr;
+  d.cost = region_cost.get_device_reference();
+  d.table = table.data();
+  d.lo = lo;
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.n = (uint32_t)table.size();
+  d.shift = shift;
+  clw_fail_hard_on_error(clwh_cost_from_field(ctx.get_handle(), &d));
+}
+
+renderer::geodesic_summary renderer::cost_geodesic(struct ui_state &, const std::vector<uint32_t> &seeds, int flags, uint32_t cap) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  if (region_cost.size() != voxels) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no cost
+  if (region_labels.size() != voxels) region_labels = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  if (region_dist.size() != voxels) region_dist = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  geodesic_summary out;
+  clwh_cost_geodesic_desc d{};
+  d.cost = region_cost.get_device_reference();
+  d.dist = region_dist.get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  cost_multipliers(d.mult_face, d.mult_edge, &d.mult_corner);
+  d.cap = cap;
+  d.flags = flags & ~CLWH_GEO_FROM_LABELS;
+  d.n_seeds = (uint32_t)(seeds.size() / 4);
+  d.seeds = seeds.data();
+  d.result = &out.result;
+  clw_fail_hard_on_error(clwh_cost_geodesic(ctx.get_handle(), &d));
+  region_dist.pull();
+  out.dist.assign(&region_dist[0], &region_dist[0] + voxels);
+  return out;
+}
+
+std::vector<uint32_t> renderer::trace_cost_path(struct ui_state &, const uint32_t target[3], int flags) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  if (region_cost.size() != voxels || region_dist.size() != voxels || region_labels.size() != voxels)
+    clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no map
+  uint64_t n = 0;
+  clwh_cost_trace_desc d{};
+  d.cost = region_cost.get_device_reference();
+  d.dist = region_dist.get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  for (int q = 0; q < 3; ++q) {
+    d.dims[q] = (uint32_t)size[q];
+    d.target[q] = target[q];
+  }
+  cost_multipliers(d.mult_face, d.mult_edge, &d.mult_corner);
+  d.flags = flags & CLWH_GEO_26;
+  d.n_points = &n;
+  clw_fail_hard_on_error(clwh_cost_trace(ctx.get_handle(), &d));  // the count; then the points
+  if (n == 0) return {};
+  clw_vector<uint32_t> points(ctx, std::vector<uint32_t>((size_t)n * 3), false);
+  d.points = points.get_device_reference();
+  d.capacity = n;
+  clw_fail_hard_on_error(clwh_cost_trace(ctx.get_handle(), &d));
+  points.pull();
+  return std::vector<uint32_t>(&points[0], &points[0] + points.size());
+}
+
+std::vector<uint32_t> renderer::centerline(struct ui_state &state, const uint32_t start[3], const uint32_t end[3], int flags, float max_radius,
+                                           uint32_t sharpness) {
+  const auto &size = volume->get_volume_size();
+  for (int q = 0; q < 3; ++q)
+    if (start[q] >= size[q] || end[q] >= size[q]) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  uint32_t r_sq_max = 1;
+  if (max_radius > 0.0f) {
+    r_sq_max = std::max(1u, mask_radius_sq(max_radius));
+  } else {  // the deepest voxel of the region, on the host
+    const std::vector<uint32_t> depth = distance_map(state, true);
+    region_mask.pull();
+    const size_t words_per_row = 2 * ((size[0] + 63) / 64);
+    for (size_t row = 0; row < (size_t)size[1] * size[2]; ++row)
+      for (size_t x = 0; x < size[0]; ++x)
+        if (((region_mask[row * words_per_row + (x >> 5)] >> (x & 31)) & 1u) && depth[row * size[0] + x] != CLWH_DIST_NONE)
+          r_sq_max = std::max(r_sq_max, depth[row * size[0] + x]);
+  }
+  uint32_t shift = 0;  // scene.centerline_shift: the depths within the table's 65535
+  while ((r_sq_max >> shift) > 65535u) ++shift;
+  cost_field(state, COST_FROM_DEPTH, centerline_cost_table(r_sq_max >> shift, sharpness), 0, shift, true);
+  cost_geodesic(state, {start[0], start[1], start[2], 1u}, flags & (CLWH_GEO_26 | CLWH_GEO_DENSE));
+  return trace_cost_path(state, end, flags);
 }
 
 clwh_mask_stats_result renderer::measure_mask(struct ui_state &, int hist_lo, int bin_width, int n_bins, std::vector<uint64_t> *hist) {

@@ -160,6 +160,25 @@ class renderer : public frame_emitter {
   };
   split_summary split_mask(struct ui_state &state, float radius, int flags = 0);
 
+  // not in the reference: cheapest paths through a COST FIELD (clwh_cost_from_field / clwh_cost_geodesic / clwh_cost_trace), where a
+  // step into a voxel costs the direction's multiplier times that voxel's cost.  cost_multipliers: the Euclidean length of each step
+  // in 1/10 of an x-voxel, rounded (the 10 / 14 / 17 chamfer for cubic voxels), which must stay within 1 .. 255.  cost_field: the
+  // cost on the device from `table` (1 .. 65536 entries) indexed by clamp((s - lo) >> shift): s is the region's depth map (the exact
+  // squared distance to the nearest voxel outside the region, in mask_weights' unit), the volume's value or its squared gradient;
+  // `masked`: 0 outside the region mask.  cost_geodesic: geodesic_map over that cost (a masked cost is a wall outside the region),
+  // whose maps trace_cost_path then reads.  centerline: the four steps at once, from the voxel `start` to the voxel `end` inside the
+  // region: the depth map, the table centerline_cost_table over it (scene.centerline_cost_table's integers; max_radius in x-voxels
+  // is the largest radius of interest, 0 takes the depth map's largest value on the host: for small volumes), the cost geodesic from
+  // `start` and the path from `end`: (x, y, z) triples, `end` first; empty if either lies outside the region.  All wait for the device.
+  enum cost_source { COST_FROM_DEPTH = 0, COST_FROM_VALUE = 1, COST_FROM_GRADIENT = 2 };
+  void cost_multipliers(uint32_t face[3], uint32_t edge[3], uint32_t *corner) const;
+  static std::vector<uint16_t> centerline_cost_table(uint32_t r_sq_max, uint32_t sharpness = 100);
+  void cost_field(struct ui_state &state, int source, const std::vector<uint16_t> &table, int64_t lo = 0, uint32_t shift = 0, bool masked = true);
+  geodesic_summary cost_geodesic(struct ui_state &state, const std::vector<uint32_t> &seeds, int flags = 0, uint32_t cap = CLWH_DIST_NONE);
+  std::vector<uint32_t> trace_cost_path(struct ui_state &state, const uint32_t target[3], int flags = 0);
+  std::vector<uint32_t> centerline(struct ui_state &state, const uint32_t start[3], const uint32_t end[3], int flags = CLWH_GEO_26,
+                                   float max_radius = 0.0f, uint32_t sharpness = 100);
+
   // not in the reference: measuring (clwh_mask_statistics / clwh_label_statistics) on the volume the views show.  measure_mask: the
   // exact record of the region mask, whoever made it (count, sum, sum of squares, extremes, centroid numerators, bounding box, faces
   // per axis inside the volume and on its border), and with n_bins > 0 the histogram of its values, n_bins bins of bin_width from
@@ -202,6 +221,7 @@ class renderer : public frame_emitter {
   clw_vector<uint32_t> held_mask;            // hold_mask's copy of region_mask (never pulled)
   clw_vector<uint32_t> region_labels;        // label_components' ranks on the device, one word per voxel (never pulled)
   clw_vector<uint32_t> region_dist;          // geodesic_map's distances on the device, for trace_path
+  clw_vector<uint16_t> region_cost;          // cost_field's cost on the device (never pulled)
   clw_vector<uint32_t> overlay_palette;      // overlay_colours() on the device, pushed once, by the constructor
   template <class Desc>
   void fill_overlay(Desc &d, const struct ui_state &state, int source, const overlay_style &style);

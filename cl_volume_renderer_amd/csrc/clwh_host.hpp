@@ -2,7 +2,7 @@
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
-// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_region_stats.hip: statistics of masks and labels).
+// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
 #pragma once
 
@@ -257,6 +257,17 @@ struct GeodesicScratch {
   TileScratch work;
 };
 
+// clwh_cost_from_field's scratch: the table on the device and the page-locked copy it travels from (the call does not wait, and the
+// caller's table need not outlive it), 65536 entries each; `copied` is recorded behind the copy, and the next call waits for it -- not
+// for the stream -- before it overwrites the page-locked copy.  clwh_cost_geodesic and clwh_cost_trace use the geodesic's scratch.
+struct CostScratch {
+  DeviceBuffer table;
+  uint16_t *host = nullptr;
+  Event copied;
+  bool in_flight = false;
+  ~CostScratch() { if (host) (void)hipHostFree(host); }
+};
+
 // clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
 // Every call rewrites what it reads: only the allocation is kept.
 struct RegionStatsScratch {
@@ -324,6 +335,7 @@ struct clwh_ctx {
   clvr::LabelScratch label;
   clvr::DistanceScratch distance;
   clvr::GeodesicScratch geodesic;
+  clvr::CostScratch cost;
   clvr::RegionStatsScratch region_stats;
   clvr::OverlayScratch overlay;
   clvr::ProjectionData proj;

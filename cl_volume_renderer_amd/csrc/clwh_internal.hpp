@@ -676,6 +676,33 @@ hipError_t launch_geo_round(const GeoArgs &a, uint32_t round, int slot, hipStrea
 hipError_t launch_geo_finish(const GeoArgs &a, hipStream_t s);  // dist, labels, *result
 hipError_t launch_geo_trace(const GeoTraceArgs &a, hipStream_t s);
 
+// ---- shortest paths through a cost field, the path behind such a distance, and the cost field from a table (costpath_kernels.hip; host
+// side clwh_costpath.hip).  The keys, the tiles and the rounds are the geodesic's; `g` holds what the two share, with the direction
+// multipliers (1 .. 255) in the weights' fields, a cap <= 0xFF000000 and a domain that may be null.
+struct CostArgs {
+  GeoArgs g;
+  const uint16_t *cost;        // [z][y][x], read only; 0 is a wall
+};
+struct CostTraceArgs {
+  GeoTraceArgs g;
+  const uint16_t *cost;
+};
+struct CostFieldArgs {
+  const uint32_t *words;       // CLWH_COST_SRC_U32
+  const int16_t *volume;       // CLWH_COST_SRC_VALUE, CLWH_COST_SRC_GRADIENT
+  const uint8_t *domain;       // grow's bit rows, or null
+  const uint16_t *table;       // device copy, n entries
+  uint16_t *cost;
+  long long lo;
+  int32_t X, Y, Z, W64;
+  uint32_t n, shift;
+  int32_t kind;                // clwh_cost_source
+};
+hipError_t launch_cost_init(const CostArgs &a, hipStream_t s);   // every key, the listed seeds, the stamps of the tiles that hold a seed
+hipError_t launch_cost_round(const CostArgs &a, uint32_t round, int slot, hipStream_t s);  // k_tile_list + k_cost_round, counters[2 * slot]
+hipError_t launch_cost_trace(const CostTraceArgs &a, hipStream_t s);
+hipError_t launch_cost_field(const CostFieldArgs &a, hipStream_t s);
+
 // ---- exact statistics of a mask's region and of every rank of a labelling (region_stats_kernels.hip; host side clwh_region_stats.hip).
 // Records are accumulated in place, in clwh_region_stats' layout: launch_stats_init sets the identities (extremes, bbox_lo), the sums'
 // kernels add with vector atomics, launch_stats_finish writes the empty record where nothing was added and makes bbox_hi exclusive.

@@ -32,6 +32,8 @@ DIST_NONE = 0xFFFFFFFF
 DIST_TO_CLEAR = 1
 GEO_26, GEO_FROM_LABELS, GEO_DENSE = 1, 2, 4
 GEO_CAP_MAX = 0xFFFF0000
+COST_CAP_MAX = 0xFF000000
+COST_SRC_U32, COST_SRC_VALUE, COST_SRC_GRADIENT = 0, 1, 2
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
@@ -272,6 +274,35 @@ class GeodesicTraceDesc(C.Structure):
 assert C.sizeof(GeodesicDesc) == 104 and C.sizeof(GeodesicTraceDesc) == 96 and C.sizeof(GeodesicResult) == 16
 
 
+class CostGeodesicDesc(C.Structure):
+    _fields_ = [
+        ("cost", C.c_void_p), ("domain", C.c_void_p), ("seed_labels", C.c_void_p), ("dist", C.c_void_p), ("labels", C.c_void_p),
+        ("dims", C.c_uint32 * 3), ("mult_face", C.c_uint32 * 3), ("mult_edge", C.c_uint32 * 3), ("mult_corner", C.c_uint32),
+        ("cap", C.c_uint32), ("flags", C.c_int32),
+        ("n_seeds", C.c_uint32), ("seeds", C.POINTER(C.c_uint32)),
+        ("result", C.POINTER(GeodesicResult)),
+    ]
+
+
+class CostTraceDesc(C.Structure):
+    _fields_ = [
+        ("cost", C.c_void_p), ("dist", C.c_void_p), ("labels", C.c_void_p), ("points", C.c_void_p), ("capacity", C.c_uint64),
+        ("dims", C.c_uint32 * 3), ("mult_face", C.c_uint32 * 3), ("mult_edge", C.c_uint32 * 3), ("mult_corner", C.c_uint32),
+        ("flags", C.c_int32), ("target", C.c_uint32 * 3),
+        ("n_points", C.POINTER(C.c_uint64)),
+    ]
+
+
+class CostFieldDesc(C.Structure):
+    _fields_ = [
+        ("source", C.c_void_p), ("domain", C.c_void_p), ("cost", C.c_void_p), ("table", C.POINTER(C.c_uint16)),
+        ("lo", C.c_int64), ("dims", C.c_uint32 * 3), ("n", C.c_uint32), ("shift", C.c_uint32), ("kind", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
+assert C.sizeof(CostGeodesicDesc) == 112 and C.sizeof(CostTraceDesc) == 104 and C.sizeof(CostFieldDesc) == 72
+
+
 class MaskCombineDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
 
@@ -388,6 +419,9 @@ _PROTOTYPES = [
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
     ("clwh_mask_geodesic", C.c_int, [C.c_void_p, C.POINTER(GeodesicDesc)]),
     ("clwh_geodesic_trace", C.c_int, [C.c_void_p, C.POINTER(GeodesicTraceDesc)]),
+    ("clwh_cost_geodesic", C.c_int, [C.c_void_p, C.POINTER(CostGeodesicDesc)]),
+    ("clwh_cost_trace", C.c_int, [C.c_void_p, C.POINTER(CostTraceDesc)]),
+    ("clwh_cost_from_field", C.c_int, [C.c_void_p, C.POINTER(CostFieldDesc)]),
     ("clwh_mask_statistics", C.c_int, [C.c_void_p, C.POINTER(MaskStatsDesc)]),
     ("clwh_label_statistics", C.c_int, [C.c_void_p, C.POINTER(LabelStatsDesc)]),
     ("clwh_overlay_slice", C.c_int, [C.c_void_p, C.POINTER(OverlaySliceDesc)]),
@@ -1146,6 +1180,162 @@ class Context:
             return (buf.pull(np.uint32)[:3 * k].reshape(k, 3).copy() if k else np.zeros((0, 3), np.uint32)), n
         finally:
             buf.release()
+
+    @staticmethod
+    def _cost_multipliers(d, multipliers):
+        """multipliers: None (all 1), (fx, fy, fz), or (face, edge, corner) as scene.geodesic_weights returns them"""
+        face, edge, corner = (1, 1, 1), (1, 1, 1), 1
+        if multipliers is not None:
+            if len(multipliers) == 3 and np.ndim(multipliers[0]) == 1:
+                face, edge, corner = multipliers
+            else:
+                face = multipliers
+        for k in range(3):
+            d.mult_face[k], d.mult_edge[k] = int(face[k]), int(edge[k])
+        d.mult_corner = int(corner)
+
+    def cost_from_field_raw(self, source: Mem, cost: Mem, dims, table, lo=0, shift=0, kind=COST_SRC_U32, domain: Mem = None, flags=0,
+                            n=None):
+        """one clwh_cost_from_field call: its status; nothing is raised.  table: uint16 entries, or None for a NULL table (then `n`
+        says how many it claims)"""
+        d = CostFieldDesc()
+        d.source, d.domain, d.cost = _handle(source), _handle(domain), _handle(cost)
+        if table is not None:
+            t = np.ascontiguousarray(np.asarray(table, dtype=np.uint16).reshape(-1))
+            d.table = t.ctypes.data_as(C.POINTER(C.c_uint16))
+        d.n = int(n) if n is not None else (len(t) if table is not None else 0)
+        d.lo, d.shift, d.kind, d.flags = int(lo), int(shift), int(kind), int(flags)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        return lib().clwh_cost_from_field(self.h, C.byref(d))
+
+    def cost_from_field(self, source: Mem, dims, table, lo=0, shift=0, kind=COST_SRC_U32, domain: Mem = None, cost: Mem = None) -> Mem:
+        """a cost field for cost_geodesic: cost(p) = table[clamp((s(p) - lo) >> shift, 0, len(table) - 1)], 0 where `domain` (a mask in
+        grow's layout) is given and clear; uint16 [z][y][x] on the device, allocated when none is given.  kind: COST_SRC_U32 (`source`
+        is a uint32 [z][y][x] buffer such as mask_distance's map, s its word), COST_SRC_VALUE (`source` is the S16 volume image, s its
+        value) or COST_SRC_GRADIENT (the same image, s the squared length of its unscaled central differences).  table: 1 .. 65536
+        uint16 entries.  Ordered on the context's stream; does not wait."""
+        own = cost is None
+        if own:
+            shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+            cost = self.buffer(2 * int(np.prod(shape)), np.uint16, shape)
+        status = self.cost_from_field_raw(source, cost, dims, table, lo, shift, kind, domain)
+        if status != OK and own:
+            cost.release()
+        _check(status, "clwh_cost_from_field")
+        return cost
+
+    def cost_geodesic_raw(self, cost: Mem, dims, seeds=None, domain: Mem = None, seed_labels: Mem = None, flags=0, multipliers=None,
+                          cap=DIST_NONE, dist: Mem = None, labels: Mem = None, result=True):
+        """one clwh_cost_geodesic call: (status, GeodesicResult); nothing is raised.  seeds: rows of (x, y, z, id), or None.
+        result=False passes a NULL result."""
+        d, res = CostGeodesicDesc(), GeodesicResult()
+        d.cost, d.domain, d.seed_labels, d.dist, d.labels = (_handle(m) for m in (cost, domain, seed_labels, dist, labels))
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        self._cost_multipliers(d, multipliers)
+        d.cap, d.flags = int(cap), int(flags)
+        if seeds is not None:
+            s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint32).reshape(-1, 4))
+            d.n_seeds = len(s)
+            d.seeds = s.ctypes.data_as(C.POINTER(C.c_uint32))
+        if result:
+            d.result = C.pointer(res)
+        return lib().clwh_cost_geodesic(self.h, C.byref(d)), res
+
+    def cost_geodesic(self, cost: Mem, dims, seeds=None, domain: Mem = None, seed_labels: Mem = None, connectivity=6, multipliers=None,
+                      cap=None, dist: Mem = None, labels: Mem = None, dense=False):
+        """shortest paths through the cost field `cost` (uint16 [z][y][x] on the device, 0 = wall; cost_from_field makes one) from
+        labelled seeds: (dist, labels, GeodesicResult), as mask_geodesic gives them.  A step INTO a voxel costs the direction's
+        multiplier times that voxel's cost.  domain: an optional mask that restricts the paths further.  multipliers: None (all 1),
+        (fx, fy, fz), or (face, edge, corner) from scene.geodesic_weights, each within 1 .. 255.  cap: at most COST_CAP_MAX; large costs
+        over long paths can pass it, and the voxels behind count as unreached: scale the cost.  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        own = [dist is None, labels is None]
+        if own[0]:
+            dist = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        if own[1]:
+            labels = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        flags = (GEO_26 if connectivity == 26 else 0) | (GEO_FROM_LABELS if seed_labels is not None else 0) | (GEO_DENSE if dense else 0)
+        status, res = self.cost_geodesic_raw(cost, dims, seeds, domain, seed_labels, flags, multipliers, DIST_NONE if cap is None else cap,
+                                             dist, labels)
+        if status != OK:
+            for mine, m in zip(own, (dist, labels)):
+                if mine:
+                    m.release()
+        _check(status, "clwh_cost_geodesic")
+        return dist, labels, res
+
+    def cost_trace_raw(self, cost: Mem, dist: Mem, dims, target, labels: Mem = None, flags=0, multipliers=None, points: Mem = None,
+                       capacity=0, result=True):
+        """one clwh_cost_trace call: (status, n_points); nothing is raised.  result=False passes a NULL n_points."""
+        d, n = CostTraceDesc(), C.c_uint64(0)
+        d.cost, d.dist, d.labels, d.points = _handle(cost), _handle(dist), _handle(labels), _handle(points)
+        d.capacity, d.flags = int(capacity), int(flags)
+        for k in range(3):
+            d.dims[k], d.target[k] = int(dims[k]), int(target[k])
+        self._cost_multipliers(d, multipliers)
+        if result:
+            d.n_points = C.pointer(n)
+        return lib().clwh_cost_trace(self.h, C.byref(d)), int(n.value)
+
+    def cost_trace(self, cost: Mem, dist: Mem, dims, target, labels: Mem = None, connectivity=6, multipliers=None, capacity=4096):
+        """the cheapest path behind cost_geodesic's `dist` from `target` = (x, y, z) back to a seed, with the cost field, connectivity
+        and multipliers of that call: (points, n_points) as geodesic_trace gives them.  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        capacity = int(capacity)
+        buf = self.buffer(max(capacity, 1) * 12, np.uint32)
+        try:
+            status, n = self.cost_trace_raw(cost, dist, dims, target, labels, GEO_26 if connectivity == 26 else 0, multipliers, buf, capacity)
+            _check(status, "clwh_cost_trace")
+            k = min(n, capacity)
+            return (buf.pull(np.uint32)[:3 * k].reshape(k, 3).copy() if k else np.zeros((0, 3), np.uint32)), n
+        finally:
+            buf.release()
+
+    def centerline(self, mask: Mem, dims, start, end, spacing=(1, 1, 1), connectivity=26, max_radius=None, sharpness=100, capacity=4096):
+        """the centreline of the structure `mask` (grow's layout, dims = (X, Y, Z)) between the voxels `start` and `end`: (points,
+        n_points), uint32 [n][3] = (x, y, z) from `end` back to `start`; scene.path_length measures it.  Four steps: the depth map d^2
+        of the mask (mask_distance to the nearest clear voxel, weights scene.mask_weights(spacing)); the cost
+        scene.centerline_cost_table over it (the depth shifted right by scene.centerline_shift so that the table has at most 65536
+        entries), low in the middle and high at the wall, 0 outside the mask (cost_from_field);
+        cost_geodesic from `start` with scene.geodesic_weights(spacing, 10) as multipliers; cost_trace from `end`.  max_radius: the
+        largest radius of interest in the unit of `spacing`; deeper voxels all cost 1.  None pulls the depth map and takes its
+        largest value inside the mask on the host: a convenience for small volumes; at full size pass the radius.  A start or end
+        outside the mask gives n_points = 0.  capacity: the first guess of the path's length; a longer path is traced a second time.
+        The call waits for the device."""
+        from . import scene
+
+        multipliers = scene.geodesic_weights(spacing, 10)
+        if max(max(multipliers[0]), max(multipliers[1]), multipliers[2]) > 255:
+            raise ValueError("centerline: a step's multiplier is above 255; use spacing relative to the smallest voxel size")
+        weights = scene.mask_weights(spacing)
+        X, Y, Z = (int(v) for v in dims)
+        depth = self.mask_distance(mask, dims, weights, to_clear=True)
+        cost = dist = None
+        try:
+            if max_radius is None:
+                d = depth.pull().reshape(Z, Y, X)
+                inside = scene.mask_unpack(mask.pull(np.uint32, (mask.nbytes // 4,)), dims) & (d != DIST_NONE)
+                r_sq_max = int(d[inside].max()) if inside.any() else 1
+            else:
+                r_sq_max = scene.radius_sq(max_radius)
+            shift = scene.centerline_shift(r_sq_max)
+            table = scene.centerline_cost_table(max(r_sq_max, 1) >> shift, sharpness)
+            cost = self.cost_from_field(depth, dims, table, 0, shift, COST_SRC_U32, mask)
+            dist, labels, _ = self.cost_geodesic(cost, dims, [tuple(int(v) for v in start) + (1,)], None, None, connectivity, multipliers)
+            labels.release()
+            points, n = self.cost_trace(cost, dist, dims, end, None, connectivity, multipliers, capacity)
+            if n > len(points):  # longer than the first guess: once more with room for all of it
+                points, n = self.cost_trace(cost, dist, dims, end, None, connectivity, multipliers, n)
+            return points, n
+        finally:
+            for m in (dist, cost, depth):
+                if m is not None:
+                    m.release()
 
     def split_mask(self, volume: Mem, mask: Mem, dims, radius_sq, weights=(1, 1, 1), connectivity=6):
         """a mask whose parts touch, split: (labels, number of parts).  Three steps: the mask is eroded by the ball of radius_sq

@@ -841,6 +841,123 @@ typedef struct clwh_geodesic_trace_desc {
 } clwh_geodesic_trace_desc;
 int clwh_geodesic_trace(clwh_ctx *ctx, const clwh_geodesic_trace_desc *desc);
 
+/* ---- geodesic distance maps through a cost field (not in the reference): clwh_mask_geodesic with a step cost that depends on the voxel,
+ * not only on the direction.  A shortest path through a tube hugs the inner wall of every bend; with a cost that is low in the middle
+ * of the structure and high at its wall (clwh_cost_from_field over clwh_mask_distance's depth map) the path is the centreline, the
+ * curve to measure a vessel's length along.  With a cost from the gradient, territories meet on the image's edges; with a cost from
+ * the value and no domain, a path follows a bright vessel that nobody has segmented.  Integers and sets only: defined bit for bit,
+ * independent of how the device schedules anything.
+ * Cost.  `cost`: a plain device buffer, 2-byte aligned, uint16 [Z][Y][X] without padding, at least 2 * X * Y * Z bytes; read only.
+ * Domain.  D = { p : cost(p) >= 1 and (domain == NULL or p's bit in `domain` is set) }: a cost of 0 is a wall.  `domain` is optional
+ * (NULL = the whole volume), in clwh_segment_grow's mask layout, read only; bits at x >= X and the padding words are ignored.
+ * Steps.  Neighbours, directions and the flags CLWH_GEO_26, CLWH_GEO_FROM_LABELS and CLWH_GEO_DENSE are clwh_mask_geodesic's.  The step
+ * from q to its neighbour p costs mult(direction) * cost(p): the direction's multiplier (mult_face[axis], mult_edge[k], mult_corner,
+ * indexed like that call's weights) times the cost of the voxel ENTERED.  Every multiplier in use is an integer in 1 .. 255; edge and
+ * corner multipliers are ignored without CLWH_GEO_26.  A step costs at most 255 * 65535 < 2^24.  The length is not symmetric: a
+ * path pays for every voxel but its first, its reverse for every voxel but its last.
+ * Seeds, result, outputs, limits, scratch: exactly clwh_mask_geodesic's (seeds on the HOST as (x, y, z, id), id >= 1, at most
+ * CLWH_GROW_MAX_SEEDS; a seed outside D contributes nothing; dist(p) = the smallest length of a path from any seed to p, 0 at a seed's
+ * own voxel whatever its cost; label(p) = the smallest id among the seeds that attain it; CLWH_DIST_NONE and 0 outside D and where no
+ * seed reaches within the cap; either output may be NULL, not both; labels may name seed_labels' memory; all X * Y * Z words of an
+ * output are written and nothing behind them; *result as there).  SYNCHRONOUS.
+ * The cap.  cap <= CLWH_COST_CAP_MAX = 0xFF000000 (CLWH_DIST_NONE means that maximum; any other value above it is an error): with
+ * steps below 2^24 no sum of real operands wraps 32 bits, and a voxel whose distance exceeds the cap counts as not reached.  LARGE
+ * COSTS OVER LONG PATHS CAN EXCEED THE CAP: a path of more than 256 steps of 255 * 65535 passes it.  Scaling the cost so that the longest
+ * path of interest stays below 0xFF000000 is the caller's job; result->max_dist and result->reached tell whether it did.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a cost that is NULL, an image or not
+ * 2-byte aligned; a domain that is given and breaks grow's rules for a mask (an image, not 8-byte aligned); dist and labels both NULL,
+ * one of them an image or not 4-byte aligned; CLWH_GEO_FROM_LABELS with a NULL, image or misaligned seed_labels; unknown flag bits;
+ * dims that break the limits; a multiplier in use of 0 or above 255; a cap above 0xFF000000 other than CLWH_DIST_NONE; n_seeds >
+ * CLWH_GROW_MAX_SEEDS, n_seeds > 0 with NULL seeds, n_seeds == 0 without CLWH_GEO_FROM_LABELS; a seed outside the volume or with id 0.
+ * CLWH_ERR_SIZE_MISMATCH: a cost smaller than 2 * X * Y * Z bytes; a domain smaller than its layout; dist, labels or (with the flag)
+ * seed_labels smaller than 4 * X * Y * Z bytes.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written on any
+ * of these.  (CLWH_ERR_INTERNAL_OVERFLOW: the iteration passed its hard cap of X * Y * Z + 2 rounds, which no input can cause: every
+ * step cost is positive, so a shortest path visits no voxel twice and crosses fewer tile faces than it has voxels.) */
+#define CLWH_COST_CAP_MAX 0xFF000000u
+typedef struct clwh_cost_geodesic_desc {
+  clwh_mem *cost;             /* plain device buffer, uint16[Z][Y][X]; read only; 0 = wall */
+  clwh_mem *domain;           /* optional plain device buffer in the mask layout; read only */
+  clwh_mem *seed_labels;      /* CLWH_GEO_FROM_LABELS: plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *dist;             /* optional plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *labels;           /* optional, the same; may name seed_labels' memory */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t mult_face[3];      /* the step along x, y, z: 1 .. 255 */
+  uint32_t mult_edge[3];      /* CLWH_GEO_26: the step that leaves x, y, z unchanged */
+  uint32_t mult_corner;       /* CLWH_GEO_26 */
+  uint32_t cap;               /* CLWH_DIST_NONE = CLWH_COST_CAP_MAX */
+  int32_t flags;              /* clwh_geodesic_flags */
+  uint32_t n_seeds;
+  const uint32_t *seeds;      /* host; uint32[n_seeds][4] = x, y, z, id */
+  clwh_geodesic_result *result;  /* host; required */
+} clwh_cost_geodesic_desc;
+int clwh_cost_geodesic(clwh_ctx *ctx, const clwh_cost_geodesic_desc *desc);
+
+/* ---- the path behind a cost geodesic's distance: clwh_geodesic_trace with the cost field.  `dist` is a map written by
+ * clwh_cost_geodesic, `labels` (optional) the labelling written with it; cost, dims, multipliers and CLWH_GEO_26 as in that call.
+ * Definition.  The path starts at the target.  From p with dist(p) > 0 the next point is p + dir for the first direction that
+ * qualifies, in clwh_geodesic_trace's order ((dz, dy, dx) ascending with dx fastest, non-neighbours skipped): p + dir lies inside the
+ * volume, dist(p + dir) != CLWH_DIST_NONE, dist(p + dir) + mult(dir) * cost(p) == dist(p) -- cost(p) is the cost of the voxel the
+ * forward path entered, the current one -- and, if labels is given, labels(p + dir) == labels(p).  Such a direction always exists for
+ * a map of clwh_cost_geodesic.  The path ends at the first point with dist == 0.
+ * Output, the unreached target (n_points = 0, CLWH_OK) and SYNCHRONOUS as in clwh_geodesic_trace.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or n_points; a NULL cost, a cost that is an image
+ * or not 2-byte aligned; a NULL dist, a dist that is an image or not 4-byte aligned; labels or points that are an image or misaligned,
+ * NULL points with capacity > 0; flag bits other than CLWH_GEO_26; dims that break clwh_mask_geodesic's limits; a multiplier in use
+ * of 0 or above 255; a target outside the volume.  CLWH_ERR_SIZE_MISMATCH: a cost smaller than 2 * X * Y * Z bytes, dist or labels
+ * smaller than 4 * X * Y * Z bytes, points smaller than 12 * capacity bytes.  Nothing is written on any of these.  Maps that are not
+ * clwh_cost_geodesic's, where at a point with dist > 0 the cost is 0 or no direction qualifies, end the path there: the points up to
+ * it and *n_points are written and the call returns CLWH_ERR_INVALID_VALUE.  It never loops: every step strictly lowers dist. */
+typedef struct clwh_cost_trace_desc {
+  clwh_mem *cost;             /* plain device buffer, uint16[Z][Y][X] */
+  clwh_mem *dist;             /* plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *labels;           /* optional, the same */
+  clwh_mem *points;           /* plain device buffer, uint32[capacity][3] */
+  uint64_t capacity;
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t mult_face[3];
+  uint32_t mult_edge[3];
+  uint32_t mult_corner;
+  int32_t flags;              /* CLWH_GEO_26 or 0 */
+  uint32_t target[3];         /* x, y, z */
+  uint64_t *n_points;         /* host; required */
+} clwh_cost_trace_desc;
+int clwh_cost_trace(clwh_ctx *ctx, const clwh_cost_trace_desc *desc);
+
+/* ---- a cost field from a table (not in the reference): the one place a cost is made on the device.
+ *   cost(p) = table[index(p)], or 0 where `domain` is given and p's bit is clear;
+ *   index(p) = clamp((s(p) - lo) >> shift, 0, n - 1), in 64-bit signed arithmetic, the clamp below 0 taken before the shift (s < lo
+ *   gives entry 0 whatever lo is).
+ * `table` is a HOST pointer to uint16[n], 1 <= n <= 65536, copied before the call returns; lo is any int64; shift <= 40.
+ * The sources of s, dims = X, Y, Z:
+ *   CLWH_COST_SRC_U32       `source` is a plain device buffer, 4-byte aligned, uint32 [Z][Y][X] (a distance map, any words); s = the
+ *                           word, CLWH_DIST_NONE included as the number it is, so it clamps to the last entry unless lo says otherwise;
+ *   CLWH_COST_SRC_VALUE     `source` is the volume V (an S16 3-D image with one channel, whose dims must equal `dims`); s = V(p);
+ *   CLWH_COST_SRC_GRADIENT  the same image; s = gx^2 + gy^2 + gz^2 with gx = V(min(x + 1, X - 1), y, z) - V(max(x - 1, 0), y, z) and
+ *                           likewise gy, gz: unscaled central differences, one-sided at the border; up to 3 * 65535^2.
+ * Output.  `cost`: a plain device buffer, 2-byte aligned, uint16 [Z][Y][X]; all X * Y * Z entries are written and nothing behind them.
+ * `domain`: optional, clwh_segment_grow's mask layout, read only.  Limits: those of clwh_labels_to_mask.  Asynchronous and ordered on
+ * the context's stream, like clwh_mask_distance; one kernel, a lane per voxel; the scratch is the table's copy.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or table; an unknown source kind; a source that is
+ * NULL or of the wrong kind for it (for CLWH_COST_SRC_U32 an image or not 4-byte aligned; for the others anything but an S16 3-D
+ * image with one channel); a cost that is NULL, an image or not 2-byte aligned; a domain that is given and breaks grow's rules; flags
+ * other than 0; n outside 1 .. 65536; shift above 40; dims that break the limits or differ from the image's.
+ * CLWH_ERR_SIZE_MISMATCH: a uint32 source smaller than 4 * X * Y * Z bytes, a cost smaller than 2 * X * Y * Z bytes, a domain smaller
+ * than its layout.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written on any of these. */
+enum clwh_cost_source { CLWH_COST_SRC_U32 = 0, CLWH_COST_SRC_VALUE = 1, CLWH_COST_SRC_GRADIENT = 2 };
+typedef struct clwh_cost_field_desc {
+  clwh_mem *source;           /* uint32[Z][Y][X] plain device buffer, or the S16 volume image */
+  clwh_mem *domain;           /* optional plain device buffer in the mask layout; read only */
+  clwh_mem *cost;             /* plain device buffer, uint16[Z][Y][X] */
+  const uint16_t *table;      /* host; uint16[n] */
+  int64_t lo;
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t n;                 /* 1 .. 65536 */
+  uint32_t shift;             /* 0 .. 40 */
+  int32_t kind;               /* clwh_cost_source */
+  int32_t flags;              /* 0 */
+} clwh_cost_field_desc;
+int clwh_cost_from_field(clwh_ctx *ctx, const clwh_cost_field_desc *desc);
+
 /* ---- measuring a region (not in the reference): once a mask has been grown, dilated, closed, intersected or selected from a
  * labelling, "how many voxels is this now, what is its mean density, where is it, how large is its surface" -- on the device, as exact
  * integers.  A region is a set R of voxels of the volume V[z][y][x] (an S16 3-D image with one channel; the dims come from it).  The
