@@ -37,6 +37,34 @@ enum : int { EV_START = 3,              // start distribution ray `o` from the p
              EV_CHECK = 5 };            // the new position has no voxel: left the volume, or one of the rare in-between cases?
 constexpr int kCertNever = 255;         // no step is this long
 
+// What a Hit's colour needs of its rule, staged in LDS once per block: entry k = {rule k writes a colour, that colour}.  The kernel
+// argument segment answers the same question with two loads, one after the other, behind the hit record's.
+__device__ __forceinline__ void stage_rule_colors(uint2 *rule_color, const TfDev &tf) {
+  if (threadIdx.x < (unsigned)CLWH_TF_MAX_RULES) {
+    const bool used = (int)threadIdx.x < tf.n;
+    const TfRuleDev &rule = tf.rules[used ? threadIdx.x : 0u];
+    rule_color[threadIdx.x] = used ? uint2{rule.flags & TF_WRITES_COLOR, rule.color} : uint2{0u, 0u};
+  }
+}
+// hit_gradient_and_color (render_device.hpp) with the rule's colour from that table: LDS reads behind the record's load
+template <int SMALL = 0>
+__device__ __forceinline__ f3 hit_gradient_and_color(const VolumePacked &v, const uint2 *rule_color, f3 pos, bool want_color, uint32_t &color) {
+  const bool regular = hit_record_serves(v, pos);
+  if (regular || want_color) {
+    const uint2 r = v.template hit_record<SMALL>(pos.x, pos.y, pos.z);  // either condition implies pos is inside the volume
+    if (want_color) {
+      const uint2 rule = rule_color[VolumePacked::hit_class(r) - 1u];
+      if (rule.x != 0u) color = rule.y;
+    }
+    if (regular) {
+      int gx, gy, gz;
+      VolumePacked::hit_gradient(r, gx, gy, gz);
+      return f3{(float)gx, (float)gy, (float)gz};
+    }
+  }
+  return gradient_literal(v, pos);
+}
+
 // Image-space accumulation of one launch: a sample adds r | g<<16 | b<<32 | 1<<48 to its HIT's 64-bit
 // delta with ONE atomic (a launch has at most 64 seeds and a contribution is at most 255, so no field can
 // carry); k_commit then folds the deltas into the caller's float4 buffer with plain read-modify-writes.

@@ -73,6 +73,11 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // kernel is VALU-issue bound, and every bounce needs four of them): one LDS read instead
   __shared__ float div255[256];
   if (threadIdx.x < 256u) div255[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  // {writes a colour, the colour} of every rule: a Hit found through its step byte reads its colour here, from LDS behind its hit
+  // record, instead of the rule's flags and then its colour from the argument segment -- two more memory waits, one after the other,
+  // in every opening half with such a Hit (128 bytes: the block still fits seven times into a CU's LDS at 512^3)
+  __shared__ uint2 rule_color[CLWH_TF_MAX_RULES];
+  stage_rule_colors(rule_color, a.tf);
   __syncthreads();
   // the hit count of this camera: a kernel argument, or still only on the device (single-pass launches, clwh_render)
   const uint32_t n_hits = a.n_hits_on_device ? a.counters[CTR_HITS] : a.n_hits;
@@ -434,8 +439,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
 
       if (ev == EV_HIT || ev == EV_HIT_COLOR_PENDING) {
         // ray_marching.cl:63-72: secondary hit -> bounce around the local normal, attenuate; the rule colour (still
-        // pending when the Hit came through the step byte) and the gradient arrive in one 8-byte load
-        bn = -normalize3(hit_gradient_and_color<SMALL>(vol, a.tf, ray.origin, ev == EV_HIT_COLOR_PENDING, color));
+        // pending when the Hit came through the step byte) and the gradient arrive in one 8-byte load; the colour is rule_color's
+        bn = -normalize3(hit_gradient_and_color<SMALL>(vol, rule_color, ray.origin, ev == EV_HIT_COLOR_PENDING, color));
         bstart = ray.origin + ray.direction;
         bseed = o + i - 1;  // (the closing half has counted this march already)
         bounce = true;
