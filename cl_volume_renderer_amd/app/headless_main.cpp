@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,7 +12,7 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
@@ -34,6 +34,15 @@
 // (renderer::centerline).  One JSON line {"centerline": {"from", "to", "points"}} follows the item's other lines, and with an `out`
 // argument the points are written beside it, to <out>.centerline.txt, one "x y z" line each, the seed first.  An end outside the
 // mask gives 0 points.  The three numbers follow the item's name, so the item takes three fields of the list.
+// profile, an item of --grow that needs centerline=: the section profile of the mask along that centreline (renderer::vessel_profile:
+// sections of 64 x 64 samples a quarter of the smallest voxel size apart, the part connected to the curve).  One JSON line
+// {"profile": {"s_mm": [...], "area_mm2": [...], "diameter_mm": [...], "cut": [...]}} with one entry per station, the seed first,
+// follows the centreline's.
+// --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean]: needs --grow=...,centerline=X,Y,Z; the frames show the straightened curved
+// reformat of the volume along that centreline in place of the other views (renderer::render_curved): row y of the frame is the line of
+// WINDOW_MM (default 32) across the curve at station y, the seed first, pixels and stations WINDOW_MM / width apart, turned by DEG
+// about the curve; thin, or the maximum / minimum / mean of a slab of N samples half a pixel apart (window centre 0 and width 4000;
+// default max).  Rows beyond the curve's end stay transparent; a curve longer than `height` stations is cut there.
 // measure, an item of --grow and of --components: a second JSON line with the exact record (renderer::measure_mask: count, sum, sum_sq,
 // min, max, sum_pos, bbox, faces, border_faces) of the mask that is applied, after any morphology and before the volume is changed:
 // {"measure": {...}}; for --components {"measure_components": [...]}, the records (renderer::measure_labels) of the selected ranks,
@@ -85,6 +94,10 @@ int main(int argc_in, char const *argv_in[]) {
   float split_radius = -1.0f;  // the split= item's erosion radius in x-voxels, or -1
   bool centerline = false;     // the centerline= item of --grow
   uint32_t centerline_end[3] = {0, 0, 0};
+  bool profile = false;        // the profile item of --grow
+  bool curved = false;         // --curved
+  float curved_window = 32.0f, curved_angle = 0.0f;
+  int curved_mode = CLWH_SLICE_MAX, curved_slab = 1;
   int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
   bool rewrites = false; // a keep, remove or fill= item
   // whether `v` is the show item; *ok is cleared if its style is unknown
@@ -120,7 +133,8 @@ int main(int argc_in, char const *argv_in[]) {
     return true;
   };
   static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kCurvedUsage = "(--curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean], with --grow=...,centerline=X,Y,Z)";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
@@ -220,6 +234,8 @@ int main(int argc_in, char const *argv_in[]) {
             ok = ok && !number.empty() && *end == '\0' && n >= 0 && n <= 0x7fffffffLL;
             centerline_end[q] = (uint32_t)n;
           }
+        } else if (v == "profile") {
+          profile = true;
         } else if (v == "measure") {
           measure = true;
         } else if (show_item(v, &ok)) {
@@ -235,7 +251,7 @@ int main(int argc_in, char const *argv_in[]) {
           ok = false;
         }
       }
-      if (!ok || field < 5 || grow_lo > grow_hi || (show >= 0 && rewrites)) {
+      if (!ok || field < 5 || grow_lo > grow_hi || (show >= 0 && rewrites) || (profile && !centerline)) {
         std::cout << "Unknown option '" << a << "' " << kGrowUsage << "\n";
         return 1;
       }
@@ -321,6 +337,37 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--slice", 0) == 0) {
       std::cout << "Unknown option '" << a << "' " << kSliceUsage << "\n";
       return 1;
+    } else if (a == "--curved" || a.rfind("--curved=", 0) == 0) {
+      std::string rest = a == "--curved" ? "" : a.substr(9);
+      bool ok = a == "--curved" || !rest.empty();
+      for (int field = 0; ok && !rest.empty(); ++field) {
+        const size_t comma = rest.find(',');
+        const std::string v = rest.substr(0, comma);
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+        if (comma != std::string::npos && rest.empty()) ok = false;  // a trailing comma
+        char *end = nullptr;
+        if (v == "max" || v == "min" || v == "mean") {
+          curved_mode = v == "max" ? CLWH_SLICE_MAX : v == "min" ? CLWH_SLICE_MIN : CLWH_SLICE_MEAN;
+        } else if (v.rfind("slab=", 0) == 0) {
+          const long n = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && n >= 1 && n <= 8192;
+          curved_slab = (int)n;
+        } else if (v.rfind("angle=", 0) == 0) {
+          curved_angle = std::strtof(v.c_str() + 6, &end);
+          ok = ok && v.size() > 6 && *end == '\0' && std::isfinite(curved_angle);
+        } else {
+          curved_window = std::strtof(v.c_str(), &end);
+          ok = ok && field == 0 && !v.empty() && *end == '\0' && std::isfinite(curved_window) && curved_window > 0.0f;
+        }
+      }
+      if (!ok) {
+        std::cout << "Unknown option '" << a << "' " << kCurvedUsage << "\n";
+        return 1;
+      }
+      curved = true;
+    } else if (a.rfind("--curved", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' " << kCurvedUsage << "\n";
+      return 1;
     } else {
       args.push_back(argv_in[i]);
     }
@@ -331,6 +378,14 @@ int main(int argc_in, char const *argv_in[]) {
   }
   if (show >= 0 && projection < 0 && composite < 0 && !isosurface && slice < 0) {
     std::cout << "show needs --projection, --composite, --isosurface or --slice " << (grow ? kGrowUsage : kCompsUsage) << "\n";
+    return 1;
+  }
+  if (curved && (projection >= 0 || composite >= 0 || isosurface || slice >= 0 || mesh)) {
+    std::cout << "--curved excludes --projection, --composite, --isosurface, --slice and --mesh\n";
+    return 1;
+  }
+  if (curved && !(grow && centerline)) {
+    std::cout << "--curved needs --grow with a centerline= item " << kCurvedUsage << "\n";
     return 1;
   }
   if (mesh && (projection >= 0 || composite >= 0 || isosurface || slice >= 0)) {
@@ -352,7 +407,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -407,6 +462,7 @@ int main(int argc_in, char const *argv_in[]) {
     }
   };
 
+  std::vector<uint32_t> curve;  // the centreline from the seed to its end: what --curved unrolls
   if (grow) {  // first: everything below sees the masked volume
     const auto &size = rv.get_volume_size();
     for (int q = 0; q < 3; ++q)
@@ -434,6 +490,12 @@ int main(int argc_in, char const *argv_in[]) {
         for (size_t k = line.size() / 3; k-- > 0;) file << line[3 * k] << ' ' << line[3 * k + 1] << ' ' << line[3 * k + 2] << '\n';
       }
     }
+    for (size_t k = line.size() / 3; k-- > 0;) curve.insert(curve.end(), line.begin() + 3 * k, line.begin() + 3 * k + 3);
+    renderer::profile_summary sections;
+    if (profile && curve.size() >= 6) {
+      const auto &sizes = rv.get_voxel_sizes();
+      sections = r.vessel_profile(none, curve, (double)std::min(sizes[0], std::min(sizes[1], sizes[2])) / 4.0);
+    }
     if (show < 0) r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
@@ -453,6 +515,20 @@ int main(int argc_in, char const *argv_in[]) {
     if (centerline)
       std::printf("{\"centerline\": {\"from\": [%u, %u, %u], \"to\": [%u, %u, %u], \"points\": %llu}}\n", grow_seed[0], grow_seed[1], grow_seed[2],
                   centerline_end[0], centerline_end[1], centerline_end[2], (unsigned long long)(line.size() / 3));
+    if (profile) {
+      const auto list = [](const char *name, const std::vector<double> &v, const char *tail) {
+        std::printf("\"%s\": [", name);
+        for (size_t k = 0; k < v.size(); ++k) std::printf("%s%.6f", k ? ", " : "", v[k]);
+        std::printf("]%s", tail);
+      };
+      std::printf("{\"profile\": {");
+      list("s_mm", sections.s_mm, ", ");
+      list("area_mm2", sections.area_mm2, ", ");
+      list("diameter_mm", sections.diameter_mm, ", ");
+      std::printf("\"cut\": [");
+      for (size_t k = 0; k < sections.cut.size(); ++k) std::printf("%s%s", k ? ", " : "", sections.cut[k] ? "true" : "false");
+      std::printf("]}}\n");
+    }
   }
 
   if (comps) {  // like --grow: everything below sees the masked volume
@@ -547,12 +623,31 @@ int main(int argc_in, char const *argv_in[]) {
   // renderer::render_frame seeds every pass from std::rand() and the application never calls srand
   // (app/renderer.cpp:142).  The ROCm runtime draws from rand() while it initialises, so the sequence is put
   // back to the never-seeded state here to make the frames reproducible (1804289383, 846930886, ...).
+  renderer::curve_frame_set curve_rows;  // --curved: `height` rows, the curve's stations first
+  if (curved) {
+    if (curve.size() < 6) {
+      std::cout << "--curved: the centreline is empty\n";
+      return 1;
+    }
+    const auto &sizes = rv.get_voxel_sizes();
+    const double spacing[3] = {(double)sizes[0], (double)sizes[1], (double)sizes[2]};
+    const double pixel_mm = (double)curved_window / (double)std::max(width, 1);
+    curve_rows = renderer::curve_frames(std::vector<double>(curve.begin(), curve.end()), spacing, width, pixel_mm, pixel_mm, 8,
+                                        (double)curved_angle * 3.141592653589793 / 180.0, curved_slab, pixel_mm / 2.0);
+    const size_t have = curve_rows.rows.size() / 9, want = (size_t)std::max(height, 0);
+    curve_rows.rows.resize(want * 9, 0.0f);
+    for (size_t j = have; j < want; ++j) curve_rows.rows[9 * j] = curve_rows.rows[9 * j + 1] = curve_rows.rows[9 * j + 2] = -1.0f;
+    curve_rows.n = std::min(curve_rows.n, want);
+  }
   std::srand(1);
   const auto t0 = std::chrono::steady_clock::now();
   for (int f = 0; f < frames; ++f) {
     bool changed = false;
     state.cam_changed = true;  // progressive refinement: keep sampling the same view
-    if (slice >= 0)
+    if (curved)
+      frame = static_cast<const unsigned char *>(r.render_curved(state, curve_rows, width, curved_mode, curved_slab,
+                                                                 (float)((double)curved_window / (double)width / 2.0), 0.0f, 4000.0f));
+    else if (slice >= 0)
       frame = static_cast<const unsigned char *>(r.render_slice(state, slice, slice_position, slice_mode, slice_slab, 0.5f, 0.0f, 4000.0f));
     else if (isosurface)
       frame = static_cast<const unsigned char *>(r.render_isosurface(state, iso_value, iso_below ? CLWH_ISO_BELOW : 0));
@@ -584,13 +679,16 @@ int main(int argc_in, char const *argv_in[]) {
   }
   static const char *const kProjectionNames[] = {"max", "min", "mean"};
   static const char *const kSliceNames[] = {"axial", "coronal", "sagittal"};
-  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s%s%s%s%s}\n",
+  std::printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"seconds\": %.6f, \"ms_per_frame\": %.4f, \"frame_fnv1a\": \"%016llx\"%s%s%s%s%s%s%s%s%s%s%s%s}\n",
               frames, width, height, seconds, seconds * 1e3 / frames, (unsigned long long)checksum,
               projection >= 0 ? ", \"projection\": \"" : "", projection >= 0 ? kProjectionNames[projection] : "", projection >= 0 ? "\"" : "",
               composite >= 0 ? ", \"composite\": \"" : "", composite >= 0 ? (composite == 1 ? "shaded" : "plain") : "", composite >= 0 ? "\"" : "",
               isosurface ? (", \"isosurface\": " + std::to_string(iso_value) + ", \"below\": " + (iso_below ? "true" : "false")).c_str() : "",
               slice >= 0 ? (std::string(", \"slice\": \"") + kSliceNames[slice] + "\", \"position\": " + std::to_string(slice_position) +
                             ", \"slab\": " + std::to_string(slice_slab) + ", \"mode\": \"" + kProjectionNames[slice_mode] + "\"").c_str() : "",
+              curved ? (std::string(", \"curved\": {\"window_mm\": ") + std::to_string(curved_window) + ", \"angle\": " + std::to_string(curved_angle) +
+                        ", \"slab\": " + std::to_string(curved_slab) + ", \"mode\": \"" + kProjectionNames[curved_mode] +
+                        "\", \"stations\": " + std::to_string(curve_rows.n) + "}").c_str() : "",
               show >= 0 ? ", \"overlay\": \"" : "", show >= 0 ? kShowNames[show] : "", show >= 0 ? "\"" : "");
   for (tf_selection *s : selection) delete s;
   return 0;

@@ -197,6 +197,41 @@ unsigned long long clvr_host_centerline(clvr_host *h, const unsigned start[3], c
   return points.size() / 3;
 }
 
+// renderer::curve_frames of n_points (x, y, z) triples of doubles: up to `capacity` rows of nine floats into rows_out and as many
+// stations' s_mm as fit `capacity` into s_out (either may be null); *n_out = the stations; returns the rows (n rounded up to 8)
+unsigned long long clvr_host_curve_frames(const double *points, unsigned long long n_points, const double spacing[3], int width, double pixel_mm,
+                                          double station_mm, int smooth_passes, double angle, int slab_samples, double step_mm, float *rows_out,
+                                          double *s_out, unsigned long long capacity, unsigned long long *n_out) {
+  const renderer::curve_frame_set f = renderer::curve_frames(std::vector<double>(points, points + 3 * n_points), spacing, width, pixel_mm,
+                                                             station_mm, smooth_passes, angle, slab_samples, step_mm);
+  const size_t H = f.rows.size() / 9;
+  if (rows_out) std::memcpy(rows_out, f.rows.data(), std::min<size_t>(H, (size_t)capacity) * 9 * sizeof(float));
+  if (s_out) std::memcpy(s_out, f.s_mm.data(), std::min<size_t>(f.n, (size_t)capacity) * sizeof(double));
+  *n_out = f.n;
+  return H;
+}
+// renderer::render_curved along n_points (x, y, z) voxels with curve_frames' rows (the volume's voxel sizes as mm, station_mm =
+// pixel_mm, step_mm = step): the RGBA8 frame (SCREEN_WIDTH x SCREEN_HEIGHT), the reformat in its first `width` columns
+const void *clvr_host_render_curved(clvr_host *h, const unsigned *points, unsigned long long n_points, int width, double pixel_mm, int mode,
+                                    int slab_samples, float step, float center, float window_width, int flags) {
+  const auto &sizes = h->rv->get_voxel_sizes();
+  const double spacing[3] = {(double)sizes[0], (double)sizes[1], (double)sizes[2]};
+  const renderer::curve_frame_set f = renderer::curve_frames(std::vector<double>(points, points + 3 * n_points), spacing, width, pixel_mm, pixel_mm,
+                                                             8, 0.0, slab_samples, (double)step);
+  return h->rend.render_curved(h->state, f, width, mode, slab_samples, step, center, window_width, flags);
+}
+// renderer::vessel_profile of the region mask along n_points (x, y, z) voxels: up to `capacity` records (16 bytes each), areas and
+// diameters; returns the stations
+unsigned long long clvr_host_vessel_profile(clvr_host *h, const unsigned *points, unsigned long long n_points, double pixel_mm, int window,
+                                            int connected, void *records, double *area_mm2, double *diameter_mm, unsigned long long capacity) {
+  const renderer::profile_summary s = h->rend.vessel_profile(h->state, std::vector<uint32_t>(points, points + 3 * n_points), pixel_mm, window, connected != 0);
+  const size_t k = std::min<size_t>(s.records.size(), (size_t)capacity);
+  std::memcpy(records, s.records.data(), k * sizeof(clwh_section_record));
+  std::memcpy(area_mm2, s.area_mm2.data(), k * sizeof(double));
+  std::memcpy(diameter_mm, s.diameter_mm.data(), k * sizeof(double));
+  return s.records.size();
+}
+
 // renderer::split_mask: the region split into parts that become the labelling; out = {radius_sq, wx, wy, wz}; returns the number of parts
 unsigned long long clvr_host_split_mask(clvr_host *h, float radius, int flags, unsigned out[4]) {
   const renderer::split_summary s = h->rend.split_mask(h->state, radius, flags);

@@ -212,6 +212,152 @@ void *renderer::render_slice(struct ui_state &state, int orientation, float posi
   return &frame[0];
 }
 
+// scene.curve_frames, operation for operation (binary64, + - * / and sqrt in the same order; the library is built without contraction)
+namespace {
+struct vec3 {
+  double v[3];
+  double &operator[](int q) { return v[q]; }
+  double operator[](int q) const { return v[q]; }
+};
+inline double dot3(const vec3 &a, const vec3 &b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+inline vec3 unit3(const vec3 &a) {
+  const double n = std::sqrt(dot3(a, a));
+  if (n == 0.0) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  return vec3{{a[0] / n, a[1] / n, a[2] / n}};
+}
+inline vec3 minus3(const vec3 &a, const vec3 &b) { return vec3{{a[0] - b[0], a[1] - b[1], a[2] - b[2]}}; }
+// a - k * b
+inline vec3 less3(const vec3 &a, double k, const vec3 &b) { return vec3{{a[0] - k * b[0], a[1] - k * b[1], a[2] - k * b[2]}}; }
+}  // namespace
+
+renderer::curve_frame_set renderer::curve_frames(const std::vector<double> &points, const double spacing[3], int width, double pixel_mm,
+                                                 double station_mm, int smooth_passes, double angle, int slab_samples, double step_mm) {
+  if (step_mm == 0.0) step_mm = pixel_mm;
+  const size_t m = points.size() / 3;
+  if (m < 2 || !(pixel_mm > 0.0 && station_mm > 0.0 && step_mm > 0.0 && spacing[0] > 0.0 && spacing[1] > 0.0 && spacing[2] > 0.0))
+    clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  std::vector<vec3> q(m);
+  for (size_t i = 0; i < m; ++i) {
+    if (i > 0 && points[3 * i] == points[3 * i - 3] && points[3 * i + 1] == points[3 * i - 2] && points[3 * i + 2] == points[3 * i - 1])
+      clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+    for (int c = 0; c < 3; ++c) q[i][c] = (points[3 * i + c] + 0.5) * spacing[c];
+  }
+  for (int pass = 0; pass < smooth_passes; ++pass) {
+    std::vector<vec3> next(q);
+    for (size_t i = 1; i + 1 < m; ++i)
+      for (int c = 0; c < 3; ++c) next[i][c] = ((q[i - 1][c] + 2.0 * q[i][c]) + q[i + 1][c]) / 4.0;
+    q.swap(next);
+  }
+  std::vector<double> L(m, 0.0);
+  for (size_t i = 0; i + 1 < m; ++i) {
+    const vec3 d = minus3(q[i + 1], q[i]);
+    L[i + 1] = L[i] + std::sqrt(dot3(d, d));
+  }
+  curve_frame_set out;
+  const size_t n = (size_t)std::floor(L[m - 1] / station_mm) + 1;
+  if (n < 2) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  out.n = n;
+  out.s_mm.resize(n);
+  std::vector<vec3> C(n), T(n), U(n);
+  size_t i = 0;  // the last segment (i <= m - 2) whose L_i <= s_j: the stations come in increasing order
+  for (size_t j = 0; j < n; ++j) {
+    const double s = (double)j * station_mm;
+    out.s_mm[j] = s;
+    while (i < m - 2 && L[i + 1] <= s) ++i;
+    const double span = L[i + 1] - L[i];
+    const double f = span > 0.0 ? (s - L[i]) / span : 0.0;
+    for (int c = 0; c < 3; ++c) C[j][c] = q[i][c] + f * (q[i + 1][c] - q[i][c]);
+  }
+  for (size_t j = 0; j < n; ++j) T[j] = unit3(minus3(C[std::min(j + 1, n - 1)], C[j > 0 ? j - 1 : 0]));
+  int axis = 0;
+  for (int c = 1; c < 3; ++c)
+    if (std::fabs(T[0][c]) < std::fabs(T[0][axis])) axis = c;
+  vec3 e{{0.0, 0.0, 0.0}};
+  e[axis] = 1.0;
+  U[0] = unit3(less3(e, dot3(e, T[0]), T[0]));
+  for (size_t j = 0; j + 1 < n; ++j) {
+    const vec3 v1 = minus3(C[j + 1], C[j]);
+    const double c1 = dot3(v1, v1);
+    if (c1 == 0.0) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+    const vec3 rL = less3(U[j], (2.0 / c1) * dot3(v1, U[j]), v1);
+    const vec3 tL = less3(T[j], (2.0 / c1) * dot3(v1, T[j]), v1);
+    const vec3 v2 = minus3(T[j + 1], tL);
+    const double c2 = dot3(v2, v2);
+    const vec3 r = c2 == 0.0 ? rL : less3(rL, (2.0 / c2) * dot3(v2, rL), v2);
+    U[j + 1] = unit3(less3(r, dot3(r, T[j + 1]), T[j + 1]));
+  }
+  const double co = std::cos(angle), si = std::sin(angle);
+  const double hw = (double)(width - 1) / 2.0, hk = ((double)(slab_samples - 1) / 2.0) * step_mm;
+  const size_t H = (n + 7) / 8 * 8;
+  out.rows.assign(H * 9, 0.0f);
+  for (size_t j = n; j < H; ++j) out.rows[9 * j] = out.rows[9 * j + 1] = out.rows[9 * j + 2] = -1.0f;  // padding: no kept sample
+  for (size_t j = 0; j < n; ++j) {
+    const vec3 &t = T[j], &u = U[j];
+    const vec3 w{{t[1] * u[2] - t[2] * u[1], t[2] * u[0] - t[0] * u[2], t[0] * u[1] - t[1] * u[0]}};
+    for (int c = 0; c < 3; ++c) {
+      const double a = co * u[c] + si * w[c], nn = (-si) * u[c] + co * w[c];
+      const double du = (a * pixel_mm) / spacing[c], normal = nn / spacing[c];
+      out.rows[9 * j + c] = (float)((C[j][c] / spacing[c] - hw * du) - hk * normal);
+      out.rows[9 * j + 3 + c] = (float)du;
+      out.rows[9 * j + 6 + c] = (float)normal;
+    }
+  }
+  return out;
+}
+
+void *renderer::render_curved(struct ui_state &, const curve_frame_set &frames, int width, int mode, int slab_samples, float step, float center,
+                              float window_width, int flags) {
+  const size_t H = frames.rows.size() / 9;
+  if (H < 1 || H > (size_t)SCREEN_HEIGHT || width < 1 || width > SCREEN_WIDTH) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  clwh_curved_desc d{};
+  d.frame = frame.get_device_reference();
+  d.volume = volume->get_reference_volume().get_device_reference();
+  d.rows = frames.rows.data();
+  d.width = (uint32_t)width;
+  d.height = (uint32_t)H;
+  d.mode = mode;
+  d.flags = flags;
+  d.slab_samples = slab_samples;
+  d.step = step;
+  d.window_center = center;
+  d.window_width = window_width;
+  clw_fail_hard_on_error(clwh_render_curved(ctx.get_handle(), &d));
+  frame.pull();
+  return &frame[0];
+}
+
+renderer::profile_summary renderer::vessel_profile(struct ui_state &, const std::vector<uint32_t> &points, double pixel_mm, int window, bool connected) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  const auto &sizes = volume->get_voxel_sizes();
+  const double spacing[3] = {(double)sizes[0], (double)sizes[1], (double)sizes[2]};
+  const curve_frame_set frames = curve_frames(std::vector<double>(points.begin(), points.end()), spacing, window, pixel_mm, pixel_mm, 8, 0.0, window, pixel_mm);
+  profile_summary out;
+  out.s_mm = frames.s_mm;
+  clw_vector<uint32_t> table(ctx, std::vector<uint32_t>(frames.n * 4), false);
+  clwh_curve_profile_desc d{};
+  d.mask = region_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.rows = frames.rows.data();
+  d.n_rows = (uint32_t)frames.n;
+  d.width = (uint32_t)window;
+  d.slab_samples = window;
+  d.step = (float)pixel_mm;
+  d.flags = connected ? CLWH_PROFILE_CONNECTED : 0;
+  d.records = table.get_device_reference();
+  clw_fail_hard_on_error(clwh_curve_profile(ctx.get_handle(), &d));
+  table.pull();  // (waits for the stream)
+  out.records.resize(frames.n);
+  std::memcpy(out.records.data(), &table[0], frames.n * sizeof(clwh_section_record));
+  for (const clwh_section_record &r : out.records) {  // scene.profile_measures
+    const double area = (double)r.count * pixel_mm * pixel_mm;
+    out.area_mm2.push_back(area);
+    out.diameter_mm.push_back(2.0 * std::sqrt(area / 3.141592653589793));
+    out.cut.push_back(r.border > 0 ? 1 : 0);
+  }
+  return out;
+}
+
 const std::vector<uint32_t> &renderer::overlay_colours() {
   static const uint8_t rgb[20][3] = {{230, 25, 75},   {60, 180, 75},   {255, 225, 25}, {0, 130, 200},   {245, 130, 48},
                                      {145, 30, 180},  {70, 240, 240},  {240, 50, 230}, {210, 245, 60},  {255, 140, 170},

@@ -83,6 +83,30 @@ class renderer : public frame_emitter {
   static void slice_plane(const size_t dims[3], int orientation, float position, int width, int height, int slab_samples, float step,
                           float origin[3], float du[3], float dv[3], float normal[3]);
 
+  // not in the reference: the straightened curved reformat along a path and the vessel's section profile (clwh_render_curved /
+  // clwh_curve_profile).  curve_frames: scene.curve_frames restated operation for operation -- the ONE place where a path (x, y, z
+  // triples in voxels, in the order given) becomes the float rows both calls read; bit-identical to the Python one.  step_mm 0 means
+  // pixel_mm.  render_curved: the reformat of `frames` into the region width x (rows of `frames`) of the frame image, row y the line
+  // across the curve at station y; mode, slab, step, window and flags as render_slice.  Pulls the frame and returns its host copy.
+  // vessel_profile: the stenosis curve of the region mask along `points` (as centerline returns them), with the volume's voxel sizes
+  // as millimetres: sections of window x window samples pixel_mm apart perpendicular to the curve, one clwh_curve_profile call, and
+  // scene.profile_measures' area and equivalent diameter per station.  Waits for the device.
+  struct curve_frame_set {
+    std::vector<float> rows;    // [H][9]: origin, du, normal; H = n rounded up to a multiple of 8, the padding rows transparent
+    std::vector<double> s_mm;   // [n]: the stations' arc length
+    size_t n = 0;
+  };
+  static curve_frame_set curve_frames(const std::vector<double> &points, const double spacing[3], int width, double pixel_mm, double station_mm,
+                                      int smooth_passes = 8, double angle = 0.0, int slab_samples = 1, double step_mm = 0.0);
+  void *render_curved(struct ui_state &state, const curve_frame_set &frames, int width, int mode = 0, int slab_samples = 1, float step = 0.5f,
+                      float center = 0.0f, float window_width = 4000.0f, int flags = 0);
+  struct profile_summary {
+    std::vector<clwh_section_record> records;
+    std::vector<double> s_mm, area_mm2, diameter_mm;
+    std::vector<uint8_t> cut;   // border > 0: the window cut the section
+  };
+  profile_summary vessel_profile(struct ui_state &state, const std::vector<uint32_t> &points, double pixel_mm, int window = 64, bool connected = true);
+
   // not in the reference: the isosurface of the volume's grid at value `iso` as a triangle mesh (marching tetrahedra on the voxel
   // centres; flags: CLWH_MESH_DENSE | CLWH_MESH_BELOW): one counting call, buffers of that size, the filling call, the readback.
   // Unlike the views it waits for the device; no camera takes part (`state` is not read).

@@ -1,6 +1,6 @@
 // clwh_host.hpp -- host-only side of libclwhip.so: the opaque handles of include/clwh.h, the owners of their device
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
-// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices and overlays; clwh_mesh.hip: the
+// functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices, curved reformats, section profiles and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
 // clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
@@ -268,6 +268,18 @@ struct CostScratch {
   ~CostScratch() { if (host) (void)hipHostFree(host); }
 };
 
+// clwh_render_curved's and clwh_curve_profile's scratch: the curve's rows on the device and the page-locked copy they travel from, under
+// clwh_cost_from_field's discipline: `copied` is recorded behind the copy, and the next call waits for it -- not for the stream --
+// before it overwrites the page-locked copy; the device buffer is rewritten in stream order.
+struct CurveScratch {
+  DeviceBuffer rows;
+  float *host = nullptr;
+  size_t host_bytes = 0;
+  Event copied;
+  bool in_flight = false;
+  ~CurveScratch() { if (host) (void)hipHostFree(host); }
+};
+
 // clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
 // Every call rewrites what it reads: only the allocation is kept.
 struct RegionStatsScratch {
@@ -336,6 +348,7 @@ struct clwh_ctx {
   clvr::DistanceScratch distance;
   clvr::GeodesicScratch geodesic;
   clvr::CostScratch cost;
+  clvr::CurveScratch curve;
   clvr::RegionStatsScratch region_stats;
   clvr::OverlayScratch overlay;
   clvr::ProjectionData proj;

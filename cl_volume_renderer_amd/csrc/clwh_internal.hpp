@@ -522,6 +522,32 @@ struct SliceArgs {
 };
 hipError_t launch_slice(const SliceArgs &a, int mode, bool dense, hipStream_t s);
 
+// ---- the curved reformat and the section profile along a curve (curved_kernels.hip).  `rows`: nine floats per station -- origin[3],
+// du[3], normal[3] in voxel space -- in the context's buffer (CurveScratch), launch_h rows for the view and n_rows for the profile.
+// The view is the slice with a frame per image row; its dilated tables stay nullptr when the launch cannot skip.
+struct CurvedArgs {
+  ViewVolume vol;
+  ViewFrame fr;
+  int32_t use_coarse;      // as SliceArgs
+  const float *rows;
+  float step;
+  float window_center, window_width;
+  int32_t slab_samples;    // 1 .. 8192: the sample indices' cap
+  float *values;           // optional, row-major launch_w x launch_h
+  float *t_extreme;        // optional, same
+};
+hipError_t launch_curved(const CurvedArgs &a, int mode, bool dense, hipStream_t s);
+struct CurveProfileArgs {
+  const unsigned long long *mask;  // grow's layout: W64 64-bit words per row of X voxels
+  int32_t X, Y, Z, W64;
+  const float *rows;
+  uint32_t n_rows;         // the grid: one wave per station
+  int32_t width, slab_samples;  // 1 .. 64 each: lanes and bits of a lane's word
+  float step;
+  uint32_t *records;       // n_rows x {count, sum_x, sum_k, border}, 16-byte aligned
+};
+hipError_t launch_curve_profile(const CurveProfileArgs &a, bool connected, hipStream_t s);
+
 // ---- the isosurface as an indexed triangle mesh (mesh_kernels.hip): marching tetrahedra, one block per 8^3 brick; without
 // CLWH_MESH_DENSE the dilated table says which bricks the surface can touch
 struct MeshArgs {

@@ -2,6 +2,8 @@
 // (compositing through a colour/opacity table), clwh_render_isosurface (the isosurface of the trilinear field) and clwh_render_slice
 // (its oblique slices and slabs).  All read the same bricked copy of the volume (ensure_projection_data), as does the mesher
 // (clwh_mesh.hip).  The kernels are in projection_kernels.hip, composite_kernels.hip, isosurface_kernels.hip and slice_kernels.hip.
+// Next to the slice clwh_render_curved, the slice with a frame per image row, and clwh_curve_profile, which measures a mask's
+// cross-sections along the same rows (curved_kernels.hip).
 // Behind them clwh_overlay_slice and clwh_overlay_camera, which draw a mask or a labelling over a frame one of them has written, with
 // the slice's or the projection's rays (overlay_kernels.hip); they read no volume.
 #include <algorithm>
@@ -271,6 +273,109 @@ extern "C" int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *d) {
   a.values = optional_output<float>(d->values);
   a.t_extreme = optional_output<float>(d->t_extreme);
   HIP_TRY(launch_slice(a, d->mode, dense, ctx->stream));
+  return CLWH_OK;
+}
+
+// ---- the curved reformat and the section profile along a curve (curved_kernels.hip)
+static_assert(sizeof(clwh_curved_desc) == 72 && sizeof(clwh_curve_profile_desc) == 64 && sizeof(clwh_section_record) == 16,
+              "the curve descriptors' layout (ffi.py states it again)");
+
+// (value) n rows of origin[3], du[3], normal[3]: every component finite, and on every axis how far any sample of a row of `width`
+// pixels and `slab_samples` samples can lie from 0 stays below 2^30 (the slice's reach without a dv)
+static bool curve_rows_ok(const float *rows, size_t n, uint32_t width, int32_t slab_samples, float step) {
+  const double across = width ? (double)width - 1.0 : 0.0, along = (double)(slab_samples - 1) * (double)step;
+  for (size_t y = 0; y < n; ++y) {
+    const float *r = rows + y * 9u;
+    for (int q = 0; q < 3; ++q) {
+      if (!(std::isfinite(r[q]) && std::isfinite(r[3 + q]) && std::isfinite(r[6 + q]))) return false;
+      const double reach = std::fabs((double)r[q]) + across * std::fabs((double)r[3 + q]) + along * std::fabs((double)r[6 + q]);
+      if (!(reach < 1073741824.0)) return false;
+    }
+  }
+  return true;
+}
+// the rows into the context's device buffer through its page-locked copy; nobody waits for the stream (CurveScratch)
+static int stage_curve_rows(clwh_ctx *ctx, const float *rows, size_t n, const float **device_rows) {
+  CurveScratch &s = ctx->curve;
+  const size_t bytes = n * 9u * sizeof(float);
+  CLWH_TRY(s.rows.reserve(ctx->stream, bytes));
+  CLWH_TRY(s.copied.ensure(hipEventDisableTiming));
+  if (s.in_flight) HIP_TRY(hipEventSynchronize(s.copied.ev));  // the previous call's copy has left the page-locked rows
+  s.in_flight = false;
+  if (s.host_bytes < bytes) {
+    if (s.host) HIP_TRY(hipHostFree(s.host));
+    s.host = nullptr;
+    s.host_bytes = 0;
+    HIP_TRY(hipHostMalloc((void **)&s.host, bytes, hipHostMallocDefault));
+    s.host_bytes = bytes;
+  }
+  std::memcpy(s.host, rows, bytes);
+  HIP_TRY(hipMemcpyAsync(s.rows.ptr, s.host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipEventRecord(s.copied.ev, ctx->stream));
+  s.in_flight = true;
+  *device_rows = s.rows.as<float>();
+  return CLWH_OK;
+}
+
+extern "C" int clwh_render_curved(clwh_ctx *ctx, const clwh_curved_desc *d) {
+  if (!ctx || !d || !view_images_ok(d->frame, d->volume) || !d->rows) return CLWH_ERR_INVALID_VALUE;
+  if (d->mode != CLWH_SLICE_MAX && d->mode != CLWH_SLICE_MIN && d->mode != CLWH_SLICE_MEAN) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_CURVED_DENSE) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->slab_samples < 1 || d->slab_samples > 8192) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->window_center) && std::isfinite(d->window_width) && d->window_width > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  if (!curve_rows_ok(d->rows, d->height, d->width, d->slab_samples, d->step)) return CLWH_ERR_INVALID_VALUE;
+  if (!view_region_ok(d->frame, d->width, d->height)) return CLWH_ERR_BAD_NDRANGE;
+  const size_t out_bytes = (size_t)d->width * d->height * sizeof(float);
+  if (!holds(d->values, out_bytes) || !holds(d->t_extreme, out_bytes)) return CLWH_ERR_SIZE_MISMATCH;
+
+  CurvedArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(ensure_projection_data(ctx, d->volume, a.vol));
+  const bool dense = (d->flags & CLWH_CURVED_DENSE) != 0 || d->mode == CLWH_SLICE_MEAN;  // MEAN reads every kept sample
+  if (!dense) CLWH_TRY(ensure_dilated_table(ctx, a.vol));
+  CLWH_TRY(stage_curve_rows(ctx, d->rows, d->height, &a.rows));
+  a.use_coarse = ctx->tune.slice_coarse;
+  a.fr = view_frame(d->frame, d->width, d->height);
+  a.step = d->step;
+  a.window_center = d->window_center;
+  a.window_width = d->window_width;
+  a.slab_samples = d->slab_samples;
+  a.values = optional_output<float>(d->values);
+  a.t_extreme = optional_output<float>(d->t_extreme);
+  HIP_TRY(launch_curved(a, d->mode, dense, ctx->stream));
+  return CLWH_OK;
+}
+
+extern "C" int clwh_curve_profile(clwh_ctx *ctx, const clwh_curve_profile_desc *d) {
+  if (!ctx || !d || !mask_ok(d->mask) || !d->rows) return CLWH_ERR_INVALID_VALUE;
+  if (!is_plain_buffer(d->records) || ((uintptr_t)d->records->dptr & 15u) != 0u) return CLWH_ERR_INVALID_VALUE;
+  if ((d->flags & ~CLWH_PROFILE_CONNECTED) != 0) return CLWH_ERR_INVALID_VALUE;
+  if (d->n_rows < 1u || d->n_rows > 65535u || d->width < 1u || d->width > 64u) return CLWH_ERR_INVALID_VALUE;
+  if (d->slab_samples < 1 || d->slab_samples > 64) return CLWH_ERR_INVALID_VALUE;
+  if (!(std::isfinite(d->step) && d->step > 0.0f)) return CLWH_ERR_INVALID_VALUE;
+  const uint64_t X = d->dims[0], Y = d->dims[1], Z = d->dims[2];
+  if (!voxels_fit_31_bits(X, Y, Z)) return CLWH_ERR_INVALID_VALUE;
+  if (!curve_rows_ok(d->rows, d->n_rows, d->width, d->slab_samples, d->step)) return CLWH_ERR_INVALID_VALUE;
+  if (!mask_fits(X, Y, Z, d->mask)) return CLWH_ERR_SIZE_MISMATCH;
+  if (d->records->bytes / sizeof(clwh_section_record) < (size_t)d->n_rows) return CLWH_ERR_SIZE_MISMATCH;
+
+  CurveProfileArgs a;
+  std::memset(&a, 0, sizeof a);
+  HIP_TRY(hipSetDevice(ctx->device));
+  CLWH_TRY(stage_curve_rows(ctx, d->rows, d->n_rows, &a.rows));
+  a.mask = (const unsigned long long *)d->mask->dptr;
+  a.X = (int32_t)X;
+  a.Y = (int32_t)Y;
+  a.Z = (int32_t)Z;
+  a.W64 = (int32_t)mask_w64(X);
+  a.n_rows = d->n_rows;
+  a.width = (int32_t)d->width;
+  a.slab_samples = d->slab_samples;
+  a.step = d->step;
+  a.records = (uint32_t *)d->records->dptr;
+  HIP_TRY(launch_curve_profile(a, (d->flags & CLWH_PROFILE_CONNECTED) != 0, ctx->stream));
   return CLWH_OK;
 }
 

@@ -24,6 +24,8 @@ COMP_DENSE, COMP_SHADE = 1, 2
 ISO_DENSE, ISO_BELOW = 1, 2
 SLICE_MAX, SLICE_MIN, SLICE_MEAN = 0, 1, 2
 SLICE_DENSE = 1
+CURVED_DENSE = 1
+PROFILE_CONNECTED = 1
 MESH_DENSE, MESH_BELOW = 1, 2
 GROW_26, GROW_FROM_MASK, GROW_DENSE = 1, 2, 4
 GROW_MAX_SEEDS = 65536
@@ -149,6 +151,39 @@ class SliceDesc(C.Structure):
         ("slab_samples", C.c_int32), ("step", C.c_float),
         ("window_center", C.c_float), ("window_width", C.c_float),
         ("values", C.c_void_p), ("t_extreme", C.c_void_p),
+    ]
+
+
+class CurvedDesc(C.Structure):
+    _fields_ = [
+        ("frame", C.c_void_p), ("volume", C.c_void_p),
+        ("rows", C.c_void_p),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("mode", C.c_int32), ("flags", C.c_int32),
+        ("slab_samples", C.c_int32), ("step", C.c_float),
+        ("window_center", C.c_float), ("window_width", C.c_float),
+        ("values", C.c_void_p), ("t_extreme", C.c_void_p),
+    ]
+
+
+class SectionRecord(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("sum_x", C.c_uint32), ("sum_k", C.c_uint32), ("border", C.c_uint32)]
+
+
+# the same record as a numpy dtype (scene.SECTION_RECORD_DTYPE): what Context.curve_profile returns
+SECTION_RECORD_DTYPE = np.dtype([("count", np.uint32), ("sum_x", np.uint32), ("sum_k", np.uint32), ("border", np.uint32)])
+assert SECTION_RECORD_DTYPE.itemsize == C.sizeof(SectionRecord) == 16
+
+
+class CurveProfileDesc(C.Structure):
+    _fields_ = [
+        ("mask", C.c_void_p),
+        ("dims", C.c_uint32 * 3),
+        ("rows", C.c_void_p),
+        ("n_rows", C.c_uint32), ("width", C.c_uint32),
+        ("slab_samples", C.c_int32), ("step", C.c_float),
+        ("flags", C.c_int32),
+        ("records", C.c_void_p),
     ]
 
 
@@ -409,6 +444,8 @@ _PROTOTYPES = [
     ("clwh_render_composite", C.c_int, [C.c_void_p, C.POINTER(CompositeDesc)]),
     ("clwh_render_isosurface", C.c_int, [C.c_void_p, C.POINTER(IsosurfaceDesc)]),
     ("clwh_render_slice", C.c_int, [C.c_void_p, C.POINTER(SliceDesc)]),
+    ("clwh_render_curved", C.c_int, [C.c_void_p, C.POINTER(CurvedDesc)]),
+    ("clwh_curve_profile", C.c_int, [C.c_void_p, C.POINTER(CurveProfileDesc)]),
     ("clwh_mesh_isosurface", C.c_int, [C.c_void_p, C.POINTER(MeshDesc)]),
     ("clwh_segment_grow", C.c_int, [C.c_void_p, C.POINTER(GrowDesc)]),
     ("clwh_volume_apply_mask", C.c_int, [C.c_void_p, C.POINTER(ApplyMaskDesc)]),
@@ -804,6 +841,78 @@ class Context:
         d.values = _handle(values)
         d.t_extreme = _handle(t_extreme)
         _check(lib().clwh_render_slice(self.h, C.byref(d)), "clwh_render_slice")
+
+    def render_curved_raw(self, frame: Mem, volume: Mem, rows, width, height, mode=SLICE_MAX, slab_samples=1, step=0.5,
+                          window=(0.0, 1.0), flags=0, values: Mem = None, t_extreme: Mem = None):
+        """one clwh_render_curved call: its status; nothing is raised.  rows: float32 [height][9] on the host (origin, du, normal per
+        image row), or None for a NULL pointer.  The library copies the rows before it returns."""
+        d = CurvedDesc()
+        d.frame, d.volume = _handle(frame), _handle(volume)
+        r = None if rows is None else np.ascontiguousarray(rows, np.float32)
+        d.rows = None if r is None else r.ctypes.data
+        d.width, d.height = int(width), int(height)
+        d.mode, d.flags = int(mode), int(flags)
+        d.slab_samples, d.step = int(slab_samples), float(step)
+        d.window_center, d.window_width = float(window[0]), float(window[1])
+        d.values = _handle(values)
+        d.t_extreme = _handle(t_extreme)
+        return lib().clwh_render_curved(self.h, C.byref(d))
+
+    def render_curved(self, frame: Mem, volume: Mem, rows, width, height, mode=SLICE_MAX, slab_samples=1, step=0.5,
+                      window=(0.0, 1.0), flags=0, values: Mem = None, t_extreme: Mem = None):
+        """the straightened curved reformat of `volume` (S16) into `frame` (RGBA8): image row y is the line origin_y + x * du_y of
+        rows[y] (scene.curve_frames makes the rows of a centreline), thin or the maximum / minimum / mean over `slab_samples` samples
+        `step` apart along normal_y.  Everything else as render_slice.  flags: CURVED_DENSE."""
+        if rows is None or np.shape(rows) != (int(height), 9):
+            raise ValueError("render_curved: rows must be float32 [height][9]")
+        _check(self.render_curved_raw(frame, volume, rows, width, height, mode, slab_samples, step, window, flags, values, t_extreme),
+               "clwh_render_curved")
+
+    def curve_profile_raw(self, mask: Mem, dims, rows, n_rows, width, slab_samples, step, flags=0, records: Mem = None):
+        """one clwh_curve_profile call: its status; nothing is raised.  rows: float32 [n_rows][9] on the host, or None for NULL."""
+        d = CurveProfileDesc()
+        d.mask, d.records = _handle(mask), _handle(records)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        r = None if rows is None else np.ascontiguousarray(rows, np.float32)
+        d.rows = None if r is None else r.ctypes.data
+        d.n_rows, d.width = int(n_rows), int(width)
+        d.slab_samples, d.step, d.flags = int(slab_samples), float(step), int(flags)
+        return lib().clwh_curve_profile(self.h, C.byref(d))
+
+    def curve_profile(self, mask: Mem, dims, rows, width, slab_samples, step, connected=True) -> np.ndarray:
+        """the section records of `mask` (grow's layout, dims = (X, Y, Z)) at the stations `rows` (float32 [n][9]): a structured array
+        (SECTION_RECORD_DTYPE: count, sum_x, sum_k, border) of n records over a grid of width x slab_samples samples per station;
+        connected: only the part of a section that is 4-connected to the grid's centre.  scene.profile_measures turns the records
+        into areas and diameters.  The call waits for the device."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != 9 or rows.shape[0] < 1:
+            raise ValueError("curve_profile: rows must be float32 [n][9], n >= 1")
+        n = rows.shape[0]
+        records = self.buffer(16 * n, SECTION_RECORD_DTYPE, (n,))
+        try:
+            _check(self.curve_profile_raw(mask, dims, rows, n, width, slab_samples, step, PROFILE_CONNECTED if connected else 0, records),
+                   "clwh_curve_profile")
+            return records.pull()
+        finally:
+            records.release()
+
+    def vessel_profile(self, mask: Mem, dims, points, spacing, pixel_mm, window=64, connected=True, station_mm=None, smooth_passes=8,
+                       angle=0.0):
+        """the stenosis curve of the vessel `mask` along the path `points` (voxels, as Context.centerline returns them): a dictionary
+        with s_mm (the stations' arc length) and, per station, area_mm2, diameter_mm, offset_mm (the section's centroid from the
+        curve, across and along the section window) and cut (the window cut the section), beside the raw records.  The sections lie
+        in the planes perpendicular to the curve: scene.curve_frames with slab_samples = width = window and step_mm = pixel_mm, one
+        clwh_curve_profile call, scene.profile_measures.  station_mm defaults to pixel_mm.  The call waits for the device."""
+        from . import scene
+
+        station_mm = pixel_mm if station_mm is None else station_mm
+        rows, s_mm, n = scene.curve_frames(points, spacing, window, pixel_mm=pixel_mm, station_mm=station_mm, smooth_passes=smooth_passes,
+                                           angle=angle, slab_samples=window, step_mm=pixel_mm)
+        records = self.curve_profile(mask, dims, rows[:n], window, window, pixel_mm, connected)
+        out = scene.profile_measures(records, pixel_mm, pixel_mm, window, window)
+        out["s_mm"], out["records"] = s_mm, records
+        return out
 
     def overlay_slice_raw(self, frame: Mem, source: Mem, kind, dims, palette: Mem, origin, du, dv, normal, width, height, slab_samples=1,
                           step=0.5, flags=OVERLAY_FILL | OVERLAY_OUTLINE, fill_alpha=96, outline_alpha=255, id_range=(1, 0xFFFFFFFF),

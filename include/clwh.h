@@ -439,6 +439,73 @@ typedef struct clwh_slice_desc {
 } clwh_slice_desc;
 int clwh_render_slice(clwh_ctx *ctx, const clwh_slice_desc *desc);
 
+/* ---- the straightened curved planar reformat (CPR): the slice with a frame of its own per image row (not in the reference).  Image
+ * row y is a line across a vessel at station y of a curve: `rows` holds, per row of the launched region, nine floats origin[3], du[3],
+ * normal[3] in voxel space (scene.curve_frames / renderer::curve_frames make them from a centreline).
+ * Rays.  For pixel (x, y) of the launched region, in float32 without contraction, per component c:
+ *   o.c = origin_y.c + (float)x * du_y.c
+ * (one multiply, then one add).  Sample k, 0 <= k < slab_samples, sits at p_k = o + normal_y * ((float)k * step).
+ * From there on the text of clwh_render_slice applies word for word: the kept rule, S(p) and the three modes (CLWH_SLICE_MAX / MIN /
+ * MEAN), the one rounding to float32, t_extreme, every NaN stored as 0x7FC00000, the pixel (0, 0, 0, 0) where no sample is kept, the
+ * window, the pixels of the frame outside the region left untouched, and the skip rule with the dilated brick table and the table of
+ * the cells of 4^3 bricks -- its proof is per ray and nowhere uses that the rays are parallel.  So
+ *   pixel (x, y) of the curved view == pixel (x, 0) of clwh_render_slice with origin = origin_y, du = du_y, normal = normal_y,
+ * byte for byte, in the frame, in values and in t_extreme (dv does not matter in a slice's row 0: (float)0 * dv adds +-0).
+ * A row with origin outside the volume and du = normal = 0 keeps no sample: a transparent row (the padding rows of curve_frames).
+ * Errors, in the slice's order of kinds.  CLWH_ERR_INVALID_VALUE: the slice's cases (ctx, desc, frame, volume, mode, flags,
+ * slab_samples, step, window, volume dims); rows == NULL; a component of a row that is not finite; on any axis c of any row,
+ * |origin.c| + (width - 1) * |du.c| + (slab_samples - 1) * step * |normal.c| >= 2^30, evaluated in double.  `rows` is read for `height`
+ * rows before the region is checked, so it holds that many whenever it is not NULL.  CLWH_ERR_BAD_NDRANGE and CLWH_ERR_SIZE_MISMATCH
+ * as in the slice.  Nothing is written on an error.
+ * Asynchronous and ordered on the context's stream; no host wait.  The rows are validated on the host and copied through a page-locked
+ * buffer of the context into a device buffer of the context, so the caller's array need not outlive the call; the next call that
+ * stages rows (this one or clwh_curve_profile) waits for that copy's event only, and the device buffer is reused in stream order.
+ * Derived data: the projections' bricked copy and the slice's dilated tables, built and invalidated exactly as for the slice. */
+enum clwh_curved_flags { CLWH_CURVED_DENSE = 1 };  /* no brick skipping: same result by contract */
+typedef struct clwh_curved_desc {
+  clwh_mem *frame;            /* RGBA8 2-D image */
+  clwh_mem *volume;           /* S16 3-D image, 1 channel */
+  const float *rows;          /* HOST, float32[height][9]: per image row origin[3], du[3], normal[3], voxel space */
+  uint32_t width, height;     /* launched region, the slice's rules */
+  int32_t mode, flags;        /* CLWH_SLICE_MAX / MIN / MEAN; CLWH_CURVED_DENSE */
+  int32_t slab_samples;       /* 1 .. 8192 */
+  float step;                 /* > 0, finite */
+  float window_center, window_width;
+  clwh_mem *values, *t_extreme;   /* optional float32[height][width] */
+} clwh_curved_desc;
+int clwh_render_curved(clwh_ctx *ctx, const clwh_curved_desc *desc);
+
+/* ---- the section profile of a mask along a curve: per station the cross-section of the mask in the plane the station's row spans,
+ * as an exact integer record (not in the reference).  Integers and sets only.
+ * Station y, 0 <= y < n_rows, has a grid of width x slab_samples samples p(x, k) = (origin_y + (float)x * du_y) + normal_y * ((float)k *
+ * step), positioned as in clwh_render_curved.  A sample is SET iff it is kept (the slice's rule against `dims`) and bit ((int)p.x,
+ * (int)p.y, (int)p.z) of the mask is set; the mask is in clwh_segment_grow's layout, and its padding bits are never read, whatever
+ * they hold.  Without CLWH_PROFILE_CONNECTED the section is all set samples.  With it the section is the union of the 4-connected
+ * components of set samples -- neighbours are (x +- 1, k) and (x, k +- 1) -- that contain a CENTRE sample: one of the up to four samples
+ * {(width - 1) / 2, width / 2} x {(slab_samples - 1) / 2, slab_samples / 2} (integer division) that is set.  No centre sample set: the
+ * section is empty.
+ * Record: count = the size of the section; sum_x, sum_k = the sums of x and of k over it (at most 64 * 64 * 63); border = the number of
+ * its samples with x in {0, width - 1} or k in {0, slab_samples - 1}: nonzero says the window cut the lumen.
+ * Asynchronous and ordered on the context's stream; the rows are staged as in clwh_render_curved.
+ * Errors.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a NULL, wrong-kind or misaligned mask (8 bytes) or records buffer (16 bytes);
+ * rows == NULL; unknown flag bits; n_rows outside [1, 65535], width or slab_samples outside [1, 64]; a step that is not finite and > 0;
+ * dims beyond clwh_segment_grow's limits; rows that are not finite or reach 2^30, as in clwh_render_curved.  CLWH_ERR_SIZE_MISMATCH: a
+ * mask smaller than grow's size for `dims`, records smaller than 16 * n_rows bytes.  Nothing is written on an error. */
+enum clwh_profile_flags { CLWH_PROFILE_CONNECTED = 1 };
+typedef struct clwh_section_record { uint32_t count, sum_x, sum_k, border; } clwh_section_record;  /* 16 bytes */
+typedef struct clwh_curve_profile_desc {
+  clwh_mem *mask;             /* plain device buffer, grow's layout */
+  uint32_t dims[3];           /* X, Y, Z of the mask */
+  const float *rows;          /* HOST, float32[n_rows][9], as above */
+  uint32_t n_rows;            /* 1 .. 65535, any number */
+  uint32_t width;             /* 1 .. 64 samples across (x) */
+  int32_t  slab_samples;      /* 1 .. 64 samples along normal (k) */
+  float step;
+  int32_t flags;
+  clwh_mem *records;          /* plain device buffer, clwh_section_record[n_rows] */
+} clwh_curve_profile_desc;
+int clwh_curve_profile(clwh_ctx *ctx, const clwh_curve_profile_desc *desc);
+
 /* ---- the isosurface as an indexed triangle mesh, by marching tetrahedra (not in the reference): the first output that is geometry, not
  * pixels.  Every decision is an integer comparison, so the result is defined bit for bit.
  * Grid.  Grid point P = (x, y, z), 0 <= P.c < dim_c, carries A(P) = (int64)V[z][y][x] << 24 and sits at the voxel's centre P + 0.5: the
