@@ -3,6 +3,8 @@ import numpy as np
 import pytest
 
 from cl_volume_renderer_amd import ffi, scene
+from tests.sdf_event_cases import blobs as _blobs
+from tests.sdf_event_cases import reference_host_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -29,31 +31,9 @@ def test_reference_host_loop_over_the_generic_launch(gpu_ctx, sdf_golden):
     """app/signed_distance_field.cpp:7-35 re-enacted call by call over clwh_kernel_get / clwh_launch,
     i.e. what the reference's unmodified host code would do through the clw_* wrappers."""
     vol, gold = sdf_golden
-    Z, Y, X = vol.shape
-    ctx = gpu_ctx
-    v = ctx.image_from(vol.astype(np.int16))
-    sdf = ctx.image([X, Y, Z], 1, np.int8, (Z, Y, X)); sdf.push(np.zeros((Z, Y, X), np.int8))
-    pong = ctx.image([X, Y, Z], 1, np.int8, (Z, Y, X))
-    code = scene.TF_TEST_VALUE_GT_800
-    max_it = min(max(X, Y, Z) // 2, 127)
-    ev = lambda g, l: (g + l - 1) // l * l  # noqa: E731  evenness(), app/common.hpp:59-66
-    gsz = [ev(X, 8), ev(Y, 8), ev(Z, 8)]
-    ctx.kernel("signed_distance_field.cl", "create_base_image", code).launch(gsz, [4, 4, 4], v, sdf, pong, np.uint32(max_it))
-    layer = ctx.kernel("signed_distance_field.cl", "create_signed_distance_field", code)
-    counter = ctx.buffer(4, np.int32)
-    ping_, pong_ = sdf, pong
-    launches = 0
-    for i in range(1, max_it + (max_it % 2) + 1 + 1):
-        counter.push(np.zeros(1, np.int32))
-        layer.launch(gsz, [4, 4, 4], ping_, pong_, np.uint32(i), counter, np.uint32(max_it))
-        ping_, pong_ = pong_, ping_
-        launches += 1
-        if counter.pull()[0] == 0 and i % 2 == 1:
-            break
+    launches, out = reference_host_loop(gpu_ctx, vol, scene.TF_TEST_VALUE_GT_800)
     assert launches == 13
-    assert np.array_equal(sdf.pull().reshape(-1).astype(np.int32), gold)
-    for m in (v, sdf, pong, counter):
-        m.release()
+    assert np.array_equal(out.reshape(-1).astype(np.int32), gold)
 
 
 @pytest.mark.parametrize("dims,tf", [
@@ -124,19 +104,6 @@ def test_sdf_at_512_equals_the_committed_oracle_checksum(gpu_ctx, golden_dir, tf
     assert int(sdf.astype(np.int64).sum()) == want["sum"]
     assert hashlib.sha256(sdf.tobytes()).hexdigest() == want["sha256"]
     v.release(); s.release()
-
-
-def _blobs(dims, seed):
-    """random smooth blobs: fronts in every direction, seeds in all four parity classes, surfaces that meet the volume's faces"""
-    rng = np.random.default_rng(seed)
-    Z, Y, X = dims[2], dims[1], dims[0]
-    z, y, x = np.mgrid[0:Z, 0:Y, 0:X].astype(np.float32)
-    vol = np.full((Z, Y, X), -900.0, np.float32)
-    for _ in range(5):
-        c = rng.uniform(0, 1, 3) * np.array([X, Y, Z])
-        r = rng.uniform(0.08, 0.3) * max(dims)
-        vol = np.maximum(vol, 1000.0 - 60.0 * (np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2) - r))
-    return np.ascontiguousarray(np.clip(vol, -1000, 1100).astype(np.int16))
 
 
 @pytest.mark.parametrize("variant", ["bits", "bits16", "bits_rec_lds", "front"])
