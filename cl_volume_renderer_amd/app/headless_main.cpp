@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -52,6 +52,14 @@
 // --projection, --composite and --isosurface): half-transparent colour, an outline, or both.  --components colours every selected
 // component by its rank (with a morphology item: the morphed mask, in one colour).  The JSON lines say "mode": "show" and
 // "overlay": "fill" | "outline" | "both".  show excludes keep, remove and fill=, and needs one of those four views.
+// --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]: where --grow runs, the
+// volume is divided among the clicks (X:Y:Z each, ids 1, 2, ... in order) by the seeded watershed of its gradient
+// (renderer::watershed_edges: the cost is 1 + the gradient's length clamped at G, default 4096; plateau_cap N, default 65534; ",26":
+// 26 neighbours): every click floods its basin, and two floods meet on the edge between them.  One JSON line {"watershed": {"seeds",
+// "connectivity", "gmax", "plateau", "mode", "fill", "reached", "max_level", "counts"}}, counts being the voxels of every id
+// (renderer::measure_labels).  show draws the labelling over the view like --components' (a colour per id); keep=ID / remove=ID make
+// the territory of one click the mask (renderer::select_components) and apply it like --grow's region; with none of the three the
+// volume is left as it is.  --watershed excludes --grow and --components.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -98,6 +106,10 @@ int main(int argc_in, char const *argv_in[]) {
   bool curved = false;         // --curved
   float curved_window = 32.0f, curved_angle = 0.0f;
   int curved_mode = CLWH_SLICE_MAX, curved_slab = 1;
+  bool shed = false;           // --watershed
+  std::vector<uint32_t> shed_seeds;  // (x, y, z, id) quadruples
+  int shed_flags = 0, shed_fill = -32768;
+  long shed_gmax = 4096, shed_plateau = CLWH_WATERSHED_PLATEAU_MAX, shed_keep = -1, shed_remove = -1;
   int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
   bool rewrites = false; // a keep, remove or fill= item
   // whether `v` is the show item; *ok is cleared if its style is unknown
@@ -134,6 +146,7 @@ int main(int argc_in, char const *argv_in[]) {
   };
   static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
   static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kShedUsage = "(--watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V])";
   static const char *const kCurvedUsage = "(--curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean], with --grow=...,centerline=X,Y,Z)";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
   std::vector<const char *> args{argv_in[0]};
@@ -306,6 +319,61 @@ int main(int argc_in, char const *argv_in[]) {
     } else if (a.rfind("--components", 0) == 0) {
       std::cout << "Unknown option '" << a << "' " << kCompsUsage << "\n";
       return 1;
+    } else if (a.rfind("--watershed=", 0) == 0) {
+      std::string rest = a.substr(12);
+      bool ok = true;
+      for (int field = 0; ok && (field == 0 || !rest.empty()); ++field) {
+        const size_t comma = rest.find(',');
+        const std::string v = rest.substr(0, comma);
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+        if (comma != std::string::npos && rest.empty()) ok = false;  // a trailing comma
+        char *end = nullptr;
+        if (v.find(':') != std::string::npos) {  // a click: they come first
+          uint32_t at[3] = {0, 0, 0};
+          const char *p = v.c_str();
+          for (int q = 0; ok && q < 3; ++q) {
+            const long long n = std::strtoll(p, &end, 10);
+            ok = end != p && *p != '-' && *p != '+' && n >= 0 && n <= 0x7fffffffLL && *end == (q < 2 ? ':' : '\0');
+            at[q] = (uint32_t)n;
+            p = end + 1;
+          }
+          ok = ok && (size_t)field == shed_seeds.size() / 4 && shed_seeds.size() / 4 < CLWH_GROW_MAX_SEEDS;
+          shed_seeds.insert(shed_seeds.end(), {at[0], at[1], at[2], (uint32_t)(shed_seeds.size() / 4 + 1)});
+        } else if (v == "26") {
+          shed_flags |= CLWH_GEO_26;
+        } else if (show_item(v, &ok)) {
+        } else if (v.rfind("gmax=", 0) == 0) {
+          shed_gmax = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && shed_gmax >= 1 && shed_gmax <= 2 * 65535;
+        } else if (v.rfind("plateau=", 0) == 0) {
+          shed_plateau = std::strtol(v.c_str() + 8, &end, 10);
+          ok = ok && v.size() > 8 && *end == '\0' && shed_plateau >= 0 && shed_plateau <= (long)CLWH_WATERSHED_PLATEAU_MAX;
+        } else if (v.rfind("keep=", 0) == 0) {
+          shed_keep = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && shed_keep >= 1;
+          rewrites = true;
+        } else if (v.rfind("remove=", 0) == 0) {
+          shed_remove = std::strtol(v.c_str() + 7, &end, 10);
+          ok = ok && v.size() > 7 && *end == '\0' && shed_remove >= 1;
+          rewrites = true;
+        } else if (v.rfind("fill=", 0) == 0) {
+          const long n = std::strtol(v.c_str() + 5, &end, 10);
+          ok = ok && v.size() > 5 && *end == '\0' && n >= -32768 && n <= 32767;
+          shed_fill = (int)n;
+        } else {
+          ok = false;
+        }
+      }
+      const long n_ids = (long)(shed_seeds.size() / 4);
+      if (!ok || n_ids < 1 || (shed_keep >= 0 && shed_remove >= 0) || (show >= 0 && rewrites) || shed_keep > n_ids || shed_remove > n_ids ||
+          (shed_fill != -32768 && !rewrites)) {
+        std::cout << "Unknown option '" << a << "' " << kShedUsage << "\n";
+        return 1;
+      }
+      shed = true;
+    } else if (a.rfind("--watershed", 0) == 0) {
+      std::cout << "Unknown option '" << a << "' " << kShedUsage << "\n";
+      return 1;
     } else if (a.rfind("--slice=", 0) == 0) {
       std::string rest = a.substr(8);
       bool ok = true;
@@ -376,8 +444,12 @@ int main(int argc_in, char const *argv_in[]) {
     std::cout << "--grow and --components exclude each other\n";
     return 1;
   }
+  if (shed && (grow || comps)) {
+    std::cout << "--watershed excludes --grow and --components\n";
+    return 1;
+  }
   if (show >= 0 && projection < 0 && composite < 0 && !isosurface && slice < 0) {
-    std::cout << "show needs --projection, --composite, --isosurface or --slice " << (grow ? kGrowUsage : kCompsUsage) << "\n";
+    std::cout << "show needs --projection, --composite, --isosurface or --slice " << (shed ? kShedUsage : grow ? kGrowUsage : kCompsUsage) << "\n";
     return 1;
   }
   if (curved && (projection >= 0 || composite >= 0 || isosurface || slice >= 0 || mesh)) {
@@ -407,7 +479,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -589,6 +661,36 @@ int main(int argc_in, char const *argv_in[]) {
       std::printf("}\n");
     }
     std::printf("%s", split_line.c_str());
+  }
+
+  if (shed) {  // like --grow: everything below sees the volume as this leaves it
+    const auto &size = rv.get_volume_size();
+    for (size_t k = 0; k < shed_seeds.size(); k += 4)
+      for (int q = 0; q < 3; ++q)
+        if (shed_seeds[k + q] >= size[q]) {
+          std::cout << "The --watershed seed (" << shed_seeds[k] << ", " << shed_seeds[k + 1] << ", " << shed_seeds[k + 2] << ") lies outside the volume\n";
+          return 1;
+        }
+    ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
+    const uint32_t n_ids = (uint32_t)(shed_seeds.size() / 4);
+    const renderer::watershed_summary w = r.watershed_edges(none, shed_seeds, shed_flags, (uint32_t)shed_gmax, (uint32_t)shed_plateau);
+    const std::vector<clwh_region_stats> records = r.measure_labels(none, n_ids);  // of the volume as loaded
+    if (shed_keep >= 0 || shed_remove >= 0) {
+      const uint32_t id = (uint32_t)(shed_keep >= 0 ? shed_keep : shed_remove);
+      r.select_components(none, id, id);
+      r.apply_mask(none, shed_fill, shed_remove >= 0 ? CLWH_MASK_INVERT : 0);
+    }
+    if (show >= 0) {
+      show_source = renderer::OVERLAY_LABELS;
+      show_style.id_hi = n_ids;
+    }
+    std::printf("{\"watershed\": {\"seeds\": %u, \"connectivity\": %d, \"gmax\": %ld, \"plateau\": %ld, \"mode\": \"%s\", \"fill\": %d, "
+                "\"reached\": %llu, \"max_level\": %u, \"counts\": [",
+                n_ids, (shed_flags & CLWH_GEO_26) ? 26 : 6, shed_gmax, shed_plateau,
+                show >= 0 ? "show" : shed_keep >= 0 ? "keep" : shed_remove >= 0 ? "remove" : "none", shed_fill,
+                (unsigned long long)w.result.reached, w.result.max_level);
+    for (size_t k = 0; k < records.size(); ++k) std::printf("%s%llu", k ? ", " : "", (unsigned long long)records[k].count);
+    std::printf("]}}\n");
   }
 
   if (mesh) {  // geometry, not frames: no transfer function, no distance field, no camera

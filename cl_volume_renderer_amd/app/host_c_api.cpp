@@ -196,6 +196,23 @@ unsigned long long clvr_host_centerline(clvr_host *h, const unsigned start[3], c
   std::memcpy(out, points.data(), std::min<size_t>(points.size(), (size_t)capacity * 3) * sizeof(uint32_t));
   return points.size() / 3;
 }
+// renderer::watershed_gradient_table: up to `capacity` entries into out and the shift that goes with them; returns the table's length
+unsigned clvr_host_watershed_table(unsigned g_max, unsigned short *out, unsigned capacity, unsigned *shift) {
+  const std::vector<uint16_t> table = renderer::watershed_gradient_table(g_max, shift);
+  std::memcpy(out, table.data(), std::min<size_t>(table.size(), capacity) * sizeof(uint16_t));
+  return (unsigned)table.size();
+}
+// renderer::watershed_edges from n_seeds (x, y, z, id) quadruples: labels[Z][Y][X] and level[Z][Y][X] (either may be null), *max_level;
+// returns the voxels reached
+unsigned long long clvr_host_watershed_edges(clvr_host *h, const unsigned *seeds, unsigned n_seeds, int flags, unsigned g_max, unsigned plateau_cap,
+                                             unsigned *labels, unsigned *level, unsigned *max_level) {
+  const renderer::watershed_summary s =
+      h->rend.watershed_edges(h->state, std::vector<uint32_t>(seeds, seeds + 4u * n_seeds), flags, g_max, plateau_cap, labels != nullptr);
+  if (labels) std::memcpy(labels, s.labels.data(), s.labels.size() * sizeof(uint32_t));
+  if (level) std::memcpy(level, s.level.data(), s.level.size() * sizeof(uint32_t));
+  *max_level = s.result.max_level;
+  return s.result.reached;
+}
 
 // renderer::curve_frames of n_points (x, y, z) triples of doubles: up to `capacity` rows of nine floats into rows_out and as many
 // stations' s_mm as fit `capacity` into s_out (either may be null); *n_out = the stations; returns the rows (n rounded up to 8)

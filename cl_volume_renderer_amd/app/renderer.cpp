@@ -794,6 +794,58 @@ renderer::geodesic_summary renderer::cost_geodesic(struct ui_state &, const std:
   return out;
 }
 
+std::vector<uint16_t> renderer::watershed_gradient_table(uint32_t g_max, uint32_t *shift) {
+  if (g_max < 1 || g_max > 2u * 65535u) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+  const uint64_t g_sq = (uint64_t)g_max * g_max;
+  uint32_t s = 0;
+  while ((g_sq >> s) >= 65536u) ++s;
+  std::vector<uint16_t> table((size_t)(g_sq >> s) + 1);
+  uint64_t root = 0;  // isqrt(i << s), which never falls as i grows
+  for (uint64_t i = 0; i < table.size(); ++i) {
+    while ((root + 1) * (root + 1) <= (i << s)) ++root;
+    table[i] = (uint16_t)(1 + std::min<uint64_t>(65534, root));
+  }
+  *shift = s;
+  return table;
+}
+
+renderer::watershed_summary renderer::watershed(struct ui_state &, const std::vector<uint32_t> &seeds, int flags, uint32_t plateau_cap,
+                                                uint32_t level_cap, bool pull_labels) {
+  const auto &size = volume->get_volume_size();
+  const size_t voxels = (size_t)size[0] * size[1] * size[2];
+  if (region_cost.size() != voxels) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no cost
+  if (region_labels.size() != voxels) region_labels = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  if (region_dist.size() != voxels) region_dist = clw_vector<uint32_t>(ctx, std::vector<uint32_t>(voxels), false);
+  watershed_summary out;
+  clwh_watershed_desc d{};
+  d.cost = region_cost.get_device_reference();
+  d.level = region_dist.get_device_reference();
+  d.labels = region_labels.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.plateau_cap = plateau_cap;
+  d.level_cap = level_cap;
+  d.flags = flags & ~CLWH_GEO_FROM_LABELS;
+  d.n_seeds = (uint32_t)(seeds.size() / 4);
+  d.seeds = seeds.data();
+  d.result = &out.result;
+  clw_fail_hard_on_error(clwh_watershed(ctx.get_handle(), &d));
+  region_dist.pull();
+  out.level.assign(&region_dist[0], &region_dist[0] + voxels);
+  if (pull_labels) {
+    region_labels.pull();
+    out.labels.assign(&region_labels[0], &region_labels[0] + voxels);
+  }
+  return out;
+}
+
+renderer::watershed_summary renderer::watershed_edges(struct ui_state &state, const std::vector<uint32_t> &seeds, int flags, uint32_t g_max,
+                                                      uint32_t plateau_cap, bool pull_labels) {
+  uint32_t shift = 0;
+  const std::vector<uint16_t> table = watershed_gradient_table(g_max, &shift);
+  cost_field(state, COST_FROM_GRADIENT, table, 0, shift, false);
+  return watershed(state, seeds, flags, plateau_cap, CLWH_WATERSHED_LEVEL_MAX, pull_labels);
+}
+
 std::vector<uint32_t> renderer::trace_cost_path(struct ui_state &, const uint32_t target[3], int flags) {
   const auto &size = volume->get_volume_size();
   const size_t voxels = (size_t)size[0] * size[1] * size[2];

@@ -203,6 +203,23 @@ class renderer : public frame_emitter {
   std::vector<uint32_t> centerline(struct ui_state &state, const uint32_t start[3], const uint32_t end[3], int flags = CLWH_GEO_26,
                                    float max_radius = 0.0f, uint32_t sharpness = 100);
 
+  // not in the reference: the seeded watershed of the cost field (clwh_watershed), beside cost_geodesic: every seed ((x, y, z, id)
+  // quadruples, id >= 1) floods its basin over cost_field's cost, and two floods meet on the ridge between them, however far either
+  // seed lies from it.  The id of the seed whose flood reaches a voxel goes to the labelling select_components, measure_labels and
+  // the overlays read; the levels (M << 16 | L, CLWH_DIST_NONE where nothing arrives) come back.  flags: CLWH_GEO_26 |
+  // CLWH_GEO_DENSE.  watershed_gradient_table: scene.watershed_gradient_table's integers, 1 + the gradient's length clamped at
+  // g_max, with the shift that goes with it.  pull_labels: the labelling comes back too (for small volumes).  watershed_edges: the two at once from clicks, over the unmasked gradient cost.
+  struct watershed_summary {
+    clwh_watershed_result result{};
+    std::vector<uint32_t> level, labels;  // labels: with pull_labels only
+  };
+  static std::vector<uint16_t> watershed_gradient_table(uint32_t g_max, uint32_t *shift);
+  watershed_summary watershed(struct ui_state &state, const std::vector<uint32_t> &seeds, int flags = 0,
+                              uint32_t plateau_cap = CLWH_WATERSHED_PLATEAU_MAX, uint32_t level_cap = CLWH_WATERSHED_LEVEL_MAX,
+                              bool pull_labels = false);
+  watershed_summary watershed_edges(struct ui_state &state, const std::vector<uint32_t> &seeds, int flags = 0, uint32_t g_max = 4096,
+                                    uint32_t plateau_cap = CLWH_WATERSHED_PLATEAU_MAX, bool pull_labels = false);
+
   // not in the reference: measuring (clwh_mask_statistics / clwh_label_statistics) on the volume the views show.  measure_mask: the
   // exact record of the region mask, whoever made it (count, sum, sum of squares, extremes, centroid numerators, bounding box, faces
   // per axis inside the volume and on its border), and with n_bins > 0 the histogram of its values, n_bins bins of bin_width from

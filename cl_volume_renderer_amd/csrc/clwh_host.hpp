@@ -2,7 +2,7 @@
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices, curved reformats, section profiles and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
-// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_region_stats.hip: statistics of masks and labels).
+// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_watershed.hip: the seeded watershed of a cost field; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
 #pragma once
 
@@ -251,7 +251,7 @@ struct DistanceScratch {
 
 // clwh_mask_geodesic's and clwh_geodesic_trace's scratch: the packed keys (8 bytes per voxel) and the worklist of their tiles of
 // 16 x 16 x 8 voxels, whose pinned line the trace's result travels in too.  Every call rewrites what it reads: only the allocations
-// are kept.
+// are kept.  clwh_watershed reuses both: the keys' bytes as two uint32 arrays, the worklist with a second word per tile.
 struct GeodesicScratch {
   DeviceBuffer keys, trace;  // trace: clwh_geodesic_trace's count and verdict
   TileScratch work;

@@ -729,6 +729,35 @@ hipError_t launch_cost_round(const CostArgs &a, uint32_t round, int slot, hipStr
 hipError_t launch_cost_trace(const CostTraceArgs &a, hipStream_t s);
 hipError_t launch_cost_field(const CostFieldArgs &a, hipStream_t s);
 
+// ---- seeded watershed of a cost field (watershed_kernels.hip; host side clwh_watershed.hip).  The tiles and the rounds are the
+// geodesic's; its 8 bytes of scratch per voxel hold two arrays of uint32, [z][y][x] without padding: the states (M << 16 | L, all ones
+// where nothing has arrived or can) and the working labels (id - 1, all ones for none).  Phase 1 (the states) and phase 2 (the labels)
+// run over one worklist with a set of stamps each.
+struct WsDeviceResult {        // what k_ws_finish accumulates, zero on entry
+  unsigned long long reached;
+  uint32_t max_level, reserved;
+};
+struct WsArgs {
+  const uint16_t *cost;        // [z][y][x], read only; 0 is a wall
+  const uint8_t *domain;       // grow's bit rows, read only, or null
+  const uint32_t *seed_labels; // CLWH_GEO_FROM_LABELS: the caller's words; else null
+  uint32_t *state, *wlab;      // scratch, one word per voxel each
+  uint32_t *level, *labels;    // the caller's maps; either may be null
+  int32_t X, Y, Z, W64;
+  uint32_t plateau_cap;        // <= 65534
+  uint32_t level_cap;          // <= 65535
+  int32_t conn26;
+  TileWork tiles;              // the phase being run: stamps is stamps_level or stamps_label
+  uint32_t *stamps_level, *stamps_label;
+  const uint32_t *seeds;       // device copy, uint32[n_seeds][4] = x, y, z, id
+  uint32_t n_seeds;
+  WsDeviceResult *result;
+};
+hipError_t launch_ws_init(const WsArgs &a, hipStream_t s);   // both arrays, the listed seeds, both phases' stamps of the tiles that hold a seed
+hipError_t launch_ws_level_round(const WsArgs &a, uint32_t round, int slot, hipStream_t s);  // k_tile_list + k_ws_level_round, counters[2 * slot]
+hipError_t launch_ws_label_round(const WsArgs &a, uint32_t round, int slot, hipStream_t s);  // k_tile_list + k_ws_label_round
+hipError_t launch_ws_finish(const WsArgs &a, hipStream_t s);  // level, labels, *result
+
 // ---- exact statistics of a mask's region and of every rank of a labelling (region_stats_kernels.hip; host side clwh_region_stats.hip).
 // Records are accumulated in place, in clwh_region_stats' layout: launch_stats_init sets the identities (extremes, bbox_lo), the sums'
 // kernels add with vector atomics, launch_stats_finish writes the empty record where nothing was added and makes bbox_hi exclusive.

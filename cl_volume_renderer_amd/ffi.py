@@ -36,6 +36,7 @@ GEO_26, GEO_FROM_LABELS, GEO_DENSE = 1, 2, 4
 GEO_CAP_MAX = 0xFFFF0000
 COST_CAP_MAX = 0xFF000000
 COST_SRC_U32, COST_SRC_VALUE, COST_SRC_GRADIENT = 0, 1, 2
+WATERSHED_PLATEAU_MAX, WATERSHED_LEVEL_MAX = 65534, 65535
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
@@ -338,6 +339,26 @@ class CostFieldDesc(C.Structure):
 assert C.sizeof(CostGeodesicDesc) == 112 and C.sizeof(CostTraceDesc) == 104 and C.sizeof(CostFieldDesc) == 72
 
 
+class WatershedResult(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("max_level", C.c_uint32), ("rounds", C.c_uint32)]
+
+    def as_dict(self):
+        """the contract's fields (`rounds` is informational and left out)"""
+        return {"reached": int(self.reached), "max_level": int(self.max_level)}
+
+
+class WatershedDesc(C.Structure):
+    _fields_ = [
+        ("cost", C.c_void_p), ("domain", C.c_void_p), ("seed_labels", C.c_void_p), ("level", C.c_void_p), ("labels", C.c_void_p),
+        ("dims", C.c_uint32 * 3), ("plateau_cap", C.c_uint32), ("level_cap", C.c_uint32), ("flags", C.c_int32),
+        ("n_seeds", C.c_uint32), ("seeds", C.POINTER(C.c_uint32)),
+        ("result", C.POINTER(WatershedResult)),
+    ]
+
+
+assert C.sizeof(WatershedDesc) == 88 and C.sizeof(WatershedResult) == 16
+
+
 class MaskCombineDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
 
@@ -457,6 +478,7 @@ _PROTOTYPES = [
     ("clwh_mask_geodesic", C.c_int, [C.c_void_p, C.POINTER(GeodesicDesc)]),
     ("clwh_geodesic_trace", C.c_int, [C.c_void_p, C.POINTER(GeodesicTraceDesc)]),
     ("clwh_cost_geodesic", C.c_int, [C.c_void_p, C.POINTER(CostGeodesicDesc)]),
+    ("clwh_watershed", C.c_int, [C.c_void_p, C.POINTER(WatershedDesc)]),
     ("clwh_cost_trace", C.c_int, [C.c_void_p, C.POINTER(CostTraceDesc)]),
     ("clwh_cost_from_field", C.c_int, [C.c_void_p, C.POINTER(CostFieldDesc)]),
     ("clwh_mask_statistics", C.c_int, [C.c_void_p, C.POINTER(MaskStatsDesc)]),
@@ -1376,6 +1398,61 @@ class Context:
                     m.release()
         _check(status, "clwh_cost_geodesic")
         return dist, labels, res
+
+    def watershed_raw(self, cost: Mem, dims, seeds=None, domain: Mem = None, seed_labels: Mem = None, flags=0, plateau_cap=WATERSHED_PLATEAU_MAX,
+                      level_cap=WATERSHED_LEVEL_MAX, labels: Mem = None, level: Mem = None, result=True):
+        """one clwh_watershed call: (status, WatershedResult); nothing is raised.  seeds: rows of (x, y, z, id), or None.
+        result=False passes a NULL result."""
+        d, res = WatershedDesc(), WatershedResult()
+        d.cost, d.domain, d.seed_labels, d.level, d.labels = (_handle(m) for m in (cost, domain, seed_labels, level, labels))
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        d.plateau_cap, d.level_cap, d.flags = int(plateau_cap), int(level_cap), int(flags)
+        if seeds is not None:
+            s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint32).reshape(-1, 4))
+            d.n_seeds = len(s)
+            d.seeds = s.ctypes.data_as(C.POINTER(C.c_uint32))
+        if result:
+            d.result = C.pointer(res)
+        return lib().clwh_watershed(self.h, C.byref(d)), res
+
+    def watershed(self, cost: Mem, dims, seeds=None, domain: Mem = None, seed_labels: Mem = None, connectivity=6,
+                  plateau_cap=WATERSHED_PLATEAU_MAX, level_cap=WATERSHED_LEVEL_MAX, labels: Mem = None, level: Mem = None, dense=False):
+        """the seeded watershed of the cost field `cost` (uint16 [z][y][x] on the device, 0 = wall; cost_from_field makes one): every
+        seed floods its basin, and two floods meet on the ridge between them: (labels, level, WatershedResult).  labels: the id of the
+        seed whose flood reaches the voxel, 0 where none does; level: M << 16 | L with M the height of the lowest pass from a seed and
+        L the steps since that height was reached, saturating at plateau_cap (0: the pure max-cost watershed); DIST_NONE where not
+        reached.  A voxel whose M would exceed level_cap is not reached.  seeds: rows of (x, y, z, id) and / or seed_labels (a uint32
+        map whose nonzero words are seeds; `labels` may be the same buffer).  The call waits for the device."""
+        if connectivity not in (6, 26):
+            raise ValueError("connectivity is 6 or 26")
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        own = [labels is None, level is None]
+        if own[0]:
+            labels = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        if own[1]:
+            level = self.buffer(4 * int(np.prod(shape)), np.uint32, shape)
+        flags = (GEO_26 if connectivity == 26 else 0) | (GEO_FROM_LABELS if seed_labels is not None else 0) | (GEO_DENSE if dense else 0)
+        status, res = self.watershed_raw(cost, dims, seeds, domain, seed_labels, flags, plateau_cap, level_cap, labels, level)
+        if status != OK:
+            for mine, m in zip(own, (labels, level)):
+                if mine:
+                    m.release()
+        _check(status, "clwh_watershed")
+        return labels, level, res
+
+    def watershed_edges(self, volume: Mem, dims, seeds, domain: Mem = None, connectivity=6, g_max=4096, plateau_cap=WATERSHED_PLATEAU_MAX,
+                        level_cap=WATERSHED_LEVEL_MAX, labels: Mem = None, level: Mem = None, dense=False):
+        """the watershed of the volume's gradient from clicks: cost_from_field with COST_SRC_GRADIENT through
+        scene.watershed_gradient_table(g_max) (cost = 1 + the gradient's length, clamped at g_max), then watershed.  The border between
+        two seeds lies on the strongest edge that separates them.  (labels, level, WatershedResult)."""
+        from .scene import watershed_gradient_table
+        table, shift = watershed_gradient_table(g_max)
+        cost = self.cost_from_field(volume, dims, table, 0, shift, COST_SRC_GRADIENT, domain)
+        try:
+            return self.watershed(cost, dims, seeds, domain, None, connectivity, plateau_cap, level_cap, labels, level, dense)
+        finally:
+            cost.release()
 
     def cost_trace_raw(self, cost: Mem, dist: Mem, dims, target, labels: Mem = None, flags=0, multipliers=None, points: Mem = None,
                        capacity=0, result=True):

@@ -911,7 +911,8 @@ int clwh_geodesic_trace(clwh_ctx *ctx, const clwh_geodesic_trace_desc *desc);
 /* ---- geodesic distance maps through a cost field (not in the reference): clwh_mask_geodesic with a step cost that depends on the voxel,
  * not only on the direction.  A shortest path through a tube hugs the inner wall of every bend; with a cost that is low in the middle
  * of the structure and high at its wall (clwh_cost_from_field over clwh_mask_distance's depth map) the path is the centreline, the
- * curve to measure a vessel's length along.  With a cost from the gradient, territories meet on the image's edges; with a cost from
+ * curve to measure a vessel's length along.  With a cost from the gradient, territories meet on the image's edges while the paths on
+ * both sides are of similar length (the cost is a SUM; clwh_watershed divides by the edges alone); with a cost from
  * the value and no domain, a path follows a bright vessel that nobody has segmented.  Integers and sets only: defined bit for bit,
  * independent of how the device schedules anything.
  * Cost.  `cost`: a plain device buffer, 2-byte aligned, uint16 [Z][Y][X] without padding, at least 2 * X * Y * Z bytes; read only.
@@ -1024,6 +1025,73 @@ typedef struct clwh_cost_field_desc {
   int32_t flags;              /* 0 */
 } clwh_cost_field_desc;
 int clwh_cost_from_field(clwh_ctx *ctx, const clwh_cost_field_desc *desc);
+
+/* ---- seeded watershed of a cost field (not in the reference): every seed floods its basin, and two floods meet on the ridge between
+ * them, however far either seed lies from it.  clwh_cost_geodesic SUMS the cost along a path, so a seed 3 voxels from a ridge of cost
+ * 20 spills over it before a seed 40 voxels away across a basin of cost 1 gets there; the watershed takes the MAXIMUM along the path,
+ * the height of the lowest pass, and the border lies on the ridge.  With a cost from the gradient (clwh_cost_from_field,
+ * CLWH_COST_SRC_GRADIENT) one click in each organ divides the image along the edges between them.  Integers and sets only: defined
+ * bit for bit, in two stages, so that the answer is a function of the input alone.
+ * Cost, domain.  `cost` and `domain` are clwh_cost_geodesic's: a plain device buffer, 2-byte aligned, uint16 [Z][Y][X] without padding,
+ * read only; an optional mask in clwh_segment_grow's layout, read only, bits at x >= X and the padding words ignored.
+ * D = { p : cost(p) >= 1 and (domain == NULL or p's bit in `domain` is set) }: a cost of 0 is a wall.
+ * Neighbours, seeds, flags.  clwh_mask_geodesic's: 6 neighbours, or 26 with CLWH_GEO_26; seeds on the HOST as (x, y, z, id), id >= 1,
+ * at most CLWH_GROW_MAX_SEEDS, and/or with CLWH_GEO_FROM_LABELS every voxel of D whose word in seed_labels is not 0, with that word as
+ * its id; several ids on one voxel are allowed; a seed outside D contributes nothing.  CLWH_GEO_DENSE: same bytes, by the contract.
+ * Stage 1, the level.  A state is a pair (M, L), ordered lexicographically.  A path in D from a seed starts with (0, 0) at the seed's
+ * own voxel, whatever its cost; stepping into p with c = cost(p) turns (M, L) into (c, 0) if c > M and into (M, min(L + 1,
+ * plateau_cap)) otherwise.  ML(p) = the smallest state over all paths in D from any seed to p.  M is the height of the lowest pass from a
+ * seed to p; L counts the steps since that height was reached and saturates at plateau_cap (0 .. 65534): it divides a plateau by the
+ * distance from where the flood entered it, where without it a flat region would go whole to the smallest id.  plateau_cap = 0 is the
+ * pure max-cost watershed.  A voxel whose M would exceed level_cap (0 .. 65535) counts as not reached.  The step is monotone in the
+ * state and never lowers it, so the minimum over paths is also the least fixpoint of the relaxation.
+ * Stage 2, the label.  Between neighbours q, p in D that are both reached, q -> p is an edge iff the step from ML(q) into p gives
+ * exactly ML(p).  label(p) = the smallest id of any seed from whose voxel p can be reached along edges (a seed on s reaches s).  Every
+ * reached voxel has such a seed: on a path s = p0 .. pn that attains ML(p), let j be the last index with ML(pj) < ML(p); the step from
+ * ML(pj) into pj+1 lies between ML(pj+1) = ML(p) and the path's own state there, which is at most ML(p), so it is an edge, and so is
+ * every later step, between voxels whose state is ML(p) already; by induction on the state pj is reached from a seed.  No step gives
+ * (0, 0), so no edge enters a seed's voxel: it keeps the smallest of its own ids.  With L saturated the edges can form cycles; the
+ * definition does not mind.
+ * Outputs.  labels: uint32 [Z][Y][X], 0 outside D and where the voxel is not reached; it may name seed_labels' memory.  level: uint32
+ * [Z][Y][X] = M << 16 | L, CLWH_DIST_NONE outside D and where the voxel is not reached (plateau_cap <= 65534 keeps the two apart).
+ * Either may be NULL, not both.  All X * Y * Z words of an output are written and nothing behind them.  *result (host, required):
+ * reached, the number of voxels with a state; max_level, the largest M among them (0 when nothing is reached); rounds: of both stages
+ * together, informational, not part of the contract.  Without `labels` stage 2 is not run.
+ * Limits, ordering, scratch.  clwh_mask_geodesic's limits.  SYNCHRONOUS, ordered on the context's stream, returns with everything
+ * written.  The scratch is that call's 8 * X * Y * Z bytes, reused as two uint32 arrays, its worklist with a second word per tile, and
+ * the copied seeds.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; a cost that is NULL, an image or not
+ * 2-byte aligned; a domain that is given and breaks grow's rules for a mask (an image, not 8-byte aligned); level and labels both NULL,
+ * one of them an image or not 4-byte aligned; CLWH_GEO_FROM_LABELS with a NULL, image or misaligned seed_labels; unknown flag bits;
+ * dims that break the limits; plateau_cap > 65534; level_cap > 65535; n_seeds > CLWH_GROW_MAX_SEEDS, n_seeds > 0 with NULL seeds,
+ * n_seeds == 0 without CLWH_GEO_FROM_LABELS; a seed outside the volume or with id 0.  CLWH_ERR_SIZE_MISMATCH: a cost smaller than
+ * 2 * X * Y * Z bytes; a domain smaller than its layout; level, labels or (with the flag) seed_labels smaller than 4 * X * Y * Z bytes.
+ * CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written on any of these.  (CLWH_ERR_INTERNAL_OVERFLOW: a stage
+ * passed its hard cap of X * Y * Z + 2 rounds, which no input can cause: cutting a loop out of a path never raises its state, so every
+ * ML is attained by a path that visits no voxel twice and crosses fewer tile faces than the volume has voxels; the same holds for the
+ * chain of edges behind a label.) */
+#define CLWH_WATERSHED_PLATEAU_MAX 65534u
+#define CLWH_WATERSHED_LEVEL_MAX 65535u
+typedef struct clwh_watershed_result {
+  uint64_t reached;
+  uint32_t max_level;
+  uint32_t rounds;
+} clwh_watershed_result;
+typedef struct clwh_watershed_desc {
+  clwh_mem *cost;             /* plain device buffer, uint16[Z][Y][X]; read only; 0 = wall */
+  clwh_mem *domain;           /* optional plain device buffer in the mask layout; read only */
+  clwh_mem *seed_labels;      /* CLWH_GEO_FROM_LABELS: plain device buffer, uint32[Z][Y][X] */
+  clwh_mem *level;            /* optional plain device buffer, uint32[Z][Y][X] = M << 16 | L */
+  clwh_mem *labels;           /* optional, the same; may name seed_labels' memory */
+  uint32_t dims[3];           /* X, Y, Z */
+  uint32_t plateau_cap;       /* 0 .. 65534 */
+  uint32_t level_cap;         /* 0 .. 65535 */
+  int32_t flags;              /* clwh_geodesic_flags */
+  uint32_t n_seeds;
+  const uint32_t *seeds;      /* host; uint32[n_seeds][4] = x, y, z, id */
+  clwh_watershed_result *result;  /* host; required */
+} clwh_watershed_desc;
+int clwh_watershed(clwh_ctx *ctx, const clwh_watershed_desc *desc);
 
 /* ---- measuring a region (not in the reference): once a mask has been grown, dilated, closed, intersected or selected from a
  * labelling, "how many voxels is this now, what is its mean density, where is it, how large is its surface" -- on the device, as exact
