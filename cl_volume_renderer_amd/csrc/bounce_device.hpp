@@ -23,6 +23,10 @@ __device__ __forceinline__ uint32_t udivmod24(uint32_t n, uint32_t d, uint32_t &
   return q;
 }
 
+// A wave-uniform value, pinned to a scalar register.  What the vector unit computed or loaded (a division's reciprocal, a word of global
+// memory) stays in a vector register otherwise, uniform or not, and every branch on it becomes an exec-mask branch.
+__device__ __forceinline__ uint32_t scalar_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
 // number of set bits of `mask` below this lane
 __device__ __forceinline__ unsigned prefix_count(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));

@@ -159,6 +159,7 @@ Tuning clvr::tuning_from_environment() {
   if (const char *e = std::getenv("CLWH_TUNE_QUEUES")) t.unit_queues = clamped(e, 1, 8);
   if (const char *e = std::getenv("CLWH_TUNE_GROUP")) t.unit_group = std::max(1, std::atoi(e));
   if (const char *e = std::getenv("CLWH_TUNE_CHUNK_BLOCK_LOG2")) t.unit_block_log2 = clamped(e, 0, 8);
+  if (const char *e = std::getenv("CLWH_TUNE_UNIT_AHEAD")) t.unit_ahead = std::atoi(e) != 0;
   if (const char *e = std::getenv("CLWH_TUNE_BLOCKS")) t.bounce_max_blocks = (uint32_t)std::max(1, std::atoi(e));
   if (const char *e = std::getenv("CLWH_TUNE_MACRO_SHIFT")) t.macro_shift = std::atoi(e);
   if (const char *e = std::getenv("CLWH_TUNE_LONG_LAUNCH")) t.force_long_launch = std::atoi(e) != 0;

@@ -137,6 +137,7 @@ struct Tuning {
   int32_t literal_gradient = 0;
   int32_t unit_block_log2 = 4;
   int32_t unit_group = 1, unit_affinity = 0, unit_queues = 8;
+  int32_t unit_ahead = -1;     // CLWH_TUNE_UNIT_AHEAD=0/1: k_bounce's waves reserve their next unit a pass ahead: never / always (-1: launch_bounce decides -- never)
   int32_t cert_hint = 1;       // CLWH_TUNE_CERT_HINT=0: a refused march asks again at its next long step, whatever the refusing entry says
   int32_t start_cert = 1;      // CLWH_TUNE_START_CERT=0: no start-certificate table (a byte per voxel), first legs march from their first step
   int32_t hull_cert = 1;       // CLWH_TUNE_HULL_CERT=0: no hull-certificate table, no plane search in k_primary, no test in k_bounce

@@ -148,6 +148,9 @@ struct RenderArgs {
   int32_t unit_queues;         // number of unit queues (1..8)
   int32_t unit_affinity;       // 0: the wave's XCD picks its home queue (default); 1: wave number; 2: queue 0 (experiments)
   TfDev tf;
+  // k_bounce: 1 = a wave reserves its next unit when it starts on the current one (the atomic's answer is there when it is wanted);
+  // 0 = it asks when it needs one.  In: -1 = launch_bounce decides (0: measured), CLWH_TUNE_UNIT_AHEAD forces 0 / 1
+  int32_t unit_ahead;  // (behind the table: every older field keeps its place in the argument segment)
 };
 
 // ---- repack arguments (volume + sdf + TF -> step bytes + hit records)

@@ -270,6 +270,7 @@ static int describe_launch(const clwh_ctx *ctx, const clwh_render_desc *d, Rende
   a.unit_block_log2 = t.unit_block_log2;
   a.unit_affinity = t.unit_affinity;
   a.unit_queues = t.unit_queues;
+  a.unit_ahead = t.unit_ahead;
   a.cert_hint = t.cert_hint;
   a.start_cert_dmin = start_cert_dmin(a.X, a.Y, a.Z);
   a.hull_delta0 = hull_cert_delta0(a.X, a.Y, a.Z);

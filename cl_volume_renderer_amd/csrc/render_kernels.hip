@@ -64,7 +64,12 @@ constexpr int kBounceThreads = CLVR_BOUNCE_THREADS;  // the waves of a block sha
 // 70 steps) parks in EVENT until the wave runs its event phase; IDLE lanes have no item.  The event
 // phase has two halves with the refill between them, so a lane whose sample ends takes its next
 // item and starts it in the same phase (k_bounce2 still parks fresh items through a step run).
-template <bool USE_GRAD, int MODE, bool SMALL_VOLUME>
+//
+// UNITS picks the refill (see there): true, a wave reserves whole units of 64 items and decodes a unit once on scalar operands -- fewer
+// wave instructions and atomics, more L2-missing lines: long launches of tables without `gradient` rules, which are bound by VALU
+// issue as much as by memory; false, every refill takes the queue's next n_idle items and each lane decodes its own -- launches that
+// run at the line rate of their misses (`gradient` tables) and short launches, a chain of dependent waits.
+template <bool USE_GRAD, int MODE, bool SMALL_VOLUME, bool UNITS>
 __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_bounce(const RenderArgs a) {
   constexpr int SMALL = SMALL_VOLUME ? 2 : 0;  // 2: the per-axis index terms are read from LDS (packed_volume.hpp)
   VolumePacked vol = make_volume(a);
@@ -80,11 +85,32 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   stage_rule_colors(rule_color, a.tf);
   __syncthreads();
   // the hit count of this camera: a kernel argument, or still only on the device (single-pass launches, clwh_render)
-  const uint32_t n_hits = a.n_hits_on_device ? a.counters[CTR_HITS] : a.n_hits;
+  const uint32_t n_hits_arg = a.n_hits_on_device ? a.counters[CTR_HITS] : a.n_hits;
+  const uint32_t n_hits = UNITS ? scalar_u32(n_hits_arg) : n_hits_arg;
   const uint32_t n_chunks = (n_hits + 63u) >> 6;
   const unsigned lane = lane_id();
-  const unsigned home_queue = home_queue_of(a, (unsigned)(kBounceThreads / 64));
-  unsigned queue_dry = 0u;  // bit q: queue q is known to be empty (lane 0's copy is the one that matters)
+  const unsigned home_queue_xcd = home_queue_of(a, (unsigned)(kBounceThreads / 64));
+  const uint32_t home_queue = UNITS ? scalar_u32(home_queue_xcd % (unsigned)a.unit_queues) : home_queue_xcd;
+  unsigned queue_dry_lane0 = 0u;  // !UNITS: bit q: queue q is known to be empty (lane 0's copy is the one that matters)
+  bool exhausted = false;         // wave-uniform: the queues have no more items (UNITS: a copy of W_EXHAUSTED)
+  // UNITS: the wave's place in the unit queues (see the refill) is wave-uniform and the refill works on it in scalar registers.  Between
+  // two refills that state lives in lanes of ONE vector register (as the scalar registers the compiler spills do): the refill reads
+  // it into scalar registers and writes it back, and the step loop and the event phase carry no scalar of it.
+  enum : int { W_UNIT_H,      // the current unit: the hit its next item names,
+               W_UNIT_LEFT,   // that many of its 64 items are left (0: the wave holds no unit),
+               W_UNIT_SEED,   // its seed
+               W_UNIT_S,      // and the seed's index (voxel-cache launches: the grants count seeds)
+               W_TICKET_Q,    // the queue of the ticket below, kNoTicket: none is out
+               W_QUEUE_DRY,   // bit q: queue q is known to be empty
+               W_EXHAUSTED }; // every queue is dry and the wave holds no unit
+  constexpr uint32_t kNoTicket = 0xFFu;
+  uint32_t wave_state = lane == (unsigned)W_TICKET_Q ? kNoTicket : 0u;
+#define WAVE_GET(k) ((uint32_t)__builtin_amdgcn_readlane((int)wave_state, (k)))
+#define WAVE_SET(k, v) asm("v_writelane_b32 %0, %1, %2" : "+v"(wave_state) : "s"(scalar_u32(v)), "n"(k))
+  // The ticket: lane 0's answer to an atomicAdd(head of queue W_TICKET_Q, 64), asked for but not yet looked at.  With `ahead` it is
+  // asked when the unit before it becomes current, a step run or more before it is wanted; without, in the refill that wants it.
+  uint32_t ticket = 0u;
+  const bool ahead = a.unit_ahead != 0;
   // The sample.  What only the event phase needs lives in LDS, one dword per lane and field (a conflict-free
   // ds_read/ds_write each): the registers decide how many waves a SIMD holds, and with one dependent fetch per step it
   // is the number of waves in flight that sets the pace.
@@ -134,7 +160,6 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   // an armed lane's grant fires while it has at least this budget left: two constants and the flag -- J as a kernel argument, one more
   // scalar live across the step loop, gave every instance a private segment
   constexpr uint32_t kFireDefer = (uint32_t)(70 - kHullDeferSteps) * kOneStep, kFireTilt = (uint32_t)(70 - kHullTiltSteps) * kOneStep;
-  bool exhausted = false;  // wave-uniform: the queue has no more items
   BounceStats stats;
 
   // One pass of the loop: step run, closing half of the event phase, refill, opening half.  (First pass: no lane marches and no
@@ -332,85 +357,207 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
     // An item is (hit, seed); 64 consecutive items of a queue are one unit = (chunk of 64 consecutive hits,
     // seed).  Units are dealt to eight queues by chunk number; a wave serves the queue of the XCD it runs on
     // first (so the seeds of one chunk -- thousands of rays leaving the same few voxels -- meet in ONE L2)
-    // and steals from the other queues when its own is dry.  As soon as `refill_min_lanes` lanes are idle
-    // they take the next items in queue order (one atomic per refill), so a wave does not drain down to its
-    // slowest sample before it gets new work.  Placement only affects speed.
+    // and steals from the other queues when its own is dry.  Two forms (UNITS; launch_bounce picks).  The dealing by
+    // refill, second below: as soon as `refill_min_lanes` lanes are idle they take the queue's next n_idle items with one
+    // atomic and every lane decodes its own.  Whole units, first below: a wave reserves WHOLE units, one atomicAdd(head, 64)
+    // each (every head is a multiple of 64), and decodes a unit once, on scalar operands: chunk -> first hit, seed
+    // index -> seed.  As soon as `refill_min_lanes` lanes are idle they take the next items of the wave's unit --
+    // h = unit_h + rank, no division and no per-lane seed load -- and, where that unit ends, go on in the next one
+    // in the same refill, so a wave does not drain down to its slowest sample before it gets new work.  A refill
+    // that stays inside its unit (three in four on the headline) waits once, for the hit records and hull words,
+    // which are issued together; one that uses its unit up waits for the atomic's answer first.  With `ahead`
+    // (CLWH_TUNE_UNIT_AHEAD=1; off: launch_bounce) the unit after the current one is asked for when the current one
+    // starts and that wait goes too.  Placement only affects speed.
     const unsigned long long idle_mask = __ballot(st == ST_IDLE);
     const uint32_t n_idle = (uint32_t)__popcll(idle_mask);
+    if (UNITS) exhausted = WAVE_GET(W_EXHAUSTED) != 0u;
     if (!exhausted && n_idle >= (uint32_t)a.refill_min_lanes) {
-      const uint32_t NQ = (uint32_t)a.unit_queues, S = (uint32_t)a.n_seeds, G = (uint32_t)a.unit_group;
-      const uint32_t KB = (uint32_t)a.unit_block_log2, n_blocks = (n_chunks + (1u << KB) - 1u) >> KB;
-      uint32_t base = 0u, count = 0u, q_sel = 0u;
-      if (lane == 0u) {
-        for (uint32_t tries = 0; tries < NQ && count == 0u; ++tries) {
-          const uint32_t q = (home_queue + tries) % NQ;
-          // blocks of 2^unit_block_log2 consecutive chunks are dealt round-robin to the queues (a block past the
-          // last chunk is padding: its items name hits that do not exist and are skipped)
-          const uint32_t blocks_q = (n_blocks + NQ - 1u - q) / NQ;
-          const uint32_t chunks_q = blocks_q << KB;
-          if (chunks_q == 0u || ((queue_dry >> q) & 1u)) continue;
-          const uint32_t total = chunks_q * S * 64u;
-          // every head sits on its own 128-byte line: same-address atomics serialise at one L2 channel
-          const uint32_t p = atomicAdd(&a.counters[CTR_QUEUE_STRIDE * (q + 1u)], n_idle);
-          if (p + n_idle >= total) queue_dry |= 1u << q;  // remembered: never asked again
-          if (p < total) {
-            base = p;
-            count = min(n_idle, total - p);
-            q_sel = q;
+      if constexpr (UNITS) {
+        uint32_t ask_ahead = kNoTicket;  // the queue to ask for the unit after the one this refill makes current: asked below, behind the hit records
+        // every head sits on its own 128-byte line: same-address atomics serialise at one L2 channel
+        auto ask_ticket = [&](uint32_t q, uint32_t &answer) {
+          // (the empty statement hides that the lane number never changes: the compiler would split the loops below into a copy for
+          // lane 0 and one for the rest, and everything in them would sit in vector registers behind exec masks)
+          uint32_t asker = lane;
+          asm volatile("" : "+v"(asker));
+          if (asker == 0u) answer = atomicAdd(&a.counters[CTR_QUEUE_STRIDE * (q + 1u)], 64u);
+        };
+        const uint32_t NQ = (uint32_t)a.unit_queues, S = (uint32_t)a.n_seeds, G = (uint32_t)a.unit_group;
+        const uint32_t KB = (uint32_t)a.unit_block_log2, n_blocks = (n_chunks + (1u << KB) - 1u) >> KB;
+        uint32_t unit_h = WAVE_GET(W_UNIT_H), unit_left = WAVE_GET(W_UNIT_LEFT), unit_seed = WAVE_GET(W_UNIT_SEED);
+        uint32_t unit_s = MODE == CLWH_ACCUM_VOXEL_CACHE ? WAVE_GET(W_UNIT_S) : 0u;
+        uint32_t ticket_q = WAVE_GET(W_TICKET_Q), queue_dry = WAVE_GET(W_QUEUE_DRY);
+        const uint32_t rank = st == ST_IDLE ? prefix_count(idle_mask) : 64u;  // this idle lane's place among the idle ones
+        uint32_t taken = 0u;                                                  // items handed out in this refill (wave-uniform)
+        uint32_t h = 0xFFFFFFFFu, s = 0u, seed = 0u;                          // this lane's item; 2^32 - 1: none
+        // blocks of 2^unit_block_log2 consecutive chunks are dealt round-robin to the queues (a block past the
+        // last chunk is padding: its items name hits that do not exist and are skipped)
+        auto chunks_of = [&](uint32_t q) { return scalar_u32((n_blocks + NQ - 1u - q) / NQ) << KB; };
+        for (;;) {  // at most two rounds: a fresh unit has 64 items
+          while (unit_left == 0u) {
+            // the next unit becomes the current one
+            uint32_t q = ticket_q, answer = ticket;
+            ticket_q = kNoTicket;
+            if (q == kNoTicket) {
+              // no ticket out (on demand; a queue ran dry; the tail of a queue): ask the first queue, from home on, not known to be dry,
+              // and wait for the answer
+              for (uint32_t tries = 0; tries < NQ && q == kNoTicket; ++tries) {
+                const uint32_t t = home_queue + tries - (home_queue + tries >= NQ ? NQ : 0u);
+                if (chunks_of(t) != 0u && ((queue_dry >> t) & 1u) == 0u) q = t;
+              }
+              if (q == kNoTicket) break;  // every queue is dry
+              ask_ticket(q, answer);
+            }
+            const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)answer, 0) >> 6;  // the unit's number in its queue
+            const uint32_t chunks_q = chunks_of(q), units_q = chunks_q * S;
+            ask_ahead = kNoTicket;
+            if (p >= units_q) {
+              queue_dry |= 1u << q;  // remembered: never asked again
+              continue;
+            }
+            if (p + 1u >= units_q) queue_dry |= 1u << q;
+            else if (ahead) ask_ahead = q;
+            // queue order: groups of `unit_group` chunks, inside a group seed-major -- the seeds of a chunk are
+            // `unit_group` units apart (their accumulation atomics do not collide) yet close enough to find
+            // each other's voxels still in L2
+            const uint32_t g = scalar_u32(p / (G * S)), r = p - g * (G * S);
+            const uint32_t in_group = min(G, chunks_q - g * G);  // the last group may be short
+            const uint32_t s_u = scalar_u32(r / in_group), ch = g * G + (r - s_u * in_group);
+            const uint32_t chunk = ((q + NQ * (ch >> KB)) << KB) + (ch & ((1u << KB) - 1u));
+            if (chunk >= n_chunks) continue;  // padding
+            unit_h = chunk * 64u;
+            unit_left = 64u;
+            unit_s = s_u;
+            unit_seed = (uint32_t)a.seeds[s_u];
+          }
+          if (unit_left == 0u) {
+            exhausted = true;  // every queue is dry and the wave holds no unit
+            break;
+          }
+          const uint32_t take = min(n_idle - taken, unit_left);
+          if (rank - taken < take) {  // (a lane served in the first round: rank < taken, the difference wraps)
+            h = unit_h + (rank - taken);
+            s = unit_s;
+            seed = unit_seed;
+          }
+          unit_h += take;
+          unit_left -= take;
+          taken += take;
+          if (taken == n_idle) break;
+        }
+        WAVE_SET(W_UNIT_H, unit_h); WAVE_SET(W_UNIT_LEFT, unit_left); WAVE_SET(W_UNIT_SEED, unit_seed);
+        if (MODE == CLWH_ACCUM_VOXEL_CACHE) WAVE_SET(W_UNIT_S, unit_s);
+        WAVE_SET(W_TICKET_Q, ask_ahead != kNoTicket ? ask_ahead : ticket_q); WAVE_SET(W_QUEUE_DRY, queue_dry); WAVE_SET(W_EXHAUSTED, exhausted ? 1u : 0u);
+        stats.refill(taken);
+        if (h < n_hits) {  // (an item of the last chunk may name a hit past the last one: skipped)
+          const uint4 *src = reinterpret_cast<const uint4 *>(&a.hits[h]);
+          const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+          const uint32_t plane = hull_cert ? hull_words[h] : 0u;  // (one layout or the other: wave-uniform masks and shift)
+          const f3 hit_origin = f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
+          const f3 hit_direction = f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
+          const f3 start = hit_origin + hit_direction;  // ray_bounce_fake_reflectance's origin (utility_ray.cl:100-103)
+          color = q2.y;
+          const int64_t entry = (int64_t)(((uint64_t)q2.w << 32) | (uint64_t)q2.z);
+          bool granted = true;
+          if (MODE == CLWH_ACCUM_VOXEL_CACHE)
+            granted = a.grants ? s < a.grants[h] : (entry >= 0 && cache_take_token(a.cache, entry, 256u));
+          if (granted) {
+            COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
+            COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
+            COLD(C_ENTRY_LO) = q2.z;
+            COLD(C_ENTRY_HI) = (q2.w & ((1u << entry_hi_bits) - 1u)) | ((plane & 0x1FFFu) << entry_hi_bits) | (plane & (hull_defer ? 0x00FF0000u : 0u)) | (q3.z << 24);
+            COLD(C_PIXEL) = q3.x;
+            COLD(C_HIT) = h;
+            COLD(C_SEED) = seed;
+            COLD(C_FIX) = (uint32_t)(-1 + 2) << 2;
+            COLD(C_BV_R) = 0u; COLD(C_BV_G) = 0u; COLD(C_BV_B) = 0u;
+            r_energy = div255[color & 255u];
+            g_energy = div255[(color >> 8) & 255u];
+            b_energy = div255[(color >> 16) & 255u];
+            o = 1;
+            st = ST_EVENT + EV_START;  // ready to bounce from its primary hit
+          } else if (a.contrib_out) {
+            uint32_t *q = a.contrib_out + ((size_t)(q3.x >> 16) * (size_t)a.launch_w + (q3.x & 0xFFFFu)) * 4;
+            q[0] = 0u; q[1] = 0u; q[2] = 0u; q[3] = 0u;
           }
         }
-      }
-      base = __shfl(base, 0);
-      count = __shfl(count, 0);
-      q_sel = __shfl(q_sel, 0);
-      stats.refill(count);
-      if (count == 0u) {
-        exhausted = true;  // every queue is dry
-      } else if (st == ST_IDLE) {
-        const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull));
-        if (rank < count) {
-          const uint32_t item = base + rank, p = item >> 6;
-          // queue order: groups of `unit_group` chunks, inside a group seed-major -- the seeds of a chunk are
-          // `unit_group` units apart (their accumulation atomics do not collide) yet close enough to find
-          // each other's voxels still in L2
-          // (units per queue stay below 2^24: launch_bounce checks)
-          const uint32_t chunks_q = ((n_blocks + NQ - 1u - q_sel) / NQ) << KB;  // wave-uniform: scalar
-          uint32_t r, c_in;
-          const uint32_t g = udivmod24(p, G * S, r);
-          const uint32_t in_group = min(G, chunks_q - g * G);  // the last group may be short
-          const uint32_t s = udivmod24(r, in_group, c_in), ch = g * G + c_in;
-          const uint32_t chunk = ((q_sel + NQ * (ch >> KB)) << KB) + (ch & ((1u << KB) - 1u));
-          const uint32_t h = chunk * 64u + (item & 63u);
-          if (h < n_hits) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(&a.hits[h]);
-            const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-            const f3 hit_origin = f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
-            const f3 hit_direction = f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
-            const f3 start = hit_origin + hit_direction;  // ray_bounce_fake_reflectance's origin (utility_ray.cl:100-103)
-            color = q2.y;
-            const int64_t entry = (int64_t)(((uint64_t)q2.w << 32) | (uint64_t)q2.z);
-            bool granted = true;
-            if (MODE == CLWH_ACCUM_VOXEL_CACHE)
-              granted = a.grants ? s < a.grants[h] : (entry >= 0 && cache_take_token(a.cache, entry, 256u));
-            if (granted) {
-              COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
-              COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
-              COLD(C_ENTRY_LO) = q2.z;
-              const uint32_t plane = hull_cert ? hull_words[h] : 0u;  // (one layout or the other: wave-uniform masks and shift)
-              COLD(C_ENTRY_HI) = (q2.w & ((1u << entry_hi_bits) - 1u)) | ((plane & 0x1FFFu) << entry_hi_bits) | (plane & (hull_defer ? 0x00FF0000u : 0u)) | (q3.z << 24);
-              COLD(C_PIXEL) = q3.x;
-              COLD(C_HIT) = h;
-              COLD(C_SEED) = (uint32_t)a.seeds[s];
-              COLD(C_FIX) = (uint32_t)(-1 + 2) << 2;
-              COLD(C_BV_R) = 0u; COLD(C_BV_G) = 0u; COLD(C_BV_B) = 0u;
-              r_energy = div255[color & 255u];
-              g_energy = div255[(color >> 8) & 255u];
-              b_energy = div255[(color >> 16) & 255u];
-              o = 1;
-              st = ST_EVENT + EV_START;  // ready to bounce from its primary hit
-            } else if (a.contrib_out) {
-              uint32_t *q = a.contrib_out + ((size_t)(q3.x >> 16) * (size_t)a.launch_w + (q3.x & 0xFFFFu)) * 4;
-              q[0] = 0u; q[1] = 0u; q[2] = 0u; q[3] = 0u;
+        // the ticket for the unit after the one that has just become current: nobody looks at the answer before the next refill that
+        // uses up a unit, a step run or more from here
+        if (ask_ahead != kNoTicket) ask_ticket(ask_ahead, ticket);
+      } else {
+        // every refill takes the next n_idle items of a queue with one atomic, and each lane decodes its own item
+        const uint32_t NQ = (uint32_t)a.unit_queues, S = (uint32_t)a.n_seeds, G = (uint32_t)a.unit_group;
+        const uint32_t KB = (uint32_t)a.unit_block_log2, n_blocks = (n_chunks + (1u << KB) - 1u) >> KB;
+        uint32_t base = 0u, count = 0u, q_sel = 0u;
+        if (lane == 0u) {
+          for (uint32_t tries = 0; tries < NQ && count == 0u; ++tries) {
+            const uint32_t q = (home_queue + tries) % NQ;
+            // blocks of 2^unit_block_log2 consecutive chunks are dealt round-robin to the queues (a block past the
+            // last chunk is padding: its items name hits that do not exist and are skipped)
+            const uint32_t blocks_q = (n_blocks + NQ - 1u - q) / NQ;
+            const uint32_t chunks_q = blocks_q << KB;
+            if (chunks_q == 0u || ((queue_dry_lane0 >> q) & 1u)) continue;
+            const uint32_t total = chunks_q * S * 64u;
+            // every head sits on its own 128-byte line: same-address atomics serialise at one L2 channel
+            const uint32_t p = atomicAdd(&a.counters[CTR_QUEUE_STRIDE * (q + 1u)], n_idle);
+            if (p + n_idle >= total) queue_dry_lane0 |= 1u << q;  // remembered: never asked again
+            if (p < total) {
+              base = p;
+              count = min(n_idle, total - p);
+              q_sel = q;
+            }
+          }
+        }
+        base = __shfl(base, 0);
+        count = __shfl(count, 0);
+        q_sel = __shfl(q_sel, 0);
+        stats.refill(count);
+        if (count == 0u) {
+          exhausted = true;  // every queue is dry
+        } else if (st == ST_IDLE) {
+          const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull));
+          if (rank < count) {
+            const uint32_t item = base + rank, p = item >> 6;
+            // queue order: groups of `unit_group` chunks, inside a group seed-major (as above)
+            // (units per queue stay below 2^24: launch_bounce checks)
+            const uint32_t chunks_q = ((n_blocks + NQ - 1u - q_sel) / NQ) << KB;  // wave-uniform: scalar
+            uint32_t r, c_in;
+            const uint32_t g = udivmod24(p, G * S, r);
+            const uint32_t in_group = min(G, chunks_q - g * G);  // the last group may be short
+            const uint32_t s = udivmod24(r, in_group, c_in), ch = g * G + c_in;
+            const uint32_t chunk = ((q_sel + NQ * (ch >> KB)) << KB) + (ch & ((1u << KB) - 1u));
+            const uint32_t h = chunk * 64u + (item & 63u);
+            if (h < n_hits) {  // (an item of the last chunk may name a hit past the last one: skipped)
+              const uint4 *src = reinterpret_cast<const uint4 *>(&a.hits[h]);
+              const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+              const f3 hit_origin = f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
+              const f3 hit_direction = f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
+              const f3 start = hit_origin + hit_direction;  // ray_bounce_fake_reflectance's origin (utility_ray.cl:100-103)
+              color = q2.y;
+              const int64_t entry = (int64_t)(((uint64_t)q2.w << 32) | (uint64_t)q2.z);
+              bool granted = true;
+              if (MODE == CLWH_ACCUM_VOXEL_CACHE)
+                granted = a.grants ? s < a.grants[h] : (entry >= 0 && cache_take_token(a.cache, entry, 256u));
+              if (granted) {
+                COLD(C_START_X) = __float_as_uint(start.x); COLD(C_START_Y) = __float_as_uint(start.y); COLD(C_START_Z) = __float_as_uint(start.z);
+                COLD(C_NORMAL_X) = q1.z; COLD(C_NORMAL_Y) = q1.w; COLD(C_NORMAL_Z) = q2.x;
+                COLD(C_ENTRY_LO) = q2.z;
+                const uint32_t plane = hull_cert ? hull_words[h] : 0u;  // (one layout or the other: wave-uniform masks and shift)
+                COLD(C_ENTRY_HI) = (q2.w & ((1u << entry_hi_bits) - 1u)) | ((plane & 0x1FFFu) << entry_hi_bits) | (plane & (hull_defer ? 0x00FF0000u : 0u)) | (q3.z << 24);
+                COLD(C_PIXEL) = q3.x;
+                COLD(C_HIT) = h;
+                COLD(C_SEED) = (uint32_t)a.seeds[s];
+                COLD(C_FIX) = (uint32_t)(-1 + 2) << 2;
+                COLD(C_BV_R) = 0u; COLD(C_BV_G) = 0u; COLD(C_BV_B) = 0u;
+                r_energy = div255[color & 255u];
+                g_energy = div255[(color >> 8) & 255u];
+                b_energy = div255[(color >> 16) & 255u];
+                o = 1;
+                st = ST_EVENT + EV_START;  // ready to bounce from its primary hit
+              } else if (a.contrib_out) {
+                uint32_t *q = a.contrib_out + ((size_t)(q3.x >> 16) * (size_t)a.launch_w + (q3.x & 0xFFFFu)) * 4;
+                q[0] = 0u; q[1] = 0u; q[2] = 0u; q[3] = 0u;
+              }
             }
           }
         }
@@ -558,6 +705,8 @@ __global__ __launch_bounds__(kBounceThreads, CLVR_BOUNCE_WAVES_PER_SIMD) void k_
   }
 #undef COLD_ENTRY_HI
 #undef COLD
+#undef WAVE_SET
+#undef WAVE_GET
 }
 
 hipError_t launch_bounce(const RenderArgs &a_in, hipStream_t s) {
@@ -588,11 +737,22 @@ hipError_t launch_bounce(const RenderArgs &a_in, hipStream_t s) {
   a.cert_min_lanes = kCertPhaseMinLanes;
   if (!long_launch) a.cert_min_step = 0;
   if (!bounce_queues_fit(a.n_hits, a.unit_block_log2, a.n_seeds)) return hipErrorInvalidValue;
+  // The refill's form (k_bounce's UNITS).  Whole units per wave cost L2-missing lines (+5.7 % on the headline: a wave owns a unit for
+  // about four refills, so a wider stretch of the queue is in flight and the seeds of a chunk share fewer lines) and save wave
+  // instructions (-4.5 %) and three atomics in four.  The long launch of a table without `gradient` rules gains 2 % by that; the launch
+  // of a `gradient` table runs at the line rate of its misses and lost 6 %, and the short launch, a chain of dependent waits, lost 2 %
+  // to atomic -> scalar decode -> seed -> hit records in a row: both keep the dealing by refill.  So does a volume
+  // beyond the 32-bit step offsets (`small` below; 2048^3): its launch runs at the line rate too, and whole units were measured at
+  // 512^3 only.
+  // A unit is asked for when a wave needs one.  Reserving the next unit a pass ahead (CLWH_TUNE_UNIT_AHEAD=1) was measured slower on
+  // the headline, 2.682 -> 2.704 ms: it stays a knob, off, that nothing but the tests and that A/B turns on.
+  a.unit_ahead = a.unit_ahead > 0 ? 1 : 0;
   const bool g = a.tf.uses_gradient != 0;
   // fewer than 2^23 bricks (up to ~1600^3): every step byte has a 32-bit offset -> the march's 32-bit addressing, with
   // the index terms of the three axes in LDS tables
   const bool small = (uint64_t)a.NBX * (uint64_t)a.NBY * (uint64_t)((a.Z + 7) / 8) < (1ull << 23) &&
                      a.X + a.Y + a.Z <= VolumePacked::kPartsMaxEntries;
+  const bool units = long_launch && !g && small;
   const size_t lds_parts_bytes = small ? (size_t)(a.X + a.Y + a.Z) * sizeof(uint32_t) : 0u;
   // CLWH_TUNE_BOUNCE_RAYS=2: long launches run k_bounce2 (two rays per lane; hit index and seed index share a dword: 2^26 hits)
   const bool two_rays = a.bounce_rays == 2 && long_launch && a.n_hits < (1u << 26) && kBounceThreads == 256;
@@ -602,8 +762,10 @@ hipError_t launch_bounce(const RenderArgs &a_in, hipStream_t s) {
     if (two_rays) {                                                                                 \
       if (small) hipLaunchKernelGGL((k_bounce2<G, M, true>), grid, block, lds_parts_bytes, s, a);  \
       else hipLaunchKernelGGL((k_bounce2<G, M, false>), grid, block, 0, s, a);                     \
-    } else if (small) hipLaunchKernelGGL((k_bounce<G, M, true>), grid, block, lds_parts_bytes, s, a); \
-    else hipLaunchKernelGGL((k_bounce<G, M, false>), grid, block, 0, s, a);                        \
+    } else if (units) {                                                                             \
+      hipLaunchKernelGGL((k_bounce<false, M, true, true>), grid, block, lds_parts_bytes, s, a);    \
+    } else if (small) hipLaunchKernelGGL((k_bounce<G, M, true, false>), grid, block, lds_parts_bytes, s, a); \
+    else hipLaunchKernelGGL((k_bounce<G, M, false, false>), grid, block, 0, s, a);                 \
   } while (0)
   if (a.mode == CLWH_ACCUM_VOXEL_CACHE) {
     if (g) CLVR_LAUNCH_BOUNCE(true, CLWH_ACCUM_VOXEL_CACHE);
