@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -12,18 +12,24 @@
 // of N planes 0.5 voxels apart centred on it (renderer::render_slice: window centre 0 and width 4000; default max).
 // --mesh=VALUE[,below]: no frames; the isosurface of the volume's grid at VALUE is extracted as a triangle mesh (renderer::extract_mesh)
 // and written to the `out` argument as a binary PLY.  frames, width and height are ignored; the JSON line has the counts.
-// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
+// --grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V]: before anything is rendered or extracted, the connected set of voxels with
 // LO <= value <= HI around voxel (X, Y, Z) is grown (renderer::grow_region; ",26": 26-connectivity) and applied to the volume in place
 // (renderer::apply_mask): "keep" (default) sets every other voxel to V, "remove" sets the region itself to V (default -32768).  One
 // JSON line has the region's count, bounding box, mean and extremes.  Goes with any one view option, with --mesh, and with none: the
 // view, the mesh or the path-traced frames then show the masked volume.
-// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
+// --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V]: where --grow runs, all connected components of the window are
 // labelled (renderer::label_components), the K largest or those of at least N voxels (default: all) become the mask
 // (renderer::select_components) and are applied in place like --grow's region.  One JSON line has n_components, n_voxels, the selected
 // rank range ([0, 0]: none) and count / first / bbox of up to the 8 largest.  --grow and --components exclude each other.
 // dilate=R | erode=R | open=R | close=R, an item of --grow and of --components: the mask is dilated, eroded, opened or closed by a ball
 // of R x-voxels (renderer::morph_mask: lengths in 1/16 x-voxel, the axes weighted by the file's voxel sizes) before it is applied; the
 // JSON line then ends with "morph": {"op", "radius_sq", "weight", "count"}, count being the voxels of the mask that is applied.
+// skeleton[=ends|kernel], an item of --grow and of --components: the mask that is applied or shown (after every other item has read it)
+// is thinned to its skeleton without a change of its parts, cavities or tunnels (renderer::thin_mask; ends, the default: the tips of
+// branches stay; kernel: only loops and cavities hold anything).  One more JSON line: {"skeleton": {"mode", "count_in", "count_out",
+// "iterations", "ends", "junction_voxels"}}, ends and junction_voxels being the skeleton's voxels with one and with three or more
+// neighbours among their 26 (renderer::mask_points).  With show the skeleton is overlaid instead of the mask.  The graph is built in
+// Python (scene.skeleton_graph).
 // split=R, an item of --grow and of --components: the mask (after any morphology item) is split into the parts that an erosion by a
 // ball of R x-voxels (erode='s convention) separates: eroded, the pieces ranked largest first, and grown back inside the mask, every
 // voxel to the piece that reaches it first (renderer::split_mask).  One JSON line {"split": {"radius_sq", "weight", "connectivity",
@@ -135,6 +141,14 @@ int main(int argc_in, char const *argv_in[]) {
     }
     return false;
   };
+  int skeleton = -1;  // the skeleton item: 1 = ends (CLWH_THIN_KEEP_ENDS), 0 = kernel, or -1
+  const auto skeleton_item = [&](const std::string &v, bool *ok) {
+    if (v != "skeleton" && v.rfind("skeleton=", 0) != 0) return false;
+    const std::string mode = v == "skeleton" ? "ends" : v.substr(9);
+    *ok = *ok && (mode == "ends" || mode == "kernel") && skeleton < 0;
+    skeleton = mode == "ends" ? 1 : 0;
+    return true;
+  };
   // whether `v` is the split= item; *ok is cleared if its radius is not a number >= 0
   const auto split_item = [&](const std::string &v, bool *ok) {
     if (v.rfind("split=", 0) != 0) return false;
@@ -144,8 +158,8 @@ int main(int argc_in, char const *argv_in[]) {
     split_radius = radius;
     return true;
   };
-  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
-  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kCompsUsage = "(--components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
+  static const char *const kGrowUsage = "(--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]])";
   static const char *const kShedUsage = "(--watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V])";
   static const char *const kCurvedUsage = "(--curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean], with --grow=...,centerline=X,Y,Z)";
   static const char *const kSliceUsage = "(--slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean])";
@@ -232,6 +246,7 @@ int main(int argc_in, char const *argv_in[]) {
           grow_flags |= CLWH_GROW_26;
         } else if (morph_item(v, &ok)) {
         } else if (split_item(v, &ok)) {
+        } else if (skeleton_item(v, &ok)) {
         } else if (v.rfind("centerline=", 0) == 0) {  // X here, Y and Z in the next two fields
           ok = ok && !centerline;
           centerline = true;
@@ -290,6 +305,7 @@ int main(int argc_in, char const *argv_in[]) {
           comps_flags |= CLWH_LABEL_26;
         } else if (morph_item(v, &ok)) {
         } else if (split_item(v, &ok)) {
+        } else if (skeleton_item(v, &ok)) {
         } else if (v == "measure") {
           measure = true;
         } else if (show_item(v, &ok)) {
@@ -479,7 +495,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -534,6 +550,22 @@ int main(int argc_in, char const *argv_in[]) {
     }
   };
 
+  // the skeleton item: the mask is thinned in place, last of all the items that read it; with show it is what is drawn
+  std::string skeleton_line;
+  const auto thin = [&](ui_state &none) {
+    const renderer::thin_summary t = r.thin_mask(none, skeleton == 1);
+    const std::vector<uint32_t> points = r.mask_points(none);
+    uint64_t ends = 0, junctions = 0;
+    for (size_t k = 3; k < points.size(); k += 4) {
+      ends += points[k] == 1u;
+      junctions += points[k] >= 3u;
+    }
+    skeleton_line = std::string("{\"skeleton\": {\"mode\": \"") + (skeleton == 1 ? "ends" : "kernel") + "\", \"count_in\": " + std::to_string(t.count_in) +
+                    ", \"count_out\": " + std::to_string(t.count_out) + ", \"iterations\": " + std::to_string(t.iterations) +
+                    ", \"ends\": " + std::to_string(ends) + ", \"junction_voxels\": " + std::to_string(junctions) + "}}\n";
+    show_source = renderer::OVERLAY_REGION_MASK;
+  };
+
   std::vector<uint32_t> curve;  // the centreline from the seed to its end: what --curved unrolls
   if (grow) {  // first: everything below sees the masked volume
     const auto &size = rv.get_volume_size();
@@ -568,6 +600,7 @@ int main(int argc_in, char const *argv_in[]) {
       const auto &sizes = rv.get_voxel_sizes();
       sections = r.vessel_profile(none, curve, (double)std::min(sizes[0], std::min(sizes[1], sizes[2])) / 4.0);
     }
+    if (skeleton >= 0) thin(none);
     if (show < 0) r.apply_mask(none, grow_fill, grow_remove ? CLWH_MASK_INVERT : 0);
     std::printf("{\"grow\": [%u, %u, %u], \"window\": [%d, %d], \"connectivity\": %d, \"mode\": \"%s\", \"fill\": %d, \"count\": %llu, "
                 "\"bbox_lo\": [%u, %u, %u], \"bbox_hi\": [%u, %u, %u], \"mean\": %.6f, \"min\": %d, \"max\": %d",
@@ -583,7 +616,7 @@ int main(int argc_in, char const *argv_in[]) {
       print_record(measured.stats);
       std::printf("}\n");
     }
-    std::printf("%s", split_line.c_str());
+    std::printf("%s%s", split_line.c_str(), skeleton_line.c_str());
     if (centerline)
       std::printf("{\"centerline\": {\"from\": [%u, %u, %u], \"to\": [%u, %u, %u], \"points\": %llu}}\n", grow_seed[0], grow_seed[1], grow_seed[2],
                   centerline_end[0], centerline_end[1], centerline_end[2], (unsigned long long)(line.size() / 3));
@@ -627,8 +660,9 @@ int main(int argc_in, char const *argv_in[]) {
     if (measure && keep > 0) measured = r.measure_labels(none, (unsigned)std::min<uint64_t>(keep, 256));  // before the mask changes the volume
     if (measure && morph_op >= 0) measured_mask = r.measure_mask(none);  // the morphed mask is no longer the union of the ranks
     if (split_radius >= 0.0f) split(none, (comps_flags & CLWH_LABEL_26) != 0);  // (replaces the labelling: after it was measured)
+    if (skeleton >= 0) thin(none);
     if (show < 0) r.apply_mask(none, comps_fill, comps_remove ? CLWH_MASK_INVERT : 0);
-    if (show >= 0 && morph_op < 0 && keep > 0 && split_radius < 0.0f) {  // the labelling itself: a colour per rank (else the mask, which may be empty or morphed)
+    if (show >= 0 && morph_op < 0 && keep > 0 && split_radius < 0.0f && skeleton < 0) {  // the labelling itself: a colour per rank (else the mask, which may be empty or morphed)
       show_source = renderer::OVERLAY_LABELS;
       show_style.id_hi = (uint32_t)keep;
     }
@@ -660,7 +694,7 @@ int main(int argc_in, char const *argv_in[]) {
       }
       std::printf("}\n");
     }
-    std::printf("%s", split_line.c_str());
+    std::printf("%s%s", split_line.c_str(), skeleton_line.c_str());
   }
 
   if (shed) {  // like --grow: everything below sees the volume as this leaves it

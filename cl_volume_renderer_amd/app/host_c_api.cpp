@@ -174,6 +174,22 @@ unsigned long long clvr_host_morph_mask(clvr_host *h, int op, float radius, unsi
 // renderer::hold_mask / combine_masks: region = region op held
 void clvr_host_hold_mask(clvr_host *h) { h->rend.hold_mask(h->state); }
 void clvr_host_combine_masks(clvr_host *h, int op) { h->rend.combine_masks(h->state, op); }
+// renderer::thin_mask: the region mask thinned in place; result = {count_in, count_out, deleted, iterations}
+void clvr_host_thin_mask(clvr_host *h, int keep_ends, unsigned max_iterations, unsigned long long result[4]) {
+  const renderer::thin_summary s = h->rend.thin_mask(h->state, keep_ends != 0, max_iterations);
+  result[0] = s.count_in;
+  result[1] = s.count_out;
+  result[2] = s.deleted;
+  result[3] = s.iterations;
+}
+// renderer::mask_points of the region mask: returns the number of points, and writes the first min(n, capacity) (x, y, z, n26)
+// quadruples to out (NULL with capacity 0: the count alone)
+unsigned long long clvr_host_mask_points(clvr_host *h, unsigned *out, unsigned long long capacity) {
+  const std::vector<uint32_t> p = h->rend.mask_points(h->state);
+  const size_t n = p.size() / 4u, take = n < capacity ? n : (size_t)capacity;
+  if (out && take) std::memcpy(out, p.data(), take * 4u * sizeof(uint32_t));
+  return n;
+}
 // renderer::geodesic_map of the region mask from n_seeds (x, y, z, id) quadruples into out[Z][Y][X]; result = {reached, max_dist}
 void clvr_host_geodesic_map(clvr_host *h, const unsigned *seeds, unsigned n_seeds, int flags, unsigned cap, unsigned *out,
                             unsigned long long result[2]) {

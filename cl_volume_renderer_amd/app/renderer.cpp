@@ -583,6 +583,46 @@ renderer::morph_summary renderer::morph_mask(struct ui_state &, int op, float ra
   return out;
 }
 
+renderer::thin_summary renderer::thin_mask(struct ui_state &, bool keep_ends, uint32_t max_iterations) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  clwh_thin_result res{};
+  clwh_thin_desc d{};
+  d.mask_in = d.mask_out = region_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.flags = keep_ends ? CLWH_THIN_KEEP_ENDS : 0;
+  d.max_iterations = max_iterations;
+  d.result = &res;
+  clw_fail_hard_on_error(clwh_mask_thin(ctx.get_handle(), &d));
+  region_mask.pull();  // (the host's copy follows the device's, as after morph_mask)
+  thin_summary out;
+  out.count_in = res.count_in;
+  out.count_out = res.count_out;
+  out.deleted = res.deleted;
+  out.iterations = res.iterations;
+  return out;
+}
+
+std::vector<uint32_t> renderer::mask_points(struct ui_state &) {
+  const auto &size = volume->get_volume_size();
+  if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+  uint64_t n = 0;
+  clwh_mask_points_desc d{};
+  d.mask = region_mask.get_device_reference();
+  for (int q = 0; q < 3; ++q) d.dims[q] = (uint32_t)size[q];
+  d.n_points = &n;
+  clw_fail_hard_on_error(clwh_mask_points(ctx.get_handle(), &d));  // the counting call
+  if (n == 0) return {};
+  clw_vector<uint32_t> points(ctx, std::vector<uint32_t>(4 * (size_t)n), false);
+  d.points = points.get_device_reference();
+  d.capacity = n;
+  clw_fail_hard_on_error(clwh_mask_points(ctx.get_handle(), &d));
+  points.pull();
+  std::vector<uint32_t> out(4 * (size_t)n);
+  for (size_t i = 0; i < out.size(); ++i) out[i] = points[i];
+  return out;
+}
+
 void renderer::hold_mask(struct ui_state &) {
   const auto &size = volume->get_volume_size();
   if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask

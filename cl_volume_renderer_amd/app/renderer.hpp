@@ -157,6 +157,17 @@ class renderer : public frame_emitter {
   // without the bone" is grow, hold, morph_mask(DILATE), combine_masks(ANDNOT).
   void hold_mask(struct ui_state &state);
   void combine_masks(struct ui_state &state, int op);
+  // not in the reference: the region thinned in place to its skeleton without a change of its parts, cavities or tunnels
+  // (clwh_mask_thin; keep_ends: the tips of branches stay, a curve skeleton; outside the volume is background, unlike morph_mask).
+  // All four numbers are exact and functions of the region alone.  mask_points: the region's voxels in ascending flat index as
+  // (x, y, z, n26) quadruples, n26 the number of set 26-neighbours (clwh_mask_points); the skeleton's graph is built from them in
+  // Python (scene.skeleton_graph).  Both wait for the device.
+  struct thin_summary {
+    uint64_t count_in = 0, count_out = 0, deleted = 0;
+    uint32_t iterations = 0;
+  };
+  thin_summary thin_mask(struct ui_state &state, bool keep_ends = true, uint32_t max_iterations = 0);
+  std::vector<uint32_t> mask_points(struct ui_state &state);
 
   // not in the reference: shortest paths THROUGH the region mask (clwh_mask_geodesic / clwh_geodesic_trace).  geodesic_weights: the
   // step costs in mask_weights' unit, the Euclidean length of each step in 1/16 of an x-voxel, rounded, within 1 .. 65535 (face per

@@ -656,6 +656,35 @@ hipError_t launch_dist_lines_bits(const DistArgs &a, const uint32_t *src, unsign
 hipError_t launch_mask_combine(const unsigned long long *a, const unsigned long long *b, unsigned long long *out, int32_t X, int32_t Y,
                                int32_t Z, int32_t W64, int32_t op, hipStream_t s);
 
+// ---- topology-preserving thinning and the list of a mask's voxels (thin_kernels.hip; host side clwh_thin.hip), over grow's bit rows
+// and grow's tiles of 64 x 16 x 16 voxels.  The counters' words: count_in (two words), then per iteration of a batch {tiles listed,
+// voxels deleted}.
+constexpr int kThinBatch = 4;  // iterations enqueued between two reads of the device's counters
+struct ThinArgs {
+  unsigned long long *mask;           // M: the caller's mask_out, thinned in place
+  const unsigned long long *anchors;  // or nullptr
+  unsigned long long *cand;           // C of the current iteration
+  uint32_t *stamps;                   // per tile: the last iteration that listed it
+  uint32_t *list;                     // the tiles that hold a candidate
+  uint32_t *counters;                 // 2 + 2 * kThinBatch words
+  int32_t X, Y, Z, W64;
+  int32_t TX, TY, TZ;
+  int32_t dense, keep_ends;
+};
+hipError_t launch_thin_begin(const ThinArgs &a, const unsigned long long *mask_in, hipStream_t s);  // M = mask_in without padding; count_in
+// one iteration in batch slot `slot`: C and the list, then the eight sub-passes; `iteration` (1, 2, ...) is the tiles' stamp
+hipError_t launch_thin_iteration(const ThinArgs &a, uint32_t iteration, int slot, hipStream_t s);
+struct PointsArgs {
+  const unsigned long long *mask;
+  const uint32_t *map;                // or nullptr
+  uint32_t *counts, *bases;           // per 64-bit word of the mask, and one more
+  uint32_t *points, *values;
+  int32_t X, Y, Z, W64;
+};
+hipError_t launch_points_count(const PointsArgs &a, hipStream_t s);
+hipError_t launch_points_scan(void *temp, size_t &temp_bytes, const uint32_t *counts, uint32_t *bases, size_t n, hipStream_t s);
+hipError_t launch_points_fill(const PointsArgs &a, hipStream_t s);
+
 // ---- geodesic distance maps and nearest-seed territories inside a mask, and the path behind a distance (geodesic_kernels.hip; host
 // side clwh_geodesic.hip).  The working keys (dist << 32 | id) are a packed array of one 64-bit word per voxel, [z][y][x] without
 // padding; the volume is cut into tiles of kGeoTileX x kGeoTileY x kGeoTileZ voxels, tile (tx, ty, tz) at (tz * TY + ty) * TX + tx; rounds are grow's.

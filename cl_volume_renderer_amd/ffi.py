@@ -40,6 +40,7 @@ WATERSHED_PLATEAU_MAX, WATERSHED_LEVEL_MAX = 65534, 65535
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
+THIN_KEEP_ENDS, THIN_DENSE = 1, 2
 REGION_MASK, REGION_LABELS = 0, 1
 OVERLAY_FILL, OVERLAY_OUTLINE, OVERLAY_DENSE = 1, 2, 4
 SHADE_LIGHT, SHADE_AO = 0, 1
@@ -359,6 +360,29 @@ class WatershedDesc(C.Structure):
 assert C.sizeof(WatershedDesc) == 88 and C.sizeof(WatershedResult) == 16
 
 
+class ThinResult(C.Structure):
+    _fields_ = [("count_in", C.c_uint64), ("count_out", C.c_uint64), ("deleted", C.c_uint64), ("iterations", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        """the contract's fields: all four are functions of the input"""
+        return {"count_in": int(self.count_in), "count_out": int(self.count_out), "deleted": int(self.deleted),
+                "iterations": int(self.iterations)}
+
+
+class ThinDesc(C.Structure):
+    _fields_ = [("mask_in", C.c_void_p), ("mask_out", C.c_void_p), ("anchors", C.c_void_p), ("dims", C.c_uint32 * 3),
+                ("flags", C.c_int32), ("max_iterations", C.c_uint32), ("reserved", C.c_uint32), ("result", C.POINTER(ThinResult))]
+
+
+class MaskPointsDesc(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("points", C.c_void_p), ("map", C.c_void_p), ("values", C.c_void_p), ("dims", C.c_uint32 * 3),
+                ("flags", C.c_int32), ("capacity", C.c_uint64), ("n_points", C.POINTER(C.c_uint64))]
+
+
+assert C.sizeof(ThinDesc) == 56 and C.sizeof(ThinResult) == 32 and C.sizeof(MaskPointsDesc) == 64
+
+
 class MaskCombineDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dims", C.c_uint32 * 3), ("op", C.c_int32)]
 
@@ -475,6 +499,8 @@ _PROTOTYPES = [
     ("clwh_mask_distance", C.c_int, [C.c_void_p, C.POINTER(DistanceDesc)]),
     ("clwh_mask_morph", C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
+    ("clwh_mask_thin", C.c_int, [C.c_void_p, C.POINTER(ThinDesc)]),
+    ("clwh_mask_points", C.c_int, [C.c_void_p, C.POINTER(MaskPointsDesc)]),
     ("clwh_mask_geodesic", C.c_int, [C.c_void_p, C.POINTER(GeodesicDesc)]),
     ("clwh_geodesic_trace", C.c_int, [C.c_void_p, C.POINTER(GeodesicTraceDesc)]),
     ("clwh_cost_geodesic", C.c_int, [C.c_void_p, C.POINTER(CostGeodesicDesc)]),
@@ -1223,6 +1249,81 @@ class Context:
             out.release()
         _check(status, "clwh_mask_combine")
         return out
+
+    def thin_mask_raw(self, mask_in: Mem, mask_out: Mem, dims, flags=0, anchors: Mem = None, max_iterations=0):
+        """one clwh_mask_thin call: (status, ThinResult); nothing is raised"""
+        d, res = ThinDesc(), ThinResult()
+        d.mask_in, d.mask_out, d.anchors = _handle(mask_in), _handle(mask_out), _handle(anchors)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        d.flags, d.max_iterations = int(flags), int(max_iterations)
+        d.result = C.pointer(res)
+        return lib().clwh_mask_thin(self.h, C.byref(d)), res
+
+    def thin_mask(self, mask: Mem, dims, keep_ends=True, anchors: Mem = None, max_iterations=0, out: Mem = None, dense=False):
+        """the skeleton of `mask` (grow's layout, dims = (X, Y, Z)) by topology-preserving thinning: (mask, ThinResult).  Parts,
+        cavities and tunnels are kept; keep_ends keeps the tips of branches (a curve skeleton), without it only `anchors` (a mask
+        of voxels that are never deleted) and closed loops hold a branch.  Outside the volume is background.  `out` may be `mask`;
+        allocated when none is given.  The call waits for the device."""
+        own = out is None
+        if own:
+            out = self._new_mask(dims)
+        status, res = self.thin_mask_raw(mask, out, dims, (THIN_KEEP_ENDS if keep_ends else 0) | (THIN_DENSE if dense else 0), anchors,
+                                         max_iterations)
+        if status != OK and own:
+            out.release()
+        _check(status, "clwh_mask_thin")
+        return out, res
+
+    def mask_points_raw(self, mask: Mem, dims, points: Mem = None, capacity=0, map: Mem = None, values: Mem = None, flags=0):
+        """one clwh_mask_points call: (status, n_points); nothing is raised"""
+        d = MaskPointsDesc()
+        n = C.c_uint64(0)
+        d.mask, d.points, d.map, d.values = _handle(mask), _handle(points), _handle(map), _handle(values)
+        for k in range(3):
+            d.dims[k] = int(dims[k])
+        d.flags, d.capacity = int(flags), int(capacity)
+        d.n_points = C.pointer(n)
+        return lib().clwh_mask_points(self.h, C.byref(d)), int(n.value)
+
+    def mask_points(self, mask: Mem, dims, map: Mem = None):
+        """the set voxels of `mask` in ascending flat index: (points uint32[n][4] = x, y, z, n26, values uint32[n] | None) as numpy
+        arrays; n26 is the number of set 26-neighbours, values the words of `map` (uint32 [z][y][x] on the device) at the voxels.
+        One counting call, then the filling call; both wait for the device."""
+        status, n = self.mask_points_raw(mask, dims)
+        _check(status, "clwh_mask_points")
+        if n == 0:
+            return np.zeros((0, 4), np.uint32), (np.zeros((0,), np.uint32) if map is not None else None)
+        points = self.buffer(16 * n, np.uint32, (n, 4))
+        values = self.buffer(4 * n, np.uint32, (n,)) if map is not None else None
+        try:
+            status, _ = self.mask_points_raw(mask, dims, points, n, map, values)
+            _check(status, "clwh_mask_points")
+            return points.pull(), (values.pull() if values is not None else None)
+        finally:
+            points.release()
+            if values is not None:
+                values.release()
+
+    def skeleton(self, mask: Mem, dims, spacing=(1, 1, 1), keep_ends=True, anchors: Mem = None):
+        """the skeleton of `mask` as a graph: scene.skeleton_graph's dict (nodes, branches with their lengths in the unit of
+        `spacing` and their mean and minimum radius), with "points" (uint32[n][4]) and "result" (ThinResult) beside.  Four steps: the
+        depth map of the mask (mask_distance to the nearest clear voxel, weights scene.mask_weights(spacing)), thin_mask,
+        mask_points sampling the depth, and the graph on the host.  The call waits for the device."""
+        from . import scene
+
+        depth = self.mask_distance(mask, dims, scene.mask_weights(spacing), to_clear=True)
+        thin = None
+        try:
+            thin, res = self.thin_mask(mask, dims, keep_ends, anchors)
+            points, depths = self.mask_points(thin, dims, depth)
+        finally:
+            depth.release()
+            if thin is not None:
+                thin.release()
+        graph = scene.skeleton_graph(points[:, :3], points[:, 3], spacing, depths)
+        graph["points"], graph["result"] = points, res
+        return graph
 
     @staticmethod
     def _geodesic_weights(d, weights):

@@ -812,6 +812,82 @@ typedef struct clwh_mask_combine_desc {
 } clwh_mask_combine_desc;
 int clwh_mask_combine(clwh_ctx *ctx, const clwh_mask_combine_desc *desc);
 
+/* ---- topology-preserving thinning of a mask (not in the reference): the skeleton of a structure -- "the whole vessel tree, every
+ * branch and fork", "is this a ring or a blob" -- where clwh_mask_morph erodes without regard to topology and clwh_cost_trace needs
+ * both ends named.  The mask is peeled layer by layer, and no voxel is deleted whose removal would change the number of parts,
+ * cavities or tunnels.  Integers and sets only: defined bit for bit, independent of how the device schedules anything.
+ * Conventions.  M = the voxels of the volume (dims = X, Y, Z) whose bit in mask_in (clwh_segment_grow's mask layout) is set; bits at
+ * x >= X and the padding words are ignored on entry and zero on return.  Object voxels are 26-connected, background voxels
+ * 6-connected.  EVERYTHING OUTSIDE THE VOLUME IS BACKGROUND -- unlike clwh_mask_morph, whose border does not erode: a structure that
+ * the scan box cuts through is peeled from its cut face too.
+ * Simple.  Take the 26 neighbours of p as a set N (outside = clear).  p is simple iff (a) N is not empty and is one 26-connected
+ * component, adjacency taken inside the 3 x 3 x 3 block without its centre, and (b) among the CLEAR positions of the 18-neighbourhood
+ * (offsets with |dx| + |dy| + |dz| <= 2) at least one is a face neighbour, and all clear face neighbours lie in one component under
+ * 6-adjacency within that 18-neighbourhood.
+ * Iteration i = 1, 2, ...  On M as it stands at the start of the iteration: B = the voxels of M with a clear or outside face
+ * neighbour; E = the voxels of M with exactly one set 26-neighbour (with CLWH_THIN_KEEP_ENDS; otherwise empty); C = B \ E \ anchors.
+ * Then eight sub-passes s = 0 .. 7 in this order, s = (x & 1) | (y & 1) << 1 | (z & 1) << 2: every voxel of C with parity s that is
+ * still set and is simple in the current M is deleted, all of them at once (two voxels of one parity are never 26-neighbours, so no
+ * order inside a sub-pass matters).  The call stops after the first iteration that deletes nothing, or after max_iterations
+ * (0 = no limit).
+ * Result (HOST, required), all exact and functions of the input alone: count_in = |M| on entry, count_out on return, deleted =
+ * count_in - count_out, iterations = the number of iterations run, the final empty one included.
+ * Buffers.  mask_out may name mask_in's memory; otherwise mask_in is read only.  `anchors` (optional, the same layout, read only) names
+ * voxels that are never deleted; its bits outside M mean nothing.  It must not overlap mask_out unless mask_out is mask_in.
+ * SYNCHRONOUS, like clwh_segment_grow: ordered on the context's stream, returns with mask_out and *result written.  Per iteration one
+ * kernel finds C and lists the tiles of 64 x 16 x 16 voxels that hold a candidate, and one kernel per sub-pass works the listed tiles;
+ * the host reads the counters every four iterations.  CLWH_THIN_DENSE visits every tile: same bytes, by the contract.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or result; mask_in, mask_out or (when given) anchors
+ * that breaks grow's rules for a mask (NULL, an image, not 8-byte aligned); unknown flag bits; a dim of 0, dims beyond the projections'
+ * rule or X * Y * Z > 2^31 - 1.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than the layout needs.  CLWH_ERR_OUT_OF_MEMORY: scratch that
+ * cannot be allocated.  Nothing is written on any of these.  (CLWH_ERR_INTERNAL_OVERFLOW: the loop passed its hard cap of
+ * count_in + 1 iterations, which no input can cause: every iteration but the last deletes a voxel.)
+ * The scratch (one bit per voxel for C, eight bytes per tile, the counters) is kept with the context and holds nothing between calls. */
+enum clwh_thin_flags {
+  CLWH_THIN_KEEP_ENDS = 1,  /* curve skeleton: a voxel with exactly one set 26-neighbour at the start of an iteration stays */
+  CLWH_THIN_DENSE = 2       /* every tile in every sub-pass: same result by contract; for tests and timing */
+};
+typedef struct clwh_thin_result {
+  uint64_t count_in, count_out, deleted;
+  uint32_t iterations;
+  uint32_t reserved;
+} clwh_thin_result;
+typedef struct clwh_thin_desc {
+  clwh_mem *mask_in;          /* plain device buffer in the mask layout */
+  clwh_mem *mask_out;         /* the same layout; may name mask_in's memory */
+  clwh_mem *anchors;          /* optional, the same layout; read only */
+  uint32_t dims[3];           /* X, Y, Z */
+  int32_t flags;              /* clwh_thin_flags */
+  uint32_t max_iterations;    /* 0 = until nothing is deleted */
+  uint32_t reserved;          /* 0 */
+  clwh_thin_result *result;   /* host; required */
+} clwh_thin_desc;
+int clwh_mask_thin(clwh_ctx *ctx, const clwh_thin_desc *desc);
+
+/* ---- the set voxels of a mask as a list (not in the reference): what turns a thin mask into something the host can walk.  The voxels
+ * of the volume (dims = X, Y, Z) whose bit in `mask` (grow's layout; read only; bits at x >= X and padding words ignored) is set, in
+ * ascending flat index (z * Y + y) * X + x.  Point k is uint32[4] = x, y, z, n26 in `points`, n26 = the number of set 26-neighbours
+ * (outside the volume = clear); with `map` (uint32 [Z][Y][X], for instance clwh_mask_distance's depth) values[k] = map at that voxel.
+ * Counting and filling follow clwh_mesh_isosurface: *n_points (HOST, required) always receives the true count; with points NULL and
+ * capacity 0 the call only counts; a count above `capacity` returns CLWH_ERR_SIZE_MISMATCH with the count set and writes nothing to
+ * the buffers.  No atomics: per-word counts, rocprim::exclusive_scan, one lane per word -- the order is fixed.  SYNCHRONOUS.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx, desc or n_points; a mask that breaks grow's rules;
+ * points, map or values that is an image or not 4-byte aligned; map without values or values without map; values without points; a
+ * capacity > 0 with NULL points; flags != 0; dims as for clwh_mask_thin.  CLWH_ERR_SIZE_MISMATCH: a mask smaller than its layout, a map
+ * smaller than 4 * X * Y * Z bytes, points smaller than 16 * capacity or values smaller than 4 * capacity bytes; the capacity rule
+ * above.  CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated (eight bytes per 64-bit word of the mask, kept with the context). */
+typedef struct clwh_mask_points_desc {
+  clwh_mem *mask;             /* plain device buffer in the mask layout; read only */
+  clwh_mem *points;           /* optional uint32[capacity][4] = x, y, z, n26 */
+  clwh_mem *map;              /* optional uint32[Z][Y][X] to sample; read only */
+  clwh_mem *values;           /* uint32[capacity]; with map only */
+  uint32_t dims[3];           /* X, Y, Z */
+  int32_t flags;              /* 0 */
+  uint64_t capacity;
+  uint64_t *n_points;         /* host; required */
+} clwh_mask_points_desc;
+int clwh_mask_points(clwh_ctx *ctx, const clwh_mask_points_desc *desc);
+
 /* ---- geodesic distance maps and nearest-seed territories inside a mask (not in the reference): shortest paths THROUGH a mask from a set
  * of labelled seeds, giving every voxel a distance and the id of its nearest seed.  "These two bones touch: give me each one" is erode,
  * label, and this call with the pieces as seeds; "how far along this vessel" is this call with one seed.  Integers and sets only:
