@@ -1,6 +1,6 @@
 // headless_main.cpp -- the reference application's start-up and frame loop without the window:
 // main (app/main.cpp:8-18) + the parts of ui::run that drive the frame_emitter (app/ui.cpp:170-199, 296).
-// Usage: clvr_headless [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
+// Usage: clvr_headless [--filter=median[,2d]|min=R|max=R|gauss=SIGMA_MM]... [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite | --composite=shaded | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <volume.nrrd> <env.hdr> [frames=16] [width=1920] [height=1080] [out.ppm]
 // Prints one JSON line with the frame time and a checksum of the last frame.  --projection: the frames are intensity projections of
 // the volume (renderer::render_projection, window centre 0 and width 4000, step 0.5) instead of path-traced passes.
 // --composite: the frames are composited through the colour/opacity table of the default selection (renderer::render_composite: tf_composite_lut with lut_first -1024, 4096 entries, opacity 0.05; step 0.5, alpha_stop 0.95,
@@ -66,6 +66,11 @@
 // (renderer::measure_labels).  show draws the labelling over the view like --components' (a colour per id); keep=ID / remove=ID make
 // the territory of one click the mask (renderer::select_components) and apply it like --grow's region; with none of the three the
 // volume is left as it is.  --watershed excludes --grow and --components.
+// --filter=median[,2d] | min=R | max=R | gauss=SIGMA_MM, repeatable: the loaded volume is filtered in place (renderer::filter_volume)
+// before any view, --grow, --components, --watershed or --mesh sees it, one filter per option in the order given: the 3 x 3 x 3
+// median (",2d": 3 x 3 in the slice), the grey minimum / maximum over a box of R voxels (0 .. 16) on every side, or the exact integer
+// Gaussian of SIGMA_MM (renderer::gaussian_weights with the file's voxel sizes: anisotropic voxels get a radius per axis).  The edge
+// is replicated.  One JSON line each: {"filter": {"kind", "radius": [rx, ry, rz]}}.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -116,6 +121,13 @@ int main(int argc_in, char const *argv_in[]) {
   std::vector<uint32_t> shed_seeds;  // (x, y, z, id) quadruples
   int shed_flags = 0, shed_fill = -32768;
   long shed_gmax = 4096, shed_plateau = CLWH_WATERSHED_PLATEAU_MAX, shed_keep = -1, shed_remove = -1;
+  struct filter_spec {
+    int kind;         // clwh_filter_kind
+    uint32_t radius;  // min, max
+    bool flat;        // median,2d
+    double sigma;     // gauss
+  };
+  std::vector<filter_spec> filters;  // --filter, in the order given
   int show = -1;         // the show item: CLWH_OVERLAY_FILL | CLWH_OVERLAY_OUTLINE, or -1
   bool rewrites = false; // a keep, remove or fill= item
   // whether `v` is the show item; *ok is cleared if its style is unknown
@@ -166,7 +178,31 @@ int main(int argc_in, char const *argv_in[]) {
   std::vector<const char *> args{argv_in[0]};
   for (int i = 1; i < argc_in; ++i) {
     const std::string a = argv_in[i];
-    if (a.rfind("--projection=", 0) == 0) {
+    if (a.rfind("--filter", 0) == 0) {
+      const std::string v = a.size() > 9 && a[8] == '=' ? a.substr(9) : "";
+      filter_spec f{CLWH_FILTER_MEDIAN, 1u, false, 0.0};
+      char *end = nullptr;
+      bool ok = true;
+      if (v == "median" || v == "median,2d") {
+        f.flat = v != "median";
+      } else if (v.rfind("min=", 0) == 0 || v.rfind("max=", 0) == 0) {
+        const long n = std::strtol(v.c_str() + 4, &end, 10);
+        ok = v.size() > 4 && *end == '\0' && n >= 0 && n <= CLWH_FILTER_MAX_RADIUS;
+        f.kind = v[1] == 'i' ? CLWH_FILTER_MIN : CLWH_FILTER_MAX;
+        f.radius = (uint32_t)n;
+      } else if (v.rfind("gauss=", 0) == 0) {
+        f.sigma = std::strtod(v.c_str() + 6, &end);
+        ok = v.size() > 6 && *end == '\0' && std::isfinite(f.sigma) && f.sigma >= 0.0;
+        f.kind = CLWH_FILTER_SMOOTH;
+      } else {
+        ok = false;
+      }
+      if (!ok) {
+        std::cout << "Unknown option '" << a << "' (--filter=median[,2d]|min=R|max=R|gauss=SIGMA_MM)\n";
+        return 1;
+      }
+      filters.push_back(f);
+    } else if (a.rfind("--projection=", 0) == 0) {
       const std::string m = a.substr(13);
       projection = m == "max" ? CLWH_PROJ_MAX : m == "min" ? CLWH_PROJ_MIN : m == "mean" ? CLWH_PROJ_MEAN : -2;
       if (projection == -2) {
@@ -495,7 +531,7 @@ int main(int argc_in, char const *argv_in[]) {
   const int argc = (int)args.size();
   char const *const *argv = args.data();
   if (argc < 3) {
-    std::cout << "Usage: " << argv[0] << " [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
+    std::cout << "Usage: " << argv[0] << " [--filter=median[,2d]|min=R|max=R|gauss=SIGMA_MM]... [--grow=X,Y,Z,LO,HI[,26][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,centerline=X,Y,Z][,profile][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --components=LO,HI[,26][,largest=K | min=N][,dilate=R | erode=R | open=R | close=R][,split=R][,skeleton[=ends|kernel]][,measure][,keep|remove][,fill=V][,show[=fill|outline|both]] | --watershed=X:Y:Z,X:Y:Z[,...][,26][,gmax=G][,plateau=N][,show[=fill|outline|both] | keep=ID | remove=ID][,fill=V]] [--projection=max|min|mean | --composite[=shaded] | --isosurface=VALUE[,below] | --slice=axial|coronal|sagittal[,POSITION][,slab=N][,max|min|mean] | --curved[=WINDOW_MM][,angle=DEG][,slab=N][,max|min|mean] | --mesh=VALUE[,below]] <path to nrrd file> <path to envmap> [frames] [width] [height] [out.ppm]\n";
     return 1;
   }
   const int frames = argc > 3 ? std::atoi(argv[3]) : 16;
@@ -523,6 +559,25 @@ int main(int argc_in, char const *argv_in[]) {
   image em = iloader.load_file(argv[2]);
   env_map emap(ctx, em);
   emitter->image_set(&rv, &emap);
+
+  {  // --filter: before anything reads the volume
+    ui_state none{argv[1], true, height, width, Position3D(0, 0, 0), {0.f, 0.f}, true};
+    for (const filter_spec &f : filters) {
+      uint32_t radius[3] = {f.radius, f.radius, f.radius};
+      if (f.kind == CLWH_FILTER_MEDIAN) radius[2] = f.flat ? 0u : 1u;
+      if (f.kind == CLWH_FILTER_SMOOTH) {
+        const auto &sizes = rv.get_voxel_sizes();
+        const double spacing[3] = {(double)sizes[0], (double)sizes[1], (double)sizes[2]};
+        const std::array<std::vector<uint16_t>, 3> w = renderer::gaussian_weights(f.sigma, spacing);
+        for (int q = 0; q < 3; ++q) radius[q] = (uint32_t)w[q].size() - 1u;
+        r.filter_volume(none, f.kind, radius, &w);
+      } else {
+        r.filter_volume(none, f.kind, radius);
+      }
+      static const char *const kFilterNames[4] = {"median", "min", "max", "gauss"};
+      std::printf("{\"filter\": {\"kind\": \"%s\", \"radius\": [%u, %u, %u]}}\n", kFilterNames[f.kind], radius[0], radius[1], radius[2]);
+    }
+  }
 
   int show_source = renderer::OVERLAY_REGION_MASK;  // what the show item draws
   renderer::overlay_style show_style;

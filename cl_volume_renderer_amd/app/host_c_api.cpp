@@ -144,6 +144,25 @@ void clvr_host_grow_region(clvr_host *h, const unsigned *seeds, unsigned n_seeds
 }
 // renderer::apply_mask: the last grown mask applied to the renderer's volume in place
 void clvr_host_apply_mask(clvr_host *h, int fill, int flags) { h->rend.apply_mask(h->state, fill, flags); }
+// renderer::filter_volume: the renderer's volume filtered in place; kind = clwh_filter_kind, SMOOTH with renderer::gaussian_weights of
+// sigma_mm and the volume's voxel sizes (its radii are returned in radius), masked != 0: only inside the last mask.  With `out` the
+// device's volume is read back into it (X * Y * Z shorts)
+void clvr_host_filter_volume(clvr_host *h, int kind, unsigned radius[3], double sigma_mm, int masked, short *out) {
+  if (kind == CLWH_FILTER_SMOOTH) {
+    const auto &sizes = h->rv->get_voxel_sizes();
+    const double spacing[3] = {(double)sizes[0], (double)sizes[1], (double)sizes[2]};
+    const std::array<std::vector<uint16_t>, 3> w = renderer::gaussian_weights(sigma_mm, spacing);
+    for (int q = 0; q < 3; ++q) radius[q] = (unsigned)w[q].size() - 1u;
+    h->rend.filter_volume(h->state, kind, radius, &w, masked != 0);
+  } else {
+    h->rend.filter_volume(h->state, kind, radius, nullptr, masked != 0);
+  }
+  if (out) {
+    clwh_mem *m = h->rv->get_reference_volume().get_device_reference();
+    const auto &size = h->rv->get_volume_size();
+    clw_fail_hard_on_error(clwh_mem_pull(h->ctx.get_handle(), m, out, size[0] * size[1] * size[2] * sizeof(short)));
+  }
+}
 // renderer::label_components: *n_components and *n_voxels, and up to top_k records (clwh_label_component, 48 bytes each) into
 // `records`; returns how many were written.  The labels stay on the device
 unsigned clvr_host_label_components(clvr_host *h, int lo, int hi, int flags, unsigned top_k, unsigned long long *n_components,

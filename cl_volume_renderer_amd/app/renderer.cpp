@@ -489,6 +489,50 @@ void renderer::apply_mask(struct ui_state &, int fill, int flags) {
   clw_fail_hard_on_error(clwh_volume_apply_mask(ctx.get_handle(), &d));
 }
 
+void renderer::filter_volume(struct ui_state &, int kind, const uint32_t radius[3], const std::array<std::vector<uint16_t>, 3> *weights, bool masked) {
+  clwh_filter_desc d{};
+  d.volume_in = d.volume_out = volume->get_reference_volume().get_device_reference();
+  if (masked) {
+    const auto &size = volume->get_volume_size();
+    if (region_mask.size() != 2 * ((size[0] + 63) / 64) * size[1] * size[2]) clw_fail_hard_on_error(CLWH_ERR_SIZE_MISMATCH);  // no mask
+    d.mask = region_mask.get_device_reference();
+  }
+  d.kind = kind;
+  for (int q = 0; q < 3; ++q) {
+    d.radius[q] = radius[q];
+    if (weights) {
+      if ((*weights)[q].size() != (size_t)radius[q] + 1u) clw_fail_hard_on_error(CLWH_ERR_INVALID_VALUE);
+      d.weights[q] = (*weights)[q].data();
+    }
+  }
+  clw_fail_hard_on_error(clwh_volume_filter(ctx.get_handle(), &d));
+}
+
+std::array<std::vector<uint16_t>, 3> renderer::gaussian_weights(double sigma_mm, const double spacing[3]) {
+  std::array<std::vector<uint16_t>, 3> out;
+  for (int c = 0; c < 3; ++c) {
+    const double s = sigma_mm / spacing[c];
+    if (!(s > 0.0)) {
+      out[c] = {4096};
+      continue;
+    }
+    const int r = std::min(16, std::max(1, (int)std::ceil(3.0 * s)));
+    std::vector<double> g((size_t)r + 1u);
+    for (int k = 0; k <= r; ++k) g[(size_t)k] = std::exp(-(double)(k * k) / (2.0 * s * s));
+    double n = g[0];
+    for (int k = 1; k <= r; ++k) n += 2.0 * g[(size_t)k];
+    std::vector<uint16_t> w((size_t)r + 1u);
+    int rest = 4096;
+    for (int k = 1; k <= r; ++k) {
+      w[(size_t)k] = (uint16_t)std::floor(4096.0 * g[(size_t)k] / n + 0.5);
+      rest -= 2 * (int)w[(size_t)k];
+    }
+    w[0] = (uint16_t)rest;
+    out[c] = w;
+  }
+  return out;
+}
+
 renderer::component_summary renderer::label_components(struct ui_state &, int lo, int hi, int flags, unsigned top_k) {
   const auto &size = volume->get_volume_size();
   const size_t voxels = (size_t)size[0] * size[1] * size[2], mask_words = 2 * ((size[0] + 63) / 64) * size[1] * size[2];

@@ -1,6 +1,7 @@
 // renderer.hpp -- the renderer the SDL/ImGui application talks to: same class name, base class and
 // public methods as the reference's app/renderer.hpp:10-29, so `ui::run(&renderer)` is a drop-in.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -121,6 +122,15 @@ class renderer : public frame_emitter {
   // CLWH_MASK_INVERT those inside.  Every view, the mesh and -- after the next flush_changes -- the path tracer then show the masked
   // volume.  The host copy of the volume keeps the loaded values.
   void apply_mask(struct ui_state &state, int fill = -32768, int flags = 0);
+  // not in the reference: the volume filtered in place (clwh_volume_filter) before it is segmented: kind = CLWH_FILTER_MEDIAN (radii 0
+  // or 1), CLWH_FILTER_MIN / CLWH_FILTER_MAX (grey erosion / dilation by the box, radii up to 16) or CLWH_FILTER_SMOOTH with `weights`
+  // (radius[c] = weights[c].size() - 1); the edge is replicated.  masked: only the voxels of the region mask change.  Like apply_mask it
+  // rewrites the device's volume, every view shows the result, and the host copy keeps the loaded values.  gaussian_weights is
+  // scene.gaussian_weights bit for bit: s = sigma_mm / spacing[c]; s <= 0 gives {4096}; r = min(16, max(1, ceil(3 s))),
+  // g_k = exp(-k^2 / (2 s^2)), n = g_0 + 2 sum g_k, w_k = floor(4096 g_k / n + 0.5) for k >= 1, w_0 = 4096 - 2 sum w_k.
+  void filter_volume(struct ui_state &state, int kind, const uint32_t radius[3], const std::array<std::vector<uint16_t>, 3> *weights = nullptr,
+                     bool masked = false);
+  static std::array<std::vector<uint16_t>, 3> gaussian_weights(double sigma_mm, const double spacing[3]);
 
   // not in the reference: all connected components of the window lo <= value <= hi at once (clwh_segment_label; flags: CLWH_LABEL_26 |
   // CLWH_LABEL_FROM_MASK, the latter splits the last mask into its parts), ranked by descending voxel count: their number, the

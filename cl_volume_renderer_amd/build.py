@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libclwhip.so")
 
-SOURCES = ["clwh_context.hip", "clwh_render.hip", "clwh_sdf.hip", "clwh_launch.hip", "clwh_views.hip", "clwh_mesh.hip", "clwh_grow.hip", "clwh_label.hip", "clwh_distance.hip", "clwh_geodesic.hip", "clwh_costpath.hip", "clwh_watershed.hip", "clwh_thin.hip", "clwh_region_stats.hip", "render_kernels.hip", "scene_kernels.hip", "primary_kernels.hip", "accumulate_kernels.hip", "sdf_layer_kernels.hip", "sdf_front_kernels.hip", "sdf_bits_kernels.hip", "sdf_bits_layers_kernels.hip", "volume_kernels.hip", "exchange_kernels.hip", "probe_kernels.hip", "projection_kernels.hip", "composite_kernels.hip", "isosurface_kernels.hip", "slice_kernels.hip", "curved_kernels.hip", "overlay_kernels.hip", "mesh_kernels.hip", "tile_work_kernels.hip", "grow_kernels.hip", "label_kernels.hip", "distance_kernels.hip", "geodesic_kernels.hip", "costpath_kernels.hip", "watershed_kernels.hip", "thin_kernels.hip", "region_stats_kernels.hip", "tf_parse.cpp", "tf_jit.cpp"]
+SOURCES = ["clwh_context.hip", "clwh_render.hip", "clwh_sdf.hip", "clwh_launch.hip", "clwh_views.hip", "clwh_mesh.hip", "clwh_grow.hip", "clwh_label.hip", "clwh_distance.hip", "clwh_geodesic.hip", "clwh_costpath.hip", "clwh_watershed.hip", "clwh_thin.hip", "clwh_filter.hip", "clwh_region_stats.hip", "render_kernels.hip", "scene_kernels.hip", "primary_kernels.hip", "accumulate_kernels.hip", "sdf_layer_kernels.hip", "sdf_front_kernels.hip", "sdf_bits_kernels.hip", "sdf_bits_layers_kernels.hip", "volume_kernels.hip", "exchange_kernels.hip", "probe_kernels.hip", "projection_kernels.hip", "composite_kernels.hip", "isosurface_kernels.hip", "slice_kernels.hip", "curved_kernels.hip", "overlay_kernels.hip", "mesh_kernels.hip", "tile_work_kernels.hip", "grow_kernels.hip", "label_kernels.hip", "distance_kernels.hip", "geodesic_kernels.hip", "costpath_kernels.hip", "watershed_kernels.hip", "thin_kernels.hip", "filter_kernels.hip", "region_stats_kernels.hip", "tf_parse.cpp", "tf_jit.cpp"]
 HEADERS = ["clwh_internal.hpp", "clwh_host.hpp", "device_math.hpp", "render_device.hpp", "bounce_device.hpp", "bounce_two_rays.hpp", "sdf_device.hpp", "packed_volume.hpp", "env_fast.hpp", "view_device.hpp", "trilinear_device.hpp", "mask_device.hpp", "tile_work_device.hpp"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -2,7 +2,7 @@
 // memory and events, and the helpers the runtime's files share (clwh_context.hip: contexts, memory objects, timing, transfer
 // functions; clwh_render.hip; clwh_sdf.hip; clwh_launch.hip: clwh_kernel_get / clwh_launch; clwh_views.hip: projections, compositing, isosurfaces, slices, curved reformats, section profiles and overlays; clwh_mesh.hip: the
 // isosurface mesh; clwh_grow.hip: region growing and masked volumes; clwh_label.hip: component labelling;
-// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_watershed.hip: the seeded watershed of a cost field; clwh_thin.hip: thinning and the list of a mask's voxels; clwh_region_stats.hip: statistics of masks and labels).
+// clwh_distance.hip: distance maps of masks, ball morphology and mask algebra; clwh_geodesic.hip: geodesic maps and paths; clwh_costpath.hip: the same through a cost field; clwh_watershed.hip: the seeded watershed of a cost field; clwh_thin.hip: thinning and the list of a mask's voxels; clwh_filter.hip: the volume filters; clwh_region_stats.hip: statistics of masks and labels).
 // No kernel needs this header.
 #pragma once
 
@@ -289,6 +289,12 @@ struct ThinScratch {
   TileScratch work;
 };
 
+// clwh_volume_filter's scratch: at most two int16 copies of the volume, between the passes and for the in-place case.  Every call
+// rewrites what it reads: only the allocations are kept.
+struct FilterScratch {
+  DeviceBuffer a, b;
+};
+
 // clwh_mask_statistics' scratch: the one record the blocks add to, with the histogram's two tails behind it (a clwh_mask_stats_result).
 // Every call rewrites what it reads: only the allocation is kept.
 struct RegionStatsScratch {
@@ -360,6 +366,7 @@ struct clwh_ctx {
   clvr::CurveScratch curve;
   clvr::RegionStatsScratch region_stats;
   clvr::ThinScratch thin;
+  clvr::FilterScratch filter;
   clvr::OverlayScratch overlay;
   clvr::ProjectionData proj;
   clvr::DeviceBuffer bilateral_weights;  // 13 x 17 tap weights of the bilateral volume filter (built on first use)

@@ -685,6 +685,21 @@ hipError_t launch_points_count(const PointsArgs &a, hipStream_t s);
 hipError_t launch_points_scan(void *temp, size_t &temp_bytes, const uint32_t *counts, uint32_t *bases, size_t n, hipStream_t s);
 hipError_t launch_points_fill(const PointsArgs &a, hipStream_t s);
 
+// ---- volume filters: median, grey min / max, exact integer smoothing (filter_kernels.hip; host side clwh_filter.hip).  One launch is
+// the whole median or one line pass; `last` passes select by the mask and read the unfiltered volume at its clear bits.
+struct FilterArgs {
+  const int16_t *src;   // what the launch filters; never dst
+  int16_t *dst;
+  const int16_t *orig;  // V, read where the mask's bit is clear (with a mask only); may be dst
+  const uint8_t *mask;  // grow's layout as bytes, or nullptr: every voxel takes the filtered value
+  int32_t X, Y, Z, W64;
+  int32_t axis, r;      // line passes: 0, 1, 2 and the radius along it, 1 .. CLWH_FILTER_MAX_RADIUS
+  int32_t wide_src, wide_dst, wide_orig;  // rows_of_8 of the three arrays
+  uint16_t w[CLWH_FILTER_MAX_RADIUS + 1];  // SMOOTH: the axis' weights by |offset|
+};
+hipError_t launch_filter_median(const FilterArgs &a, int rx, int ry, int rz, hipStream_t s);  // radii 0 or 1, not all 0
+hipError_t launch_filter_line(const FilterArgs &a, int kind, hipStream_t s);                  // kind: CLWH_FILTER_MIN, _MAX or _SMOOTH
+
 // ---- geodesic distance maps and nearest-seed territories inside a mask, and the path behind a distance (geodesic_kernels.hip; host
 // side clwh_geodesic.hip).  The working keys (dist << 32 | id) are a packed array of one 64-bit word per voxel, [z][y][x] without
 // padding; the volume is cut into tiles of kGeoTileX x kGeoTileY x kGeoTileZ voxels, tile (tx, ty, tz) at (tz * TY + ty) * TX + tx; rounds are grow's.

@@ -41,6 +41,8 @@ MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MASK_AND, MASK_OR, MASK_XOR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3, 4
 MASK_INVERT = 1
 THIN_KEEP_ENDS, THIN_DENSE = 1, 2
+FILTER_MEDIAN, FILTER_MIN, FILTER_MAX, FILTER_SMOOTH = 0, 1, 2, 3
+FILTER_MAX_RADIUS, FILTER_WEIGHT_SUM = 16, 4096
 REGION_MASK, REGION_LABELS = 0, 1
 OVERLAY_FILL, OVERLAY_OUTLINE, OVERLAY_DENSE = 1, 2, 4
 SHADE_LIGHT, SHADE_AO = 0, 1
@@ -230,6 +232,17 @@ class ApplyMaskDesc(C.Structure):
         ("volume_in", C.c_void_p), ("volume_out", C.c_void_p), ("mask", C.c_void_p),
         ("fill", C.c_int32), ("flags", C.c_int32),
     ]
+
+
+class FilterDesc(C.Structure):
+    _fields_ = [
+        ("volume_in", C.c_void_p), ("volume_out", C.c_void_p), ("mask", C.c_void_p),
+        ("kind", C.c_int32), ("flags", C.c_int32), ("radius", C.c_uint32 * 3),
+        ("weights", C.POINTER(C.c_uint16) * 3),
+    ]
+
+
+assert C.sizeof(FilterDesc) == 72
 
 
 class LabelComponent(C.Structure):
@@ -499,6 +512,7 @@ _PROTOTYPES = [
     ("clwh_mask_distance", C.c_int, [C.c_void_p, C.POINTER(DistanceDesc)]),
     ("clwh_mask_morph", C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
     ("clwh_mask_combine", C.c_int, [C.c_void_p, C.POINTER(MaskCombineDesc)]),
+    ("clwh_volume_filter", C.c_int, [C.c_void_p, C.POINTER(FilterDesc)]),
     ("clwh_mask_thin", C.c_int, [C.c_void_p, C.POINTER(ThinDesc)]),
     ("clwh_mask_points", C.c_int, [C.c_void_p, C.POINTER(MaskPointsDesc)]),
     ("clwh_mask_geodesic", C.c_int, [C.c_void_p, C.POINTER(GeodesicDesc)]),
@@ -1087,6 +1101,31 @@ class Context:
         rewrite of `out`: every view of it rebuilds its derived data at its next use."""
         _check(self.apply_mask_raw(volume, mask, out if out is not None else volume, fill, MASK_INVERT if invert else 0),
                "clwh_volume_apply_mask")
+
+    def filter_volume_raw(self, volume_in: Mem, volume_out: Mem, kind, radius, weights=None, mask: Mem = None, flags=0):
+        """one clwh_volume_filter call: its status; nothing is raised.  weights: None, or three sequences (an entry may be None: a NULL
+        pointer) of uint16, tap 0 first"""
+        d = FilterDesc()
+        d.volume_in, d.volume_out, d.mask = _handle(volume_in), _handle(volume_out), _handle(mask)
+        d.kind, d.flags = int(kind), int(flags)
+        keep = []  # the arrays live until the call returns: it copies them
+        for k in range(3):
+            d.radius[k] = int(radius[k])
+            if weights is not None and weights[k] is not None:
+                w = np.ascontiguousarray(weights[k], np.uint16)
+                keep.append(w)
+                d.weights[k] = w.ctypes.data_as(C.POINTER(C.c_uint16))
+        return lib().clwh_volume_filter(self.h, C.byref(d))
+
+    def filter_volume(self, volume: Mem, kind, radius=(1, 1, 1), weights=None, mask: Mem = None, out: Mem = None):
+        """`volume` filtered over the box |dx| <= rx, |dy| <= ry, |dz| <= rz with the edge replicated: FILTER_MEDIAN (radii 0 or 1),
+        FILTER_MIN / FILTER_MAX (grey erosion / dilation, radii up to 16) or FILTER_SMOOTH (three exact integer passes x, y, z with
+        `weights`, three uint16 arrays as scene.gaussian_weights / scene.binomial_weights return them; the radii are taken from their
+        lengths).  With `mask` (grow's layout) only the voxels whose bit is set change.  out=None: in place.  Counts as a rewrite of
+        `out`: every view of it rebuilds its derived data at its next use."""
+        if kind == FILTER_SMOOTH and weights is not None:
+            radius = tuple(len(w) - 1 for w in weights)
+        _check(self.filter_volume_raw(volume, out if out is not None else volume, kind, radius, weights, mask), "clwh_volume_filter")
 
     def label_components_raw(self, volume: Mem, lo, hi, flags=0, box=None, mask: Mem = None, labels: Mem = None, components: Mem = None,
                              capacity=0):

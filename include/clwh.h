@@ -662,6 +662,48 @@ typedef struct clwh_apply_mask_desc {
 } clwh_apply_mask_desc;
 int clwh_volume_apply_mask(clwh_ctx *ctx, const clwh_apply_mask_desc *desc);
 
+/* ---- volume filters (not in the reference): "denoise, then segment".  The median (the speckle remover that keeps edges), grey erosion
+ * and dilation by a box, and a separable smoothing whose integer weights the caller derives from millimetres (scene.gaussian_weights),
+ * over the int16 volume and into a volume, so every view, the mesher, the path tracer and every segmentation call read the result
+ * unchanged.  Integers only: defined bit for bit.  The reference's bilateral_filter (clwh_launch) is a different filter and unchanged.
+ * Neighbourhood and border.  V = volume_in (dims X, Y, Z); N(p) = the box of offsets |dx| <= rx, |dy| <= ry, |dz| <= rz, radius =
+ * (rx, ry, rz).  Every tap is read at the coordinate CLAMPED to the volume per axis, V(clamp(x + dx, 0, X - 1), ...): the edge is
+ * replicated.  (The reference's zero border would pull a -1000 HU air border towards 0.)
+ * CLWH_FILTER_MEDIAN.  Every radius 0 or 1: n = 1, 3, 9 or 27 taps; (1, 1, 0) is the in-plane median for thick slices.  F(p) = element
+ * (n - 1) / 2 of the sorted multiset of the n clamped taps; duplicates from clamping count as often as they occur.
+ * CLWH_FILTER_MIN / CLWH_FILTER_MAX.  Every radius 0 .. CLWH_FILTER_MAX_RADIUS.  F(p) = the minimum / maximum over the clamped taps.
+ * CLWH_FILTER_SMOOTH.  Every radius 0 .. CLWH_FILTER_MAX_RADIUS.  weights[c][k] (HOST, uint16[radius[c] + 1], copied before the call
+ * returns) is the weight of the taps +-k along axis c, and weights[c][0] + 2 * sum over k >= 1 of weights[c][k] ==
+ * CLWH_FILTER_WEIGHT_SUM exactly, per axis.  Three passes in the order x, y, z, each rounded to int16 on its own:
+ *   T(p) = (sum over k of w[|k|] * S(clamp(p + k e_c)) + 2048) >> 12,
+ * the sum in 32-bit signed arithmetic (|sum| <= 2^27), the shift arithmetic (floor).  T stays within the line's extremes (no clamp),
+ * constant volumes pass through unchanged, and an axis of radius 0 (weights {4096}) is the identity.  The order of the passes and the
+ * rounding per pass are part of the contract: another order or one rounding at the end give other bytes.
+ * Output.  out(p) = F(p) where mask is NULL or its bit at p is set (clwh_segment_grow's mask layout, read only, padding ignored whatever
+ * it holds); elsewhere out(p) = V(p).  F always reads the unfiltered V, also next to clear bits.  volume_out may be volume_in, or another
+ * handle to the same pointer: the result is as if all of V had been read before anything was written.
+ * Asynchronous and ordered on the context's stream, like clwh_volume_apply_mask, and a rewrite of volume_out in exactly its sense: the
+ * same version bump.  Axes of radius 0 launch nothing; all radii 0 is a copy.  Scratch (at most two int16 copies of the volume) is kept
+ * with the context and holds nothing between calls.
+ * Errors, tested in this order of kinds.  CLWH_ERR_INVALID_VALUE: a NULL ctx or desc; a NULL or wrong-kind volume_in or volume_out; a
+ * mask that is given and is an image or whose device pointer is not 8-byte aligned; an unknown kind; flags != 0; a radius above the
+ * kind's limit; SMOOTH with a NULL weights[c] or a sum other than 4096 (weights of other kinds are ignored); volume dims beyond the
+ * projections' rule.  CLWH_ERR_SIZE_MISMATCH: volumes of different dims; a mask smaller than the layout needs.
+ * CLWH_ERR_OUT_OF_MEMORY: scratch that cannot be allocated.  Nothing is written and no version is bumped on any of these. */
+enum clwh_filter_kind { CLWH_FILTER_MEDIAN = 0, CLWH_FILTER_MIN = 1, CLWH_FILTER_MAX = 2, CLWH_FILTER_SMOOTH = 3 };
+#define CLWH_FILTER_MAX_RADIUS 16
+#define CLWH_FILTER_WEIGHT_SUM 4096
+typedef struct clwh_filter_desc {
+  clwh_mem *volume_in;        /* S16 3-D image, 1 channel */
+  clwh_mem *volume_out;       /* the same dims; may name volume_in's memory */
+  clwh_mem *mask;             /* optional; grow's mask layout; read only */
+  int32_t kind;               /* clwh_filter_kind */
+  int32_t flags;              /* 0 */
+  uint32_t radius[3];         /* rx, ry, rz in voxels */
+  const uint16_t *weights[3]; /* host; SMOOTH only: weights[c] = uint16[radius[c] + 1], tap 0 first */
+} clwh_filter_desc;
+int clwh_volume_filter(clwh_ctx *ctx, const clwh_filter_desc *desc);
+
 /* ---- connected-component labelling (not in the reference): ALL components of a value window at once, ranked largest first, where
  * clwh_segment_grow gives the one under the seeds.  "How many pieces", "keep the largest", "drop the specks below N voxels" are then a
  * table lookup and a rank interval.  Integers and sets only: defined bit for bit, independent of how the device schedules anything.
